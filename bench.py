@@ -87,6 +87,10 @@ def parse():
     ap.add_argument("--mode", default="sequences", choices=["sequences", "frames"],
                     help="sequences (default): one sequence per GPU, weak scaling, no data-path exchange.  frames: ONE sequence, batches of "
                          "frames detected round-robin over the GPUs, detections sent to the tracker on rank 0 (strong scaling, SURVEY 8e)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the pinned-host and coupled timed passes, the launch-list "
+                    "probe and PMC traffic, the cfg4 ReID figures, latency mode, the tracker roofline, the CPU baseline with parity, the cfg3 / cfg4 child runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): "
+                    "detections, detection_counts, tracks, track_counts (rank 0's sequence)")
     args = ap.parse_args()
     # under a launcher (torchrun / the driver's torch.distributed.run / SLURM: WORLD_SIZE with RANK or LOCAL_RANK) the world size comes from the environment and
     # --gpus, if given, must agree; WORLD_SIZE=1 without a rank variable is a container default, not a launcher
@@ -111,6 +115,22 @@ LEVEL_QUOTA = (0.55, 0.2, 0.15, 0.1)      # share of the candidates each Detect 
 def plant_objectness_bias(det, frames, target=2000):
     """~`target` anchors per frame above conf_thres = 0.01 (state dict and device blob both updated), every Detect level supplying its quota of them"""
     return det.plant_objectness_bias(frames, target, level_quota=LEVEL_QUOTA if len(det.plan.heads) == len(LEVEL_QUOTA) else None)
+
+
+def dump_outputs(path, dets, ndets, rows, cap_t):
+    """--dump-outputs: what a caller of the timed path receives for the frames of its last step -- the detector's NMS output (B, 300, 6)
+    [x1, y1, x2, y2, conf, cls] and the tracker's returned tracks (B, cap_t, 7) [id, x, y, w, h, cls, score], each with its per-frame count
+    and with the rows past that count zeroed (buffer contents a caller never reads)"""
+    nd = ndets.cpu().numpy().astype(np.int64)
+    d = dets.cpu().numpy().astype(np.float32)
+    d[np.arange(d.shape[1])[None, :] >= nd[:, None]] = 0
+    r = rows.cpu().numpy()
+    nt = np.ascontiguousarray(r[:, cap_t]).view(np.int32)[:, 0].astype(np.int64)      # row cap_t of a frame starts with its track count
+    t = r[:, :cap_t, :7].astype(np.float64)
+    t[np.arange(cap_t)[None, :] >= nt[:, None]] = 0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("detections", d), ("detection_counts", nd.astype(np.float64)), ("tracks", t), ("track_counts", nt.astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args, det, frames_host, dets_seq, gpu_heads0=None, gpu_dets0=None, gpu_cands0=None, gpu_kept_rows0=None):
@@ -376,7 +396,7 @@ def other_workloads(args):
     out = {}
     for wl in ("cfg3", "cfg4"):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", wl, "--steps", "16", "--warmup", "3", "--no_cpu_baseline", "--no_latency_mode",
-               "--no_other_workloads", "--batch", str(args.batch), "--img", str(args.img), "--arch", args.arch]
+               "--no_other_workloads", "--full", "--batch", str(args.batch), "--img", str(args.img), "--arch", args.arch]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
@@ -662,7 +682,7 @@ def main():
     sd0 = conditioned_state_dict(args, nc, frames_host) if conditioned else None
     det = model.Detector(arch.ARCHS[args.arch](nc), sd0, img_size=(H, W), max_batch=B, seed=0)
     frames = torch.from_numpy(frames_host).cuda()
-    extra_passes = world == 1 and args.mode == "sequences" and args.halves == 1
+    extra_passes = args.full and world == 1 and args.mode == "sequences" and args.halves == 1
     coupled_pass = extra_passes and not cfg3 and not cfg4 and max(1, args.seqs) == 1 and args.tracker_launch == "frames" and args.hipgraph == 0 and not args.no_coupled
     n_frames *= 2 if extra_passes else 1   # second pass: the same pipeline fed from host memory (a third, `coupled`, has its own tracker and result rows)
     S = max(1, args.seqs)
@@ -752,6 +772,8 @@ def main():
     tracker_name = "botsort" if cfg3 else "deepsort" if cfg4 else "bytetrack"
     metric_name = "end-to-end fps (detect+track) YOLOv7-w6@1280 " + ("BoT-SORT, 500-object stress" if cfg3 else
                                                                      "DeepSORT + OSNet x0_25 ReID (128x64 crops)" if cfg4 else "ByteTrack")
+    if args.dump_outputs and (args.mode == "frames" or (args.halves == 2 and world == 1)):
+        raise SystemExit("--dump-outputs: the default pipeline only (--mode sequences --halves 1)")
     if args.halves == 2 and world == 1:
         dt_s, fwd_ms_step, d0 = halves_mode(args, lambda b: model.Detector(arch.ARCHS[args.arch](nc), None, img_size=(H, W), max_batch=b, seed=0),
                                            frames, dets_dev, trk, results, plant_objectness_bias)
@@ -811,13 +833,14 @@ def main():
     graph = None
     if args.hipgraph == 1:
         with torch.cuda.stream(sA):
-            graph, _, _ = det.capture(frames, CONF, 0.45, None)
+            graph, g_dets, g_nd = det.capture(frames, CONF, 0.45, None)
 
     # ops of the launch list that run on the 640^2 / 320^2 maps: memory-bound; the previous batch's decode+NMS (memory-bound too)
     # is held back until the forward is past them (an event recorded between two pieces of the list)
     k_mid = next((i for i, op in enumerate(det.plan.ops) if int(op["H"]) <= H // args.nms_gate_div), 0)
     ev_mid = [torch.cuda.Event() for _ in range(NS)]
     pending = []          # (step, staged heads) whose decode+NMS and tracker steps are not enqueued yet
+    post_of = {}          # step -> (dets, ndets) its decode + NMS wrote
     fwd_graphs = fwd_out = None
     if args.hipgraph == 2:    # the same launch list, captured in two pieces around the gate event, once per candidate set
         fwd_graphs, fwd_out = [], []
@@ -880,7 +903,7 @@ def main():
                 sC.wait_event(ev_trk1[ps - 2])     # coupled pass: this NMS rewrites the rows the tracker steps of batch ps - 2 read
             if gate is not None:
                 sC.wait_event(gate)
-            det.postprocess(out, CONF, 0.45, None)
+            post_of[ps] = det.postprocess(out, CONF, 0.45, None)
             ev_nms[ps].record(sC)
         with torch.cuda.stream(sB):
             sB.wait_event(ev_nms[ps])      # a frame's detections exist before its tracker step runs
@@ -904,6 +927,7 @@ def main():
             with torch.cuda.stream(sA):
                 ev_fwd0[s].record(sA)
                 graph.replay()                 # input layout + conv launches + pools + decode/NMS as one hipGraph
+                post_of[s] = (g_dets, g_nd)
                 ev_fwd1[s].record(sA)
                 ev_nms[s].record(sA)
             with torch.cuda.stream(sB):
@@ -962,6 +986,9 @@ def main():
         return time.perf_counter() - t0
 
     dt_s = timed_pass(0)
+    if args.dump_outputs and rank == 0:
+        s_last = Wm + K - 1
+        dump_outputs(args.dump_outputs, *post_of[s_last], results[s_last * B:(s_last + 1) * B], trk.cap_t)
     dt_h2d = None
     second_pass = extra_passes and graph is None
     dt_coupled = {}
@@ -1052,7 +1079,7 @@ def main():
                                     "note": "same pipeline, every batch copied from pinned host memory (uint8 BGR, %.1f MB per frame) on a copy "
                                             "stream, double-buffered; never `value`" % (H * W * 3 / 1e6)}
         line["value_note"] = ("frames resident in HBM when the timed region starts (the measurement contract of this build: a PCIe-inclusive rate is never `value`); "
-                              "the reference's own timer starts with the frame on the host (tracker/track.py:140): that rate is `fps_incl_h2d`, and `coupled` is the same "
+                              "the reference's own timer starts with the frame on the host (tracker/track.py:140): that rate is `fps_incl_h2d` (--full), and `coupled` is the same "
                               "host-fed pipeline with the tracker consuming the step's own NMS output")
         for cv in coupled_variants:
             s0c, tc, rc_, dtc = cv["first"] + Wm, cv["trk"], cv["results"], dt_coupled[cv["name"]]
@@ -1078,7 +1105,7 @@ def main():
         exps = {k: v for k, v in os.environ.items() if k.startswith("Y7T_") and k != "Y7T_TEST_EXPERIMENTS"}
         if exps:      # a run with experiment switches in the environment says so in its own line (none in the driver's run)
             line["config"]["environment_switches"] = exps
-        if world == 1:
+        if world == 1 and args.full:
             hist, ll_names = {}, det.launch_list(B)
             for nme in ll_names:
                 hist[nme] = hist.get(nme, 0) + 1

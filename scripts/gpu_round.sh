@@ -19,7 +19,7 @@
 #   exp_lowering    round 4's small-map lowering rules against round 3's thresholds (per-op tables, bench lines with latency mode)
 #   exp_r4misc      round 4's small experiments: stem with full-line stores, LDS max-pool, 64-channel tiles instead of split-K -- parity + per-op tables per variant
 #   suite           the whole `-m gpu` suite, as the driver runs it
-#   bench           the driver's bench line (python bench.py --steps 20 --warmup 5) -> bench_line.json
+#   bench           the driver's bench line (python bench.py --full --steps 20 --warmup 5) -> bench_line.json
 #   bench_variants  default vs --weights chaotic vs --cu_reserve 8 / 16 / 8+nms in ONE session (A/B deltas are only meaningful inside a session)
 #   profile         rocprofv3 kernel stats of the bench command, per-op table of the launch list, HBM traffic (2 PMC passes), MFMA busy -> stamped JSONs
 #   exp_ws          weights-stationary 64 -> 64 kernel (default; Y7T_CONV_WS=0 = the patch kernels): layer parity, parity inside the pinned list, per-layer timing, bench line
@@ -88,9 +88,9 @@ exp_p8)
   paste <(grep " 1/1 \|TOTAL" $O/b_nop8.txt | cut -c1-62) <(grep " 1/1 \|TOTAL" $O/b_p8.txt | cut -c36-62) | tee -a $O/summary.txt
   say "exp_p8 c: bench lines (same session): p8, then Y7T_CONV_P8=0, then p8 again"
   X="--steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode"
-  timeout 300 python bench.py $X > $O/bench_p8.json 2> $O/bench_p8.err
-  Y7T_CONV_P8=0 timeout 300 python bench.py $X > $O/bench_nop8.json 2> $O/bench_nop8.err
-  timeout 300 python bench.py $X > $O/bench_p8b.json 2> $O/bench_p8b.err
+  timeout 300 python bench.py --full $X > $O/bench_p8.json 2> $O/bench_p8.err
+  Y7T_CONV_P8=0 timeout 300 python bench.py --full $X > $O/bench_nop8.json 2> $O/bench_nop8.err
+  timeout 300 python bench.py --full $X > $O/bench_p8b.json 2> $O/bench_p8b.err
   benchsum p8 nop8 p8b
   ;;
 
@@ -140,9 +140,9 @@ exp_ws_s2)
   for v in "Y7T_CONV_WS_S2=0" "X=1" "Y7T_CONV_WS_WGS=248" "Y7T_CONV_WS_WGS=512"; do echo "-- $v: $(env $v ONLY=640,64,128,3,2 timeout 120 python scripts/bench_conv.py 32 50 2>&1 | grep ' 3/2 ' | cut -c1-70)"; done | tee -a $O/summary.txt
   say "exp_ws_s2 c: bench lines: with, without (Y7T_CONV_WS_S2=0), with"
   X="--steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode"
-  timeout 300 python bench.py $X > $O/bench_ws2.json 2> $O/bench_ws2.err
-  Y7T_CONV_WS_S2=0 timeout 300 python bench.py $X > $O/bench_nows2.json 2> $O/bench_nows2.err
-  timeout 300 python bench.py $X > $O/bench_ws2b.json 2> $O/bench_ws2b.err
+  timeout 300 python bench.py --full $X > $O/bench_ws2.json 2> $O/bench_ws2.err
+  Y7T_CONV_WS_S2=0 timeout 300 python bench.py --full $X > $O/bench_nows2.json 2> $O/bench_nows2.err
+  timeout 300 python bench.py --full $X > $O/bench_ws2b.json 2> $O/bench_ws2b.err
   benchsum ws2 nows2 ws2b
   ;;
 
@@ -152,9 +152,9 @@ exp_lowering)
   NAME=low_default OUT=$O bash scripts/per_layer_table.sh | tee -a $O/summary.txt
   env $R3 NAME=low_r3 OUT=$O bash scripts/per_layer_table.sh | tee -a $O/summary.txt
   X="--steps 20 --warmup 5 --no_cpu_baseline"
-  timeout 400 python bench.py $X > $O/bench_low.json 2> $O/bench_low.err
-  env $R3 timeout 400 python bench.py $X > $O/bench_lowr3.json 2> $O/bench_lowr3.err
-  timeout 400 python bench.py $X > $O/bench_low2.json 2> $O/bench_low2.err
+  timeout 400 python bench.py --full $X > $O/bench_low.json 2> $O/bench_low.err
+  env $R3 timeout 400 python bench.py --full $X > $O/bench_lowr3.json 2> $O/bench_lowr3.err
+  timeout 400 python bench.py --full $X > $O/bench_low2.json 2> $O/bench_low2.err
   benchsum low lowr3 low2
   ;;
 
@@ -177,7 +177,7 @@ r5_wgs)
   say "r5_wgs: persistent kernels over-decomposed (Y7T_CONV_WS_WGS = 256 default / 512 / 1024: the hardware dispatcher as the dynamic scheduler), bench lines in one session"
   X="--steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode"
   for w in 256 512 1024 256; do
-    Y7T_CONV_WS_WGS=$w timeout 300 python bench.py $X > $O/bench_wgs$w.json 2> $O/bench_wgs$w.err; benchsum wgs$w
+    Y7T_CONV_WS_WGS=$w timeout 300 python bench.py --full $X > $O/bench_wgs$w.json 2> $O/bench_wgs$w.err; benchsum wgs$w
   done
   ;;
 
@@ -189,7 +189,7 @@ r5_dyn)
   say "r5_dyn b: bench lines in one session: ws64 on the tile counter (default) | static (Y7T_CONV_WS_DYN=0) | + ws128 on the counter | + ws128 static | default again"
   X="--steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode"
   for v in dyn:X=1 static:Y7T_CONV_WS_DYN=0 dyn128:Y7T_CONV_WS128=1 static128:Y7T_CONV_WS128=1,Y7T_CONV_WS_DYN=0 dyn2:X=1 dyn128b:Y7T_CONV_WS128=1; do
-    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
+    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py --full $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
   done
   say "r5_dyn c: per-op tables of the launch list alone on the chip (through the plan: tile counters live): default, static, + ws128"
   for v in dyn:X=1 static:Y7T_CONV_WS_DYN=0 dyn128:Y7T_CONV_WS128=1; do
@@ -202,14 +202,14 @@ r5_batch)
   say "r5_batch: frames per step (bench.py --batch): tile quantisation of the 4-per-CU kernels against the batch (25 pixel tiles per 80 x 80 frame: 1600 workgroups on 512 slots at 32 frames)"
   X="--steps 12 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   for b in ${BATCHES:-32 24 40 48 64 32}; do
-    timeout 400 python bench.py $X --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err; benchsum b$b
+    timeout 400 python bench.py --full $X --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err; benchsum b$b
   done
   ;;
 
 r5_latency)
   say "r5_latency: batch-1 latency mode (reference Timer semantics), the frame's H2D copy as 1 / 2 / 4 concurrent pieces, one session"
   for n in 1 2 4 1 2; do
-    timeout 400 python bench.py --steps 3 --warmup 1 --no_cpu_baseline --no_other_workloads --upload_pieces $n > $O/bench_up$n.json 2> $O/bench_up$n.err
+    timeout 400 python bench.py --full --steps 3 --warmup 1 --no_cpu_baseline --no_other_workloads --upload_pieces $n > $O/bench_up$n.json 2> $O/bench_up$n.err
     python3 - $O/bench_up$n.json $n <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:
@@ -235,7 +235,7 @@ r5_branches)
   X="--steps 16 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   export Y7T_LIB=$LIBD/liby7t_ablate.so
   for v in br1:Y7T_DETECT_BRANCHES=1 br0:Y7T_DETECT_BRANCHES=0 br1b:Y7T_DETECT_BRANCHES=1 br0b:Y7T_DETECT_BRANCHES=0 p128:Y7T_CONV_PATCH_PANEL64_BELOW=0 p64:Y7T_CONV_PATCH_PANEL64_BELOW=400 x64:Y7T_CONV_1X1_PANEL64_BELOW=600 x128:Y7T_CONV_1X1_PANEL64_BELOW=0 br1c:Y7T_DETECT_BRANCHES=1; do
-    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
+    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py --full $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
   done
   unset Y7T_LIB
   ;;
@@ -245,7 +245,7 @@ r5_panel240)
   X="--steps 16 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   export Y7T_LIB=$LIBD/liby7t_ablate.so
   for v in base:X=1 p240:Y7T_CONV_PATCH_PANEL64_BELOW=240 base2:X=1 p240b:Y7T_CONV_PATCH_PANEL64_BELOW=240; do
-    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
+    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py --full $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
   done
   for v in base:X=1 p240:Y7T_CONV_PATCH_PANEL64_BELOW=240; do
     n=${v%%:*}; e=${v#*:}; env ${e//,/ } NAME=$n OUT=$O bash scripts/per_layer_table.sh | tee -a $O/summary.txt
@@ -268,7 +268,7 @@ r5_ws128s2)
   say "r5_ws128s2 b: bench lines, alternating (0 = patch_s2 for those two layers, 1 = ws128_s2)"
   X="--steps 16 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   for v in s2off:Y7T_CONV_WS128_S2=0 s2on:Y7T_CONV_WS128_S2=1 s2offb:Y7T_CONV_WS128_S2=0 s2onb:Y7T_CONV_WS128_S2=1; do
-    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
+    n=${v%%:*}; e=${v#*:}; env ${e//,/ } timeout 300 python bench.py --full $X > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
   done
   say "r5_ws128s2 c: per-op tables"
   for v in s2off:Y7T_CONV_WS128_S2=0 s2on:Y7T_CONV_WS128_S2=1; do
@@ -289,12 +289,12 @@ r5_coop)
   say "r5_coop c: cfg3 (BoT-SORT, 500 objects) and the headline, previous / this library alternating"
   X="--steps 10 --warmup 3 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   for v in prev:$LIBD/liby7t_prev.so new:$LIBD/liby7t.so prevb:$LIBD/liby7t_prev.so newb:$LIBD/liby7t.so; do
-    n=${v%%:*}; l=${v#*:}; Y7T_LIB=$l timeout 300 python bench.py $X --workload cfg3 > $O/bench_cfg3_$n.json 2> $O/bench_cfg3_$n.err; benchsum cfg3_$n
+    n=${v%%:*}; l=${v#*:}; Y7T_LIB=$l timeout 300 python bench.py --full $X --workload cfg3 > $O/bench_cfg3_$n.json 2> $O/bench_cfg3_$n.err; benchsum cfg3_$n
   done
   for v in prev:$LIBD/liby7t_prev.so new:$LIBD/liby7t.so; do
-    n=${v%%:*}; l=${v#*:}; Y7T_LIB=$l timeout 300 python bench.py --steps 16 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads > $O/bench_cfg2_$n.json 2> $O/bench_cfg2_$n.err; benchsum cfg2_$n
+    n=${v%%:*}; l=${v#*:}; Y7T_LIB=$l timeout 300 python bench.py --full --steps 16 --warmup 4 --no_cpu_baseline --no_latency_mode --no_other_workloads > $O/bench_cfg2_$n.json 2> $O/bench_cfg2_$n.err; benchsum cfg2_$n
   done
-  timeout 300 python bench.py $X --workload cfg4 > $O/bench_cfg4_new.json 2> $O/bench_cfg4_new.err; benchsum cfg4_new
+  timeout 300 python bench.py --full $X --workload cfg4 > $O/bench_cfg4_new.json 2> $O/bench_cfg4_new.err; benchsum cfg4_new
   ;;
 
 r5_coop2)
@@ -307,7 +307,7 @@ r5_coop2)
   X="--steps 10 --warmup 3 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   for v in ${LIBS:-prev:liby7t_prev.so min8:liby7t.so min4:liby7t_coop4.so min2:liby7t_coop2.so}; do
     n=${v%%:*}; l=$LIBD/${v#*:}; [ -f $l ] || continue
-    Y7T_LIB=$l timeout 300 python bench.py $X --workload cfg3 > $O/bench_cfg3_$n.json 2> $O/bench_cfg3_$n.err; benchsum cfg3_$n
+    Y7T_LIB=$l timeout 300 python bench.py --full $X --workload cfg3 > $O/bench_cfg3_$n.json 2> $O/bench_cfg3_$n.err; benchsum cfg3_$n
   done
   ;;
 
@@ -321,7 +321,7 @@ r5_tracker_ab)
   X="--steps 10 --warmup 3 --no_cpu_baseline --no_latency_mode --no_other_workloads"
   for w in cfg3 cfg2 cfg4; do for v in prev:liby7t_prev.so new:liby7t.so prevb:liby7t_prev.so newb:liby7t.so; do
     n=${w}_${v%%:*}; l=$LIBD/${v#*:}; [ -f $l ] || continue
-    Y7T_LIB=$l timeout 300 python bench.py $X --workload $w > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
+    Y7T_LIB=$l timeout 300 python bench.py --full $X --workload $w > $O/bench_$n.json 2> $O/bench_$n.err; benchsum $n
   done; done
   ;;
 
@@ -332,19 +332,19 @@ suite)
 
 bench)
   say "bench: the driver's line"
-  timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?" | tee -a $O/summary.txt
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?" | tee -a $O/summary.txt
   cp $O/bench_line.json $O/bench_default.json; benchsum default
   ;;
 
 bench_variants)
   say "bench_variants (one session): default, chaotic weights, tracker chain on reserved CUs"
   X="--steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode"
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-  timeout 300 python bench.py $X --weights chaotic > $O/bench_chaotic.json 2> $O/bench_chaotic.err
-  timeout 300 python bench.py $X --cu_reserve 8 > $O/bench_cu8.json 2> $O/bench_cu8.err
-  timeout 300 python bench.py $X --cu_reserve 16 > $O/bench_cu16.json 2> $O/bench_cu16.err
-  timeout 300 python bench.py $X --cu_reserve 8 --cu_reserve_nms 1 > $O/bench_cu8nms.json 2> $O/bench_cu8nms.err
-  timeout 300 python bench.py $X > $O/bench_default2.json 2> $O/bench_default2.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+  timeout 300 python bench.py --full $X --weights chaotic > $O/bench_chaotic.json 2> $O/bench_chaotic.err
+  timeout 300 python bench.py --full $X --cu_reserve 8 > $O/bench_cu8.json 2> $O/bench_cu8.err
+  timeout 300 python bench.py --full $X --cu_reserve 16 > $O/bench_cu16.json 2> $O/bench_cu16.err
+  timeout 300 python bench.py --full $X --cu_reserve 8 --cu_reserve_nms 1 > $O/bench_cu8nms.json 2> $O/bench_cu8nms.err
+  timeout 300 python bench.py --full $X > $O/bench_default2.json 2> $O/bench_default2.err
   benchsum default chaotic cu8 cu16 cu8nms default2
   for n in default chaotic cu8 cu16 cu8nms default2; do [ -s $O/bench_$n.err ] && { echo "-- stderr of $n"; grep -v amdgpu.ids $O/bench_$n.err | tail -4; }; done | tee -a $O/summary.txt
   ;;
@@ -353,7 +353,7 @@ stats)
   say "stats: rocprofv3 --kernel-trace --stats of the bench command (kernel stats only; the per-op table and the PMC passes are the profile step)"
   P=$O/prof; mkdir -p $P
   ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/ks
-    timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $ROOT/bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --no_other_workloads > $P/bench_under_rocprof.log 2>&1
+    timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --no_other_workloads > $P/bench_under_rocprof.log 2>&1
     f=$(find /tmp/ks -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $P/bench_kernel_stats.csv )
   head -14 $P/bench_kernel_stats.csv 2>/dev/null | cut -c1-160 | tee -a $O/summary.txt
   grep -o '"value": [0-9.]*, "unit": "frames/s"\|"launch_list_ms": [0-9.]*' $P/bench_under_rocprof.log | head -2 | tee -a $O/summary.txt
@@ -363,7 +363,7 @@ closing_small)
   say "closing_small: the chained parity tests, smoke(), the driver's bench line"
   timeout 600 python -m pytest tests/test_chained_gpu.py -q -m gpu > $O/t_chained.log 2>&1; echo "rc=$?" >> $O/t_chained.log; tailsum $O/t_chained.log 3
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "rc=$?" >> $O/smoke.log; tailsum $O/smoke.log 2
-  timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?" | tee -a $O/summary.txt
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?" | tee -a $O/summary.txt
   cp $O/bench_line.json $O/bench_default.json; benchsum default
   ;;
 
@@ -372,7 +372,7 @@ profile)
   P=$O/prof; mkdir -p $P
   COMMIT=$(cat $ROOT/.commit_stamp 2>/dev/null || echo unknown)
   ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/ks /tmp/kt /tmp/pf /tmp/pw /tmp/mb
-    timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $ROOT/bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --no_other_workloads > $P/bench_under_rocprof.log 2>&1
+    timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --no_other_workloads > $P/bench_under_rocprof.log 2>&1
     f=$(find /tmp/ks -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $P/bench_kernel_stats.csv
     timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python $ROOT/scripts/forward_only.py 4 > $P/forward_only.log 2>&1
     f=$(find /tmp/kt -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && cp $f $P/forward_kernel_trace.csv
@@ -395,8 +395,8 @@ exp_ws)
   Y7T_CONV_WS_WGS=512 timeout 200 python scripts/bench_conv.py 32 > $O/b_ws_512.txt 2>&1
   for f in default ws ws_512; do echo "-- $f"; grep "  64->64 \|TOTAL" $O/b_$f.txt; done | tee -a $O/summary.txt
   say "exp_ws c: bench line with it on"
-  timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_ws.json 2> $O/bench_ws.err
-  Y7T_CONV_WS=0 timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_nows.json 2> $O/bench_nows.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_ws.json 2> $O/bench_ws.err
+  Y7T_CONV_WS=0 timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_nows.json 2> $O/bench_nows.err
   benchsum ws nows
   ;;
 
@@ -410,7 +410,7 @@ exp_ws4)
   say "exp_ws4 c: issue counters of the kernel"
   OUT=$O/pmc_ws bash scripts/pmc_kernel.sh c64_ws python scripts/forward_only.py 2 > $O/pmc_ws.txt 2>&1; grep -v "^pass" $O/pmc_ws/summary.txt | awk '{print $1, $2, $4}' | sort -u | tee -a $O/summary.txt
   say "exp_ws4 d: bench line"
-  timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_ws.json 2> $O/bench_ws.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_ws.json 2> $O/bench_ws.err
   benchsum ws
   ;;
 
@@ -431,8 +431,8 @@ exp_noslp)
   timeout 200 python scripts/bench_conv.py 32 > $O/b_new.txt 2>&1
   paste <(cut -c1-52 $O/b_prev.txt) <(cut -c36-52 $O/b_new.txt) | tee -a $O/summary.txt
   say "exp_noslp c: bench lines, previous library then this one"
-  Y7T_LIB=$LIBD/liby7t_prev.so timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_prev.json 2> $O/bench_prev.err
-  timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_new.json 2> $O/bench_new.err
+  Y7T_LIB=$LIBD/liby7t_prev.so timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_prev.json 2> $O/bench_prev.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode > $O/bench_new.json 2> $O/bench_new.err
   benchsum prev new
   ;;
 
@@ -467,7 +467,7 @@ exp_arena)
   timeout 600 python -m pytest tests/test_tracker_gpu.py tests/test_fullsize_gpu.py -q -m gpu -x > $O/t_trk.log 2>&1; echo "rc=$?" >> $O/t_trk.log; tailsum $O/t_trk.log
   say "exp_arena b: bench lines (cfg2, cfg3) with the arena (default) and without (Y7T_TRACKER_ARENA=0), same session"
   for w in cfg2 cfg3; do for a in 1 0; do
-    Y7T_TRACKER_ARENA=$a timeout 300 python bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --workload $w > $O/bench_${w}_arena$a.json 2> $O/bench_${w}_arena$a.err
+    Y7T_TRACKER_ARENA=$a timeout 300 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_latency_mode --workload $w > $O/bench_${w}_arena$a.json 2> $O/bench_${w}_arena$a.err
   done; done
   benchsum cfg2_arena1 cfg2_arena0 cfg3_arena1 cfg3_arena0
   ;;

@@ -68,8 +68,8 @@ suite)
   ;;
 
 bench)
-  say "bench: python bench.py --steps 20 --warmup 5"
-  timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "rc=$?" | tee -a $O/summary.txt
+  say "bench: python bench.py --full --steps 20 --warmup 5"
+  timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "rc=$?" | tee -a $O/summary.txt
   benchline $O/bench_line.json
   ;;
 
@@ -77,7 +77,7 @@ batch_sweep)
   say "batch_sweep: frames per step above the 40 that 2 GiB tensors allowed (conv launches over runs of frames, csrc/y7t_detector.hip): the chunk test, then the headline at 40 / 48 / 56 / 64 / 40"
   timeout 600 python -m pytest -x -q -m gpu tests/test_fullsize_gpu.py -k "runs_of_frames" > $O/t_runs.log 2>&1; echo "rc=$?" >> $O/t_runs.log; tailsum $O/t_runs.log 3
   for b in ${SWEEP:-40 48 56 64 40}; do
-    timeout 900 python bench.py --steps 12 --warmup 4 --batch $b --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/bench_b$b.json 2> $O/bench_b$b.err; echo "b$b rc=$?" | tee -a $O/summary.txt
+    timeout 900 python bench.py --full --steps 12 --warmup 4 --batch $b --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/bench_b$b.json 2> $O/bench_b$b.err; echo "b$b rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_b$b.json; tail -2 $O/bench_b$b.err | cut -c1-300
   done
   ;;
@@ -99,7 +99,7 @@ tests_pinned)
 
 bench_quick)
   say "bench_quick: the headline only (no latency mode / cpu baseline / other workloads)"
-  timeout 600 python bench.py --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads > $O/bench_quick.json 2> $O/bench_quick.err; echo "rc=$?" | tee -a $O/summary.txt
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads > $O/bench_quick.json 2> $O/bench_quick.err; echo "rc=$?" | tee -a $O/summary.txt
   benchline $O/bench_quick.json
   ;;
 
@@ -117,7 +117,7 @@ owncu_ab)
   say "owncu_ab: tracker step kernels asking for the CU's whole LDS (default) against asking for what they use (measuring build, Y7T_TRACKER_OWN_CU=0): headline + cfg3 / cfg4 child runs, A/B/A"
   for v in own1_a own0 own1_b; do
     case $v in own0) E="Y7T_LIB=$ROOT/yolov7-tracker_amd/lib/liby7t_ablate.so Y7T_TRACKER_OWN_CU=0";; *) E="Y7T_LIB=$ROOT/yolov7-tracker_amd/lib/liby7t_ablate.so Y7T_TRACKER_OWN_CU=1";; esac
-    env $E timeout 900 python bench.py --steps 10 --warmup 3 --no_latency_mode --no_cpu_baseline --no_coupled > $O/bench_$v.json 2> $O/bench_$v.err; echo "$v rc=$?" | tee -a $O/summary.txt
+    env $E timeout 900 python bench.py --full --steps 10 --warmup 3 --no_latency_mode --no_cpu_baseline --no_coupled > $O/bench_$v.json 2> $O/bench_$v.err; echo "$v rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_$v.json
   done
   ;;
@@ -126,7 +126,7 @@ hipgraph2)
   say "hipgraph2: the conv launch list as two captured hipGraphs per candidate set (bench.py --hipgraph 2) against the plain launches, A/B/A"
   for v in plain_a graph plain_b; do
     case $v in graph) F="--hipgraph 2";; *) F="";; esac
-    timeout 600 python bench.py --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled $F > $O/bench_hg_$v.json 2> $O/bench_hg_$v.err; echo "$v rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled $F > $O/bench_hg_$v.json 2> $O/bench_hg_$v.err; echo "$v rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_hg_$v.json
   done
   ;;
@@ -176,7 +176,7 @@ tests_tracker)
 nms_gate)
   say "nms_gate: where the previous batch's rank sort + NMS is released into the forward (bench.py --nms_gate_div 8 / 16 / 32), A/B/C/A"
   for v in 8 16 32 8; do
-    timeout 600 python bench.py --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --nms_gate_div $v > $O/bench_gate_$v.json 2> $O/bench_gate_$v.err; echo "gate_div $v rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --nms_gate_div $v > $O/bench_gate_$v.json 2> $O/bench_gate_$v.err; echo "gate_div $v rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_gate_$v.json
   done
   ;;
@@ -218,7 +218,7 @@ deepsort_prof)
 cfg4_trace)
   say "cfg4_trace: rocprofv3 --kernel-trace of a short cfg4 bench (where a DeepSORT frame's four launches wait beside the detector) -> cfg4_kernel_trace.csv"
   ( cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/c4
-    timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/c4 -- python $ROOT/bench.py --workload ${WL:-cfg4} --steps 3 --warmup 1 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/cfg4_trace.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/c4 -- python $ROOT/bench.py --full --workload ${WL:-cfg4} --steps 3 --warmup 1 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/cfg4_trace.log 2>&1
     f=$(find /tmp/c4 -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python $ROOT/scripts/trace_compact.py $f $O/${WL:-cfg4}_kernel_trace.csv )
   wc -l $O/${WL:-cfg4}_kernel_trace.csv | tee -a $O/summary.txt; tail -2 $O/cfg4_trace.log | cut -c1-300
   ;;
@@ -227,19 +227,19 @@ closing_ab)
   say "closing_ab: the 80-frame headline against (b) persistent conv kernels on a static partition (Y7T_CONV_WS_DYN=0), (c) 96 frames, (d) the list as captured hipGraphs, (e) NMS gate variants; A first and last"
   Q="--steps 16 --warmup 4 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled"
   run() { n=$1; shift; env "$@" > /dev/null 2>&1; }
-  timeout 600 python bench.py $Q > $O/ab_a.json 2> $O/ab_a.err; echo "a default rc=$?" | tee -a $O/summary.txt; benchline $O/ab_a.json
-  Y7T_CONV_WS_DYN=0 timeout 600 python bench.py $Q > $O/ab_b.json 2> $O/ab_b.err; echo "b static partition rc=$?" | tee -a $O/summary.txt; benchline $O/ab_b.json
-  timeout 600 python bench.py $Q --batch 96 > $O/ab_c.json 2> $O/ab_c.err; echo "c 96 frames rc=$?" | tee -a $O/summary.txt; benchline $O/ab_c.json
-  timeout 600 python bench.py $Q --hipgraph 2 > $O/ab_d.json 2> $O/ab_d.err; echo "d hipgraph 2 rc=$?" | tee -a $O/summary.txt; benchline $O/ab_d.json
-  timeout 600 python bench.py $Q --nms_gate_div 16 > $O/ab_e.json 2> $O/ab_e.err; echo "e nms gate 16 rc=$?" | tee -a $O/summary.txt; benchline $O/ab_e.json
-  timeout 600 python bench.py $Q --tracker_launch per_frame > $O/ab_f.json 2> $O/ab_f.err; echo "f tracker per frame rc=$?" | tee -a $O/summary.txt; benchline $O/ab_f.json
-  timeout 600 python bench.py $Q > $O/ab_a2.json 2> $O/ab_a2.err; echo "a2 default rc=$?" | tee -a $O/summary.txt; benchline $O/ab_a2.json
+  timeout 600 python bench.py --full $Q > $O/ab_a.json 2> $O/ab_a.err; echo "a default rc=$?" | tee -a $O/summary.txt; benchline $O/ab_a.json
+  Y7T_CONV_WS_DYN=0 timeout 600 python bench.py --full $Q > $O/ab_b.json 2> $O/ab_b.err; echo "b static partition rc=$?" | tee -a $O/summary.txt; benchline $O/ab_b.json
+  timeout 600 python bench.py --full $Q --batch 96 > $O/ab_c.json 2> $O/ab_c.err; echo "c 96 frames rc=$?" | tee -a $O/summary.txt; benchline $O/ab_c.json
+  timeout 600 python bench.py --full $Q --hipgraph 2 > $O/ab_d.json 2> $O/ab_d.err; echo "d hipgraph 2 rc=$?" | tee -a $O/summary.txt; benchline $O/ab_d.json
+  timeout 600 python bench.py --full $Q --nms_gate_div 16 > $O/ab_e.json 2> $O/ab_e.err; echo "e nms gate 16 rc=$?" | tee -a $O/summary.txt; benchline $O/ab_e.json
+  timeout 600 python bench.py --full $Q --tracker_launch per_frame > $O/ab_f.json 2> $O/ab_f.err; echo "f tracker per frame rc=$?" | tee -a $O/summary.txt; benchline $O/ab_f.json
+  timeout 600 python bench.py --full $Q > $O/ab_a2.json 2> $O/ab_a2.err; echo "a2 default rc=$?" | tee -a $O/summary.txt; benchline $O/ab_a2.json
   ;;
 
 threads_sweep)
   say "threads_sweep: threads of the tracker step workgroup inside the pipeline (bench.py --tracker_threads), per workload"
   for wl in cfg2 cfg3 cfg4; do for t in ${THREADS:-0 128 256 512}; do
-    timeout 600 python bench.py --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --tracker_threads $t > $O/bench_thr_${wl}_$t.json 2> $O/bench_thr_${wl}_$t.err; echo "$wl threads $t rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --tracker_threads $t > $O/bench_thr_${wl}_$t.json 2> $O/bench_thr_${wl}_$t.err; echo "$wl threads $t rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_thr_${wl}_$t.json
   done; done
   ;;
@@ -249,7 +249,7 @@ cfg4_ab)
   timeout 900 python -m pytest -x -q -m gpu tests/test_tracker_gpu.py tests/test_reid_gpu.py -k "deepsort or DeepSORT or reid or embed" > $O/t_ds.log 2>&1; echo "rc=$?" >> $O/t_ds.log; tailsum $O/t_ds.log 3
   timeout 600 python scripts/time_deepsort.py > $O/time_deepsort.log 2>&1; grep "kernel-only" $O/time_deepsort.log | cut -c1-200 | tee -a $O/summary.txt
   for k in 1 2; do
-    timeout 600 python bench.py --workload cfg4 --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/bench_cfg4_$k.json 2> $O/bench_cfg4_$k.err; echo "cfg4 run $k rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --workload cfg4 --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled > $O/bench_cfg4_$k.json 2> $O/bench_cfg4_$k.err; echo "cfg4 run $k rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_cfg4_$k.json
   done
   ;;
@@ -257,7 +257,7 @@ cfg4_ab)
 prio_ab)
   say "prio_ab: the tracker chain's stream at high queue priority (bench.py --prio 2) against the default, cfg4 / cfg3 / cfg2, A/B/A"
   for wl in cfg4 cfg3 cfg2; do for v in 0 2 0b; do
-    timeout 600 python bench.py --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --prio ${v%b} > $O/bench_prio_${wl}_$v.json 2> $O/bench_prio_${wl}_$v.err; echo "$wl prio $v rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --prio ${v%b} > $O/bench_prio_${wl}_$v.json 2> $O/bench_prio_${wl}_$v.err; echo "$wl prio $v rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_prio_${wl}_$v.json
   done; done
   ;;
@@ -265,7 +265,7 @@ prio_ab)
 cu_reserve_cfg4)
   say "cu_reserve_cfg4: the tracker chain's stream on reserved CUs (bench.py --cu_reserve N) for cfg4 (four dependent launches per frame) and cfg3, against the default"
   for wl in cfg4 cfg3; do for v in 0 2 8 0b; do
-    timeout 600 python bench.py --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --cu_reserve ${v%b} > $O/bench_cur_${wl}_$v.json 2> $O/bench_cur_${wl}_$v.err; echo "$wl cu_reserve $v rc=$?" | tee -a $O/summary.txt
+    timeout 600 python bench.py --full --workload $wl --steps 8 --warmup 3 --no_latency_mode --no_cpu_baseline --no_other_workloads --no_coupled --cu_reserve ${v%b} > $O/bench_cur_${wl}_$v.json 2> $O/bench_cur_${wl}_$v.err; echo "$wl cu_reserve $v rc=$?" | tee -a $O/summary.txt
     benchline $O/bench_cur_${wl}_$v.json
   done; done
   ;;

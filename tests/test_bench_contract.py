@@ -41,6 +41,37 @@ def test_bench_command_line_is_the_drivers():
     finally:
         sys.argv = old
     assert a.gpus == 1 and 1 <= a.steps <= 50 and 0 <= a.warmup <= 20          # no flags: one GPU, a run of minutes
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+    assert a.full is False and a.dump_outputs is None                          # a plain run: the headline only, nothing written
+
+
+def test_dump_outputs_writes_what_a_caller_receives(tmp_path):
+    """--dump-outputs: the last timed step's NMS rows and returned tracks, float32 / float64, rows past each frame's count zeroed"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, cap_t = 3, 16
+    g = torch.Generator().manual_seed(0)
+    dets = torch.rand((B, 300, 6), generator=g)
+    ndets = torch.tensor([5, 0, 300], dtype=torch.int32)
+    rows = torch.rand((B, cap_t + 1, 8), dtype=torch.float64, generator=g)
+    counts = [4, 0, cap_t]
+    for b, n in enumerate(counts):
+        rows[b, cap_t].view(torch.int32)[0] = n
+    bench.dump_outputs(str(tmp_path), dets, ndets, rows, cap_t)
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert set(got) == {"detections", "detection_counts", "tracks", "track_counts"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["detection_counts"].tolist() == [5, 0, 300] and got["track_counts"].tolist() == counts
+    d, t = got["detections"], got["tracks"]
+    assert d.shape == (B, 300, 6) and t.shape == (B, cap_t, 7)
+    for b in range(B):
+        n = int(ndets[b])
+        np.testing.assert_array_equal(d[b, :n], dets[b, :n].numpy())
+        assert not d[b, n:].any()
+        np.testing.assert_array_equal(t[b, :counts[b]], rows[b, :counts[b], :7].numpy())
+        assert not t[b, counts[b]:].any()
 
 
 def test_gpus_n_without_a_launcher_starts_n_ranks_itself():
