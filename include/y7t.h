@@ -30,7 +30,7 @@ enum { Y7T_OK = 0, Y7T_E_ARG = -1, Y7T_E_HIP = -2, Y7T_E_CAPACITY = -3, Y7T_E_ST
 /* Kalman filter kinds == KALMAN_DICT keys, tracker/basetrack.py:64-69 */
 enum { Y7T_KALMAN_DEFAULT = 0, Y7T_KALMAN_NAIVE = 1, Y7T_KALMAN_BOTSORT = 2, Y7T_KALMAN_STRONGSORT = 3 };
 /* tracker kinds == TRACKER_DICT keys implemented on the device, tracker/track.py:56-65 */
-enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3 };
+enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4 };
 
 const char* y7t_last_error(void);
 int y7t_version(void);
@@ -139,6 +139,14 @@ int y7t_tracker_step(void* state, const float* dets, int n, double* out_rows, in
  * GMC.apply returns (botsort.py:13-248 -- OpenCV ORB/RANSAC estimation, out of scope); the step applies multi_gmc
  * (botsort.py:250-269) to the predicted pool and the unconfirmed tracks.  Same op on its own: */
 int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* warp, int N, y7t_stream stream);
+
+/* C-BIoU (tracker/c_biou_tracker.py:212-353, tracker kind Y7T_TRACKER_C_BIOU; the Kalman kind of y7t_tracker_init is ignored): no motion model, three
+ * IoU associations of buffered boxes.  Same pool blob, same layout and the same entry points as SORT / ByteTrack: y7t_tracker_step, y7t_tracker_step_frames,
+ * y7t_tracker_step_batch (a batch may mix C-BIoU pools with the others).  A slot's `cov` storage holds the track's last 6 boxes, its two motion states and
+ * buffered boxes instead of a covariance.  n < 0 (update_without_detection) on a pool whose confirmed-tracked + lost lists are not empty sets status bit 16
+ * (the reference's update_without_detection needs a Kalman mean and fails there) and changes nothing; with an empty pool it advances the frame.  The lost
+ * list is never aged (as in the reference): size cap_tracks for the length of the sequence -- an overflow sets status bit 1.
+ * y7t_tracker_step_deepsort refuses a C-BIoU pool: Y7T_E_STATE and status bit 8. */
 
 /* DeepSORT (tracker/deepsort.py:79-227, tracker kind Y7T_TRACKER_DEEPSORT): appearance + motion.  Next to the pool blob the tracker owns
  * a FEATURE STATE (y7t_deepsort_feature_bytes, y7t_deepsort_init): per slot the last `budget` appearance vectors of the track

@@ -1,0 +1,191 @@
+"""C-BIoU without a GPU: the CPU build of the tracker workgroup programs (tests/_hostsim) with tracker kind 4 against the reference's golden vectors
+(tests/golden/tracker_c_biou_*.npz, tests/golden/make_golden_c_biou.py) and, where the reference sources exist, against the live reference on random
+scenes; the port's matching.buffered_iou_distance against the reference's."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from tests import _hostsim as hs
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NAMES = ["default", "bounce", "misses", "crowd", "empty", "conf04"]
+LIB = os.path.join(os.path.dirname(GOLDEN), "..", "yolov7-tracker_amd", "lib", "liby7t.so")
+
+
+class CBHost(hs.HostSimTracker):
+    TRACKERS = dict(hs.HostSimTracker.TRACKERS, c_biou=4)
+
+
+def load_golden(name):
+    g = np.load(os.path.join(GOLDEN, "tracker_c_biou_%s.npz" % name))
+    off = np.concatenate([[0], np.cumsum(g["det_counts"])])
+    dets = [g["dets"][off[i]:off[i + 1]] for i in range(len(g["det_counts"]))]
+
+    def split(counts, flat):
+        o = np.concatenate([[0], np.cumsum(counts)])
+        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
+    frames = []
+    for f in range(len(dets)):
+        sel = g["frame"] == f
+        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
+    return dict(dets=dets, frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]), lost=split(g["lost_counts"], g["lost_ids"]),
+                conf=float(g["conf_thresh"]))
+
+
+_LAYOUT = {}
+
+
+def layout(cap_t, cap_d):
+    """byte offsets of the pool blob's fields (the product library's y7t_tracker_layout: host code, no device needed)"""
+    if (cap_t, cap_d) not in _LAYOUT:
+        L = ctypes.CDLL(LIB)
+        L.y7t_tracker_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        L.y7t_tracker_field_name.restype = ctypes.c_char_p
+        n = L.y7t_tracker_layout(cap_t, cap_d, None, 0)
+        offs = (ctypes.c_int64 * n)()
+        L.y7t_tracker_layout(cap_t, cap_d, offs, n)
+        _LAYOUT[(cap_t, cap_d)] = {L.y7t_tracker_field_name(i).decode(): int(offs[i]) for i in range(n)}
+    return _LAYOUT[(cap_t, cap_d)]
+
+
+def id_lists(trk):
+    """-> (ids of the tracked list, ids of the lost list) of a host pool, in list order"""
+    lo, b = layout(trk.cap_t, 1024), trk.blob
+    i32 = lambda off, n: b[off:off + 4 * n].view(np.int32)      # noqa: E731
+    tid = i32(lo["tid"], trk.cap_t)
+    nt, nl = int(i32(lo["hdr_n_tracked"], 1)[0]), int(i32(lo["hdr_n_lost"], 1)[0])
+    return tid[i32(lo["tracked"], nt)].tolist(), tid[i32(lo["lost"], nl)].tolist()
+
+
+def replay(dets, conf, arena_frames=0, want=None):
+    """run the host build over `dets`; with `want` (golden / reference frames) compare every frame"""
+    trk = CBHost("c_biou", conf_thresh=conf)
+    got = []
+    for f, d in enumerate(dets):
+        if arena_frames and f % arena_frames == 0:
+            assert hs.lib().hs_arena_begin(trk.blob.ctypes.data)
+        rows = trk.update(d)
+        group_end = not arena_frames or f % arena_frames == arena_frames - 1 or f == len(dets) - 1
+        if arena_frames and group_end:
+            hs.lib().hs_arena_end(trk.blob.ctypes.data)
+        got.append(rows)
+        if want is None:
+            continue
+        ids, tlwh, cls, score = want["frames"][f]
+        assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
+        assert np.array_equal(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh), "frame %d: tlwh" % f
+        assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score)
+        if group_end:      # (inside an arena group the lists live in the arena)
+            assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
+    return got
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_hostsim_c_biou_matches_reference_golden(name):
+    g = load_golden(name)
+    replay(g["dets"], g["conf"], want=g)
+
+
+@pytest.mark.parametrize("name,frames", [("default", 8), ("misses", 16), ("crowd", 5), ("empty", 3)])
+def test_hostsim_c_biou_with_list_arena_matches_reference_golden(name, frames):
+    g = load_golden(name)
+    replay(g["dets"], g["conf"], arena_frames=frames, want=g)
+
+
+def test_hostsim_c_biou_misses_golden_exercises_the_buffer():
+    """the 30 %-miss golden holds what the tracker's quirks need: re-found tracks (stale δ), a full 6-box buffer, a lost list that only grows by misses"""
+    g = load_golden("misses")
+    assert max(len(x) for x in g["lost"]) >= 20
+    assert len(g["frames"]) == 300 and max(int(f[0].max()) for f in g["frames"] if len(f[0])) > 300
+
+
+def test_hostsim_c_biou_update_without_detection():
+    """an empty pool only advances the frame; a non-empty one is refused with Y7T_ERR_PREDICT (16), the state unchanged"""
+    trk = CBHost("c_biou")
+    assert trk.update(None) == []
+    assert trk.update(np.zeros((0, 6), np.float32)) == []
+    d = np.array([[10, 10, 60, 90, 0.9, 0], [200, 40, 260, 160, 0.8, 1]], np.float32)
+    assert len(trk.update(d)) == 0      # frame 3: new tracks, not activated
+    assert len(trk.update(d)) == 2
+    lo = layout(trk.cap_t, 1024)
+    frame = lambda: int(trk.blob[lo["hdr_frame_id"]:lo["hdr_frame_id"] + 4].view(np.int32)[0])      # noqa: E731
+    before, lists = frame(), id_lists(trk)
+    with pytest.raises(RuntimeError, match="status 16"):
+        trk.update(None)
+    assert frame() == before == 4 and id_lists(trk) == lists
+
+
+def test_hostsim_c_biou_pool_overflow_sets_status():
+    trk = CBHost("c_biou", cap_t=16)
+    from yolov7_tracker_amd import synth
+    with pytest.raises(RuntimeError, match="capacity"):
+        for d in synth.make_detections(5, 40, seq_idx=3):
+            trk.update(d)
+
+
+# ---- against the live reference (where its sources exist) ----
+from oracle import ref_harness  # noqa: E402
+
+needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference sources not present")
+
+
+def _ref_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_c_biou", os.path.join(GOLDEN, "make_golden_c_biou.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    return mg
+
+
+@needs_ref
+@pytest.mark.parametrize("seed", range(20))
+def test_hostsim_c_biou_matches_live_reference(seed):
+    from yolov7_tracker_amd import synth
+    mg = _ref_module()
+    rng = np.random.default_rng(1000 + seed)
+    nf, nobj = int(rng.integers(20, 70)), int(rng.integers(5, 140))
+    extra = {"bounce": bool(rng.integers(0, 2)), "miss": float(rng.uniform(0.0, 0.4))}
+    dets = synth.make_detections(nf, nobj, seq_idx=200 + seed, **extra)
+    if seed % 3 == 0:
+        dets = [np.zeros((0, 6), np.float32) if rng.random() < 0.15 else d for d in dets]
+    conf = [0.2, 0.3, 0.4, 0.25][seed % 4]
+    ref = mg.run_reference(dets, conf)
+    want = dict(frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
+                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref],
+                tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref])
+    replay(dets, conf, arena_frames=(7 if seed % 2 else 0), want=want)
+
+
+@needs_ref
+def test_buffered_iou_distance_equals_reference(monkeypatch):
+    """matching.buffered_iou_distance of the port: the same tlbr boxes in the same dtypes as the reference's, for detections built by either side and for
+    tracks with extrapolated motion states; the IoU itself (a device op in the port) is restated by the oracle here"""
+    from oracle import cnative
+    from yolov7_tracker_amd import synth
+    from yolov7_tracker_amd.tracker import matching as pm
+    from yolov7_tracker_amd.tracker.c_biou_tracker import C_BIoUSTrack
+    mg = _ref_module()
+    mod = mg.load_c_biou()
+    rm = ref_harness.load_tracker().matching
+    monkeypatch.setattr(pm, "_cost", lambda a, b: 1 - cnative.bbox_overlaps(np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)))
+    # tracks of a reference run (full buffers, extrapolated states, lost tracks) against the next frame's detections
+    dets = synth.make_detections(60, 50, seq_idx=41, miss=0.3, bounce=True)
+    mod.BaseTrack._count = 0
+    trk = mod.C_BIoUTracker(ref_harness.make_opts(), frame_rate=30)
+    for d in dets[:-1]:
+        trk.update(d, None)
+    tracks = trk.tracked_stracks + trk.lost_stracks
+    last = dets[-1]
+    ref_dets = [mod.C_BIoUSTrack(c, mod.C_BIoUSTrack.tlbr2tlwh(b), s) for c, b, s in zip(last[:, -1], last[:, :4], last[:, 4])]
+    port_dets = [C_BIoUSTrack(c, C_BIoUSTrack.tlbr2tlwh(b), s) for c, b, s in zip(last[:, -1], last[:, :4], last[:, 4])]
+    for r, p in zip(ref_dets, port_dets):
+        for a in ("buffer_bbox1", "buffer_bbox2", "motion_state1", "motion_state2", "tlwh", "tlbr"):
+            x, y = getattr(r, a), getattr(p, a)
+            assert x.dtype == y.dtype and np.array_equal(x, y), a
+    for level in (1, 2):
+        want = rm.buffered_iou_distance(tracks, ref_dets, level=level)
+        assert np.array_equal(pm.buffered_iou_distance(tracks, port_dets, level=level), want)
+        assert np.array_equal(pm.buffered_iou_distance(tracks, ref_dets, level=level), want)
+    assert pm.buffered_iou_distance([], port_dets).shape == (0, len(port_dets))

@@ -16,7 +16,7 @@
 #include "y7t_track_core.h"
 
 struct Y7TTrkCfg {
-    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT
+    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT / Y7T_DEEPSORT / Y7T_C_BIOU
     int kf;             // Kalman kind
     int cap_t, cap_d;   // capacities: live tracks (tracked+lost), detections per frame
     int max_time_lost;  // int(frame_rate / 30 * track_buffer)
@@ -148,7 +148,8 @@ Y7T_FN void y7t_arena_copy(const Y7TExec& ex, void* blob, bool load) {
 Y7T_FN void y7t_arena_load(const Y7TExec& ex, void* blob) { y7t_arena_copy(ex, blob, true); }
 Y7T_FN void y7t_arena_store(const Y7TExec& ex, void* blob) { y7t_arena_copy(ex, blob, false); }
 
-enum { Y7T_ERR_CAP_T = 1, Y7T_ERR_CAP_D = 2, Y7T_ERR_OUT = 4, Y7T_ERR_KIND = 8 /* a DeepSORT pool stepped with detections by the plain step */ };
+enum { Y7T_ERR_CAP_T = 1, Y7T_ERR_CAP_D = 2, Y7T_ERR_OUT = 4, Y7T_ERR_KIND = 8 /* a DeepSORT pool stepped with detections by the plain step */,
+       Y7T_ERR_PREDICT = 16 /* update_without_detection on a non-empty pool of a tracker without a motion model (C-BIoU) */ };
 
 #if !Y7T_DEVICE
 static inline long long clock64() { return 0; }
@@ -840,6 +841,27 @@ Y7T_FN void y7t_gather_det_tlbr(const Y7TExec& ex, const Y7TTrk& s, const int* l
     }
 }
 
+// the tail of an association: the matched rows (s.xrow[i] >= 0) whose s.tmpa[i] says 1 (update) / 2 (re_activate) appended to the frame's act / refind lists, in row order
+Y7T_FN void y7t_append_matches(const Y7TExec& ex, const Y7TTrk& s, const int* tracks, int na, int& n_act, int& n_refind) {
+    n_act = y7t_compact(ex, na, [&](int i) { return s.xrow[i] >= 0 && s.tmpa[i] == 1; }, s.tmpb, 0);
+    // tmpb holds row indices; translate into slots appended to actl
+    {
+        const int base = s.h->n_act_last;
+        for (int k = ex.tid; k < n_act; k += ex.nt) s.actl[base + k] = tracks[s.tmpb[k]];
+        y7t_sync(ex);
+        if (ex.tid == 0) s.h->n_act_last = base + n_act;
+        y7t_sync(ex);
+    }
+    n_refind = y7t_compact(ex, na, [&](int i) { return s.xrow[i] >= 0 && s.tmpa[i] == 2; }, s.tmpb, 0);
+    {
+        const int base = s.h->n_refind_last;
+        for (int k = ex.tid; k < n_refind; k += ex.nt) s.refind[base + k] = tracks[s.tmpb[k]];
+        y7t_sync(ex);
+        if (ex.tid == 0) s.h->n_refind_last = base + n_refind;
+        y7t_sync(ex);
+    }
+}
+
 // apply matches of one association (parallel over pairs: distinct tracks), then append to the
 // act / refind lists in row order.  mode 0: ByteTrack pool semantics (Tracked->update,
 // Lost->re_activate, anything else untouched); 1: SORT (Tracked->update, else re_activate);
@@ -872,23 +894,7 @@ Y7T_FN void y7t_apply_matches(const Y7TExec& ex, const Y7TTrk& s, const int* tra
         s.len[sl] = (what == 1) ? s.len[sl] + 1 : 0;
     }
     y7t_sync(ex);
-    n_act = y7t_compact(ex, na, [&](int i) { return s.xrow[i] >= 0 && s.tmpa[i] == 1; }, s.tmpb, 0);
-    // tmpb holds row indices; translate into slots appended to actl
-    {
-        const int base = s.h->n_act_last;
-        for (int k = ex.tid; k < n_act; k += ex.nt) s.actl[base + k] = tracks[s.tmpb[k]];
-        y7t_sync(ex);
-        if (ex.tid == 0) s.h->n_act_last = base + n_act;
-        y7t_sync(ex);
-    }
-    n_refind = y7t_compact(ex, na, [&](int i) { return s.xrow[i] >= 0 && s.tmpa[i] == 2; }, s.tmpb, 0);
-    {
-        const int base = s.h->n_refind_last;
-        for (int k = ex.tid; k < n_refind; k += ex.nt) s.refind[base + k] = tracks[s.tmpb[k]];
-        y7t_sync(ex);
-        if (ex.tid == 0) s.h->n_refind_last = base + n_refind;
-        y7t_sync(ex);
-    }
+    y7t_append_matches(ex, s, tracks, na, n_act, n_refind);
 }
 
 // STrack.multi_predict over a slot list (basetrack.py:253-271)
@@ -907,9 +913,10 @@ Y7T_FN void y7t_multi_predict(const Y7TExec& ex, const Y7TTrk& s, const int* lis
 
 // the end-of-frame list bookkeeping shared by update / update_without_detection
 // (bytetrack.py:185-194).  act/refind/lostn/removedl hold this frame's lists.
-Y7T_FN void y7t_finish(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int out_cap, int* out_count) {
+// tlbr(slot, double[4]) / tlwh(slot, double[4]): a pool track's box as the tracker's STrack class computes it (Kalman trackers: y7t_finish below)
+template <class TlbrFn, class TlwhFn>
+Y7T_FN void y7t_finish_g(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int out_cap, int* out_count, TlbrFn tlbr, TlwhFn tlwh) {
     Y7TTrkHdr* h = s.h;
-    const int kf = h->cfg.kf;
     int nt_ = h->n_tracked, nl = h->n_lost;
     const int n_act = h->n_act_last, n_ref = h->n_refind_last, n_lostn = h->n_lostn_last, n_rem = h->n_removed_last;
     // tracked = [t for t in tracked if t.state == Tracked]
@@ -956,14 +963,11 @@ Y7T_FN void y7t_finish(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int
     y7t_sync(ex);
     // remove_duplicate_stracks(tracked, lost): pairs with IoU distance < 0.15 (basetrack.py:563-576)
     if (n1 > 0 && n2 > 0) {
-        y7t_gather_track_tlbr(ex, s, s.tracked, n1);
+        for (int i = ex.tid; i < n1; i += ex.nt) tlbr(s.tracked[i], s.ttlbr + 4 * (size_t)i);
         y7t_sync(ex);
         // lost boxes go through dtlbr-sized scratch? use cost tail: keep a second tlbr array in `cost`
         double* lb = s.cost;  // n2*4 doubles, consumed before cost is needed again
-        for (int i = ex.tid; i < n2; i += ex.nt) {
-            const int sl = s.lost[i];
-            y7t_track_tlbr(kf, s.mean + 8 * (size_t)sl, s.f32m[sl], lb + 4 * (size_t)i);
-        }
+        for (int i = ex.tid; i < n2; i += ex.nt) tlbr(s.lost[i], lb + 4 * (size_t)i);
         for (int i = ex.tid; i < n1; i += ex.nt) s.tmpa[i] = 0;
         for (int i = ex.tid; i < n2; i += ex.nt) s.tmpb[i] = 0;
         y7t_sync(ex);
@@ -1030,11 +1034,18 @@ Y7T_FN void y7t_finish(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int
             const int sl = s.tracked[s.tmpa[k]];
             double* o = out_rows + 8 * (size_t)k;
             o[0] = s.tid[sl];
-            y7t_track_tlwh(kf, s.mean + 8 * (size_t)sl, s.f32m[sl], o + 1);
+            tlwh(sl, o + 1);
             o[5] = s.cls[sl]; o[6] = s.score[sl]; o[7] = sl;
         }
     }
     y7t_sync(ex);
+}
+
+Y7T_FN void y7t_finish(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int out_cap, int* out_count) {
+    const int kf = s.h->cfg.kf;
+    y7t_finish_g(ex, s, out_rows, out_cap, out_count,
+                 [&](int sl, double* o) { y7t_track_tlbr(kf, s.mean + 8 * (size_t)sl, s.f32m[sl], o); },
+                 [&](int sl, double* o) { y7t_track_tlwh(kf, s.mean + 8 * (size_t)sl, s.f32m[sl], o); });
 }
 
 // One frame.  dets: n x 6 float32 rows [x1, y1, x2, y2, conf, cls] (n < 0: update_without_detection)
@@ -1239,6 +1250,14 @@ Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg
     y7t_sync(ex);
 }
 
+#include "y7t_track_cbiou.h"
+
+// the frame step of any pool the plain step serves: C-BIoU pools run their own program (y7t_track_cbiou.h), every other kind y7t_tracker_step_body
+Y7T_FN void y7t_tracker_step_any(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_C_BIOU) y7t_tracker_step_cbiou_body(ex, blob, dets, n, out_rows, out_cap, out_count);
+    else y7t_tracker_step_body(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+}
+
 Y7T_NOINL void y7t_tracker_step(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
-    y7t_tracker_step_body(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    y7t_tracker_step_any(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
 }

@@ -202,6 +202,43 @@ __global__ void __launch_bounds__(MAXT) k_tracker_step_frames(void* state, const
     y7t_arena_store(ex, state);
 }
 
+// ---- C-BIoU (y7t_track_cbiou.h): kernels of their own, so that the instances above keep their register allocation.  The host picks them for a pool
+// initialised as Y7T_C_BIOU (note_state_kind); a batch launch cannot see its pools' kinds, so it takes k_tracker_step_mixed -- which branches on every
+// workgroup's pool -- while a C-BIoU pool exists in the process ----
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_cbiou(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, unsigned fast_bytes) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_tracker_step_cbiou_body(ex, state, dets, n, out_rows, out_cap, out_count);
+}
+
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_cbiou_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count,
+                                                                     int out_cap, int n_frames, unsigned fast_bytes, unsigned arena_bytes) {
+    Y7TExec ex = make_exec(fast_bytes);
+    if (arena_bytes) { ex.arena = y7t_smem + Y7T_LDS_HDR + fast_bytes; ex.arena_bytes = arena_bytes; }
+    y7t_arena_load(ex, state);
+    for (int f = 0; f < n_frames; ++f) {
+        y7t_tracker_step_cbiou_body(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
+        y7t_sync(ex);
+    }
+    y7t_arena_store(ex, state);
+}
+
+__global__ void __launch_bounds__(512) k_tracker_step_mixed(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
+                                                            int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
+    const int b = blockIdx.x;
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_tracker_step_any(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
+}
+
+// a step the library refuses on the device side: the pool's status word says why (Y7T_ERR_KIND), no row is returned
+__global__ void k_tracker_refuse(void* state, int* out_count) {
+    if (threadIdx.x == 0) {
+        ((Y7TTrkHdr*)state)->status |= Y7T_ERR_KIND;
+        if (out_count) *out_count = 0;
+    }
+}
+
 // ---- DeepSORT (y7t_track_deepsort.h) ----
 __global__ void k_feat_init(void* fblob, int cap_t, int cap_d, int dim, int budget) {
     Y7TExec ex;
@@ -532,6 +569,11 @@ static size_t state_arena_bytes(const void* state) {
     auto it = g_state_arena.find(state);
     return it == g_state_arena.end() ? 0 : it->second;
 }
+static bool any_cbiou_state() {
+    std::lock_guard<std::mutex> l(g_kind_mu);
+    for (const auto& kv : g_state_kind) if (kv.second == Y7T_C_BIOU) return true;
+    return false;
+}
 static int state_kind(const void* state) {
     std::lock_guard<std::mutex> l(g_kind_mu);
     auto it = g_state_kind.find(state);
@@ -556,7 +598,9 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
                                 double conf_thresh, double iou_thresh, int max_time_lost, int flags, int* id_counter,
                                 y7t_stream stream) {
     Y7T_ARG_CHECK(state && id_counter && cap_t > 0 && cap_d > 0);
-    Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT);
+    Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT ||
+                  tracker_kind == Y7T_C_BIOU);
+    if (tracker_kind == Y7T_C_BIOU) kalman_kind = Y7T_KF_XYAH;      // (C-BIoU has no Kalman filter: the kind is ignored)
     if (tracker_kind == Y7T_DEEPSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("DeepSORT gates on xyah measurements (deepsort.py:59): kalman_format default / strongsort only");
         return Y7T_E_ARG;
@@ -606,7 +650,11 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     const int nt = step_threads(threads);
     Y7T_ARG_CHECK(nt > 0);
     static std::atomic<unsigned long long> attr_done{0}, attr_done_m{0};
-    if (nt <= 512) {
+    if (nt <= 512 && any_cbiou_state()) {      // (a C-BIoU pool may be among the states: the kernel that branches on each pool's kind)
+        static std::atomic<unsigned long long> attr_done_x{0};
+        if (int e = ensure_lds_once(k_tracker_step_mixed, kFastBytes + Y7T_LDS_HDR, attr_done_x)) return e;
+        hipLaunchKernelGGL(k_tracker_step_mixed, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
+    } else if (nt <= 512) {
         if (int e = ensure_lds_once(k_tracker_step<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)) return e;
         hipLaunchKernelGGL(k_tracker_step<512>, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     } else {
@@ -630,6 +678,21 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
     }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
     const unsigned fb = step_fast_bytes(n);
+    if (state_kind(state) == Y7T_C_BIOU) {
+        static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
+        if (nt <= 256) {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou<256>, kFastBytes + Y7T_LDS_HDR, cb_done_s)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        } else if (nt <= 512) {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou<512>, kFastBytes + Y7T_LDS_HDR, cb_done_m)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        } else {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou<1024>, kFastBytes + Y7T_LDS_HDR, cb_done)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        }
+        Y7T_LAUNCH_CHECK();
+        return 0;
+    }
     if (nt <= 256) {
         if (int e = ensure_lds_once(k_tracker_step1<256>, kFastBytes + Y7T_LDS_HDR, attr_done_s)) return e;
         hipLaunchKernelGGL(k_tracker_step1<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
@@ -663,6 +726,24 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
     unsigned arena = 0, fast = kFastBytes;
     if (ab && ab + 64 * 1024 + Y7T_LDS_HDR <= kLdsMax) { arena = (unsigned)((ab + 15) & ~(size_t)15); fast = (kLdsMax - Y7T_LDS_HDR - arena) & ~15u; if (fast > kFastBytes) fast = kFastBytes; }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
+    if (state_kind(state) == Y7T_C_BIOU) {
+        static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
+        if (nt <= 256) {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<256>, kLdsMax, cb_done_s)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        } else if (nt <= 512) {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<512>, kLdsMax, cb_done_m)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<512>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        } else {
+            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<1024>, kLdsMax, cb_done)) return e;
+            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<1024>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        }
+        Y7T_LAUNCH_CHECK();
+        return 0;
+    }
     if (nt <= 256) {
         if (int e = ensure_lds_once(k_tracker_step_frames<256>, kLdsMax, attr_done_s)) return e;
         hipLaunchKernelGGL(k_tracker_step_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap, n_frames,
@@ -700,6 +781,12 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     Y7T_ARG_CHECK(cap_tracks <= 64 * Y7T_EMBED_WORKERS);      // (k_embed_dist: a workgroup owns at most 64 live slots)
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
+    if (state_kind(state) == Y7T_C_BIOU) {      // no Kalman state, no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+        hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+        Y7T_LAUNCH_CHECK();
+        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as C-BIoU -- it steps through y7t_tracker_step");
+        return Y7T_E_STATE;
+    }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
     if (int e = nt <= 256 ? ensure_lds_once(k_tracker_step_deepsort<256>, kFastBytes + Y7T_LDS_HDR, attr_done_s)
               : nt <= 512 ? ensure_lds_once(k_tracker_step_deepsort<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)

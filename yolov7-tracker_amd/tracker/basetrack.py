@@ -298,6 +298,7 @@ class BaseTracker(object):
     """SORT (basetrack.py:346-537).  opts: conf_thresh, track_buffer, kalman_format, img_size, iou_thresh
     (+ optional max_tracks / max_dets capacities of the device pool)."""
     _KIND = 0  # Y7T_TRACKER_SORT
+    _VIEW = None  # class of the track views update() returns (None: _PoolTrack)
 
     def __init__(self, opts, frame_rate=30, *args, **kwargs):
         _lib.require_gpu()
@@ -451,10 +452,10 @@ class BaseTracker(object):
         rows = host[:cnt]
         ids, slots = rows[:, 0].astype(np.int64).tolist(), rows[:, 7].astype(np.int64).tolist()
         boxes, kcls, score = list(rows[:, 1:5].copy()), list(rows[:, 5].astype(np.float32)), list(rows[:, 6].astype(np.float32))
-        fid, kf, new = self.frame_id, self.opts.kalman_format, object.__new__
+        fid, kf, new, view = self.frame_id, self.opts.kalman_format, object.__new__, self._VIEW or _PoolTrack
         out = []
         for slot, tid, box, c, sc in zip(slots, ids, boxes, kcls, score):
-            o = new(_PoolTrack)
+            o = new(view)
             o.__dict__ = {"_pool": self, "_slot": slot, "_epoch": fid, "track_id": tid, "_tlwh_now": box, "cls": c, "score": sc, "kalman_format": kf,
                           "features": [], "has_feature": False}
             out.append(o)

@@ -38,6 +38,21 @@ def iou_distance(atracks, btracks):
     return _cost(atlbrs, btlbrs)
 
 
+def buffered_iou_distance(atracks, btracks, level=1):
+    """matching.py:391-407 (C-BIoU): the tracks' motion states against the detections' buffered boxes, both as tlbr in their own dtype
+    (tlwh2tlbr of the C_BIoUSTrack objects), -> (N, M) float64 cost 1 - IoU.  level 1: motion_state1 / buffer_bbox1, level 2: motion_state2 / buffer_bbox2."""
+    assert level in [1, 2], 'level must be 1 or 2'
+    if level == 1:
+        atlbrs = [track.tlwh2tlbr(track.motion_state1) for track in atracks]
+        btlbrs = [det.tlwh2tlbr(det.buffer_bbox1) for det in btracks]
+    else:
+        atlbrs = [track.tlwh2tlbr(track.motion_state2) for track in atracks]
+        btlbrs = [det.tlwh2tlbr(det.buffer_bbox2) for det in btracks]
+    if len(atlbrs) == 0 or len(btlbrs) == 0:
+        return np.ones((len(atlbrs), len(btlbrs)), dtype=np.float64)
+    return _cost(atlbrs, btlbrs)
+
+
 def lapjv_device(cost, cost_limit):
     """-> (opt, x, y) like lap.lapjv(cost, extend_cost=True, cost_limit=cost_limit)."""
     _lib.require_gpu()
