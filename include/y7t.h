@@ -30,7 +30,8 @@ enum { Y7T_OK = 0, Y7T_E_ARG = -1, Y7T_E_HIP = -2, Y7T_E_CAPACITY = -3, Y7T_E_ST
 /* Kalman filter kinds == KALMAN_DICT keys, tracker/basetrack.py:64-69 */
 enum { Y7T_KALMAN_DEFAULT = 0, Y7T_KALMAN_NAIVE = 1, Y7T_KALMAN_BOTSORT = 2, Y7T_KALMAN_STRONGSORT = 3 };
 /* tracker kinds == TRACKER_DICT keys implemented on the device, tracker/track.py:56-65 */
-enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4 };
+enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4,
+       Y7T_TRACKER_UAVMOT = 5 };
 
 const char* y7t_last_error(void);
 int y7t_version(void);
@@ -52,6 +53,10 @@ int y7t_stream_destroy(y7t_stream stream);
 /* matching.iou_distance -> ious -> cython_bbox.bbox_overlaps, tracker/matching.py:44-82.
  * cost[i*m + j] = 1 - IoU(a_i, b_j) with the "+1 pixel" convention. a: n x 4 tlbr, b: m x 4. */
 int y7t_iou_cost_f64(const double* a_tlbr, int n, const double* b_tlbr, int m, double* cost, y7t_stream stream);
+/* matching.structure_similarity_distance (tracker/matching.py:284-388, UAVMOT): out[n x m] = max(0, cosine distance) of the structure vectors
+ * [max, min, included angle] of n track centres (mean[0:2], float64 arithmetic) and m detection centres (get_xy(): float32 values, float32 distance
+ * arithmetic).  Device pointers; n + m <= 2048 (one workgroup holds the vectors). */
+int y7t_structure_distance_f64(const double* track_xy, int n, const double* det_xy, int m, double* out, y7t_stream stream);
 
 /* KalmanFilter.initiate, tracker/kalman_filter.py:190-221 (xyah), :436-467 (xywh).
  * z: K x 4 measurements; mean: K x 8; cov: K x 64.  flags bit0: keep the std products in
@@ -147,6 +152,13 @@ int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* warp, int N, y
  * (the reference's update_without_detection needs a Kalman mean and fails there) and changes nothing; with an empty pool it advances the frame.  The lost
  * list is never aged (as in the reference): size cap_tracks for the length of the sequence -- an overflow sets status bit 1.
  * y7t_tracker_step_deepsort refuses a C-BIoU pool: Y7T_E_STATE and status bit 8. */
+
+/* UAVMOT (tracker/uavmot.py:109-256, tracker kind Y7T_TRACKER_UAVMOT; Kalman kinds default / botsort / strongsort): ByteTrack with a first association
+ * at 0.7 that is re-solved at 0.8 on the fused cost 0.98 * IoU distance + (1 - 0.98) * structure distance (y7t_structure_distance_f64) unless it matched
+ * nothing or only the pair (0, 0); the second association's unmatched indices mark strack_pool[idx] lost, as in the reference.  Same pool blob, same
+ * layout and the same entry points as ByteTrack: y7t_tracker_step, y7t_tracker_step_frames, y7t_tracker_step_batch (a batch may mix UAVMOT pools with
+ * the others).  The structure vectors of a frame (3 doubles per pool track and per detection) live in the blob's dense-LAP work array, which holds
+ * (cap_t + max(cap_t, cap_d)) x 40 bytes.  y7t_tracker_step_deepsort refuses a UAVMOT pool: Y7T_E_STATE and status bit 8. */
 
 /* DeepSORT (tracker/deepsort.py:79-227, tracker kind Y7T_TRACKER_DEEPSORT): appearance + motion.  Next to the pool blob the tracker owns
  * a FEATURE STATE (y7t_deepsort_feature_bytes, y7t_deepsort_init): per slot the last `budget` appearance vectors of the track

@@ -37,6 +37,7 @@ SIGNATURES = {
     "y7t_last_kernel": (ctypes.c_char_p, []),
     "y7t_device_count": (c_int, []),
     "y7t_iou_cost_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "y7t_structure_distance_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "y7t_kf_initiate_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "y7t_kf_multi_predict_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "y7t_kf_project_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -2,7 +2,7 @@
 // program over a device-resident struct-of-arrays track pool.  Portable text (see
 // y7t_track_core.h for the two ways it is compiled).
 //
-// Restates /root/reference/tracker/bytetrack.py:41-204 (ByteTrack.update),
+// Restates /root/reference/tracker/bytetrack.py:41-204 (ByteTrack.update), tracker/uavmot.py:109-256 (UAVMOT.update: y7t_amf_first),
 // tracker/basetrack.py:368-487 (BaseTracker.update == SORT), :489-537
 // (update_without_detection), :222-339 (STrack.activate/re_activate/update/multi_predict),
 // :183-219 (tlwh/tlbr), :540-576 (joint/sub/remove_duplicate_stracks).
@@ -16,7 +16,7 @@
 #include "y7t_track_core.h"
 
 struct Y7TTrkCfg {
-    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT / Y7T_DEEPSORT / Y7T_C_BIOU
+    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT / Y7T_DEEPSORT / Y7T_C_BIOU / Y7T_UAVMOT
     int kf;             // Kalman kind
     int cap_t, cap_d;   // capacities: live tracks (tracked+lost), detections per frame
     int max_time_lost;  // int(frame_rate / 30 * track_buffer)
@@ -1048,12 +1048,167 @@ Y7T_FN void y7t_finish(const Y7TExec& ex, const Y7TTrk& s, double* out_rows, int
                  [&](int sl, double* o) { y7t_track_tlwh(kf, s.mean + 8 * (size_t)sl, s.f32m[sl], o); });
 }
 
+// ---- UAVMOT's AMF pass (uavmot.py:179-190, matching.py:284-388): the structure representation of a list of centres and the fused cost ----
+#define Y7T_AMF_LAMBDA 0.98
+#define Y7T_AMF_W 0.020000000000000018      // (1 - 0.98 in float64: local_relation_fuse_motion's weight of the structure distance)
+#define Y7T_AMF_R 400                       // local_R
+
+// math.atan2(y, x), the exact directions pinned to the correctly rounded values glibc returns (the device's atan2 need not round them correctly, and
+// int(a * 180 / pi) of a value an ulp off flips at 90, 45, 135, 180: axis-parallel and diagonal offsets are common on the half-pixel lattice of NMS boxes)
+Y7T_FN double y7t_atan2_pinned(double y, double x) {
+    const double pi = 3.141592653589793, pi_2 = 1.5707963267948966, pi_4 = 0.7853981633974483, pi3_4 = 2.356194490192345;
+    if (x == 0.0 && y == 0.0) return signbit(x) ? copysign(pi, y) : copysign(0.0, y);
+    if (x == 0.0) return copysign(pi_2, y);
+    if (y == 0.0) return x > 0.0 ? copysign(0.0, y) : copysign(pi, y);
+    if (fabs(x) == fabs(y)) return copysign(x > 0.0 ? pi_4 : pi3_4, y);
+    return atan2(y, x);
+}
+
+// matching.angle (matching.py:321-342): truncated degrees of both offsets, then their included angle by the reference's integer rules
+Y7T_FN int y7t_amf_angle(double dx1, double dy1, double dx2, double dy2) {
+    const int a1 = (int)(y7t_atan2_pinned(dy1, dx1) * 180.0 / 3.141592653589793);
+    const int a2 = (int)(y7t_atan2_pinned(dy2, dx2) * 180.0 / 3.141592653589793);
+    if (a1 * a2 >= 0) return a1 > a2 ? a1 - a2 : a2 - a1;
+    int inc = (a1 < 0 ? -a1 : a1) + (a2 < 0 ? -a2 : a2);
+    if (inc > 180) inc = 360 - inc;
+    return inc;
+}
+
+// np.linalg.norm([p0, p1]): float64 -- OpenBLAS ddot's tail fuses the second product; float32 (detections: get_xy is float32) -- two rounded squares and a sum
+Y7T_FN double y7t_amf_norm(double p0, double p1) { return sqrt(fma(p1, p1, p0 * p0)); }
+Y7T_FN float y7t_amf_norm(float p0, float p1) { const float a = p0 * p0, b = p1 * p1; return sqrtf(a + b); }
+Y7T_FN double y7t_amf_abs(double d) { return sqrt(d * d); }      // np.linalg.norm of a 0-d array
+Y7T_FN float y7t_amf_abs(float d) { return sqrtf(d * d); }
+
+// structure_representation (matching.py:344-388) of element a of a list of n centres: [max, min, angle] over the others at 0 < distance < 400, the first
+// occurrence of the maximum and of the minimum in list order; F: the dtype of the centres (double: track means, float: detections' get_xy).  at(b, c): centre b, coordinate c
+template <class F, class At>
+Y7T_FN void y7t_amf_vec(int n, int a, At at, double* o) {
+    const F ax = at(a, 0), ay = at(a, 1);
+    F mx = 0, mn = 0;
+    int imx = -1, imn = -1;
+    for (int b = 0; b < n; ++b) {
+        const F dx = ax - at(b, 0), dy = ay - at(b, 1);
+        const F l = y7t_amf_norm(y7t_amf_abs(dx), y7t_amf_abs(dy));
+        if (l < (F)Y7T_AMF_R && l > (F)0) {
+            if (imx < 0 || l > mx) { mx = l; imx = b; }
+            if (imn < 0 || l < mn) { mn = l; imn = b; }
+        }
+    }
+    if (imx < 0) { o[0] = 0.0001; o[1] = 0.0001; o[2] = 0.0001; return; }
+    o[0] = mx; o[1] = mn;
+    if (mx == mn) { o[2] = 0.0001; return; }
+    const F x1 = at(imx, 0) - ax, y1 = at(imx, 1) - ay, x2 = at(imn, 0) - ax, y2 = at(imn, 1) - ay;      // (v1 = B_max - A, v2 = B_min - A, in F)
+    o[2] = y7t_amf_angle(x1, y1, x2, y2);
+}
+
+// np.maximum(0, cdist(u, v, "cosine")): unfused left-to-right sums, the cosine clipped to [-1, 1]
+Y7T_FN double y7t_amf_cos_dist(const double* u, const double* v) {
+    const double dot = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+    const double uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
+    const double vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    double c = dot / (sqrt(uu) * sqrt(vv));
+    c = c > 1.0 ? 1.0 : c < -1.0 ? -1.0 : c;
+    const double d = 1.0 - c;
+    return d > 0.0 ? d : 0.0;
+}
+// local_relation_fuse_motion: lambda * IoU distance + (1 - lambda) * structure distance
+Y7T_FN double y7t_amf_fuse(double iou_d, double sd) { const double a = Y7T_AMF_LAMBDA * iou_d, b = Y7T_AMF_W * sd; return a + b; }
+
+// the fused pair: a box with its structure vector (y7t_pairs contexts; the box geometry rejects as for IoU -- a pair of boxes apart costs 0.98 + W * S >= 0.98,
+// above any limit the AMF solve uses)
+struct Y7TAmfC { Y7TBoxC b; double sv[3]; };
+struct Y7TAmfR { Y7TBoxR b; double sv[3]; };
+struct Y7TAmfGeo {
+    static constexpr bool on = true;
+    using G = Y7TBoxGeo::G;
+    Y7T_MFN G group(const Y7TAmfC& c, bool valid) const { return Y7TBoxGeo().group(c.b, valid); }
+    Y7T_MFN double key(const Y7TAmfC& c) const { return c.b.v[0]; }
+    Y7T_MFN bool near(const Y7TAmfR& r, const G& g) const { return Y7TBoxGeo().near(r.b, g); }
+};
+
+// matching.linear_assignment(local_relation_fuse_motion(iou_distance(pool, D_high), pool, D_high), thresh) for the boxes in ttlbr / dtlbr and the
+// structure vectors tsv[3 na] / dsv[3 nb] -> xrow / ycol.  y7t_assoc with the fused cost: sparse solver first (a candidate costs <= thresh < 0.98, so its
+// boxes overlap), the dense lapjv fallback on the fused matrix.  tsv / dsv must not live in the fast scratch or the cost matrix (both solvers use those).
+Y7T_FN void y7t_assoc_amf(const Y7TExec& ex, const Y7TTrk& s, int na, int nb, double thresh, const double* tsv, const double* dsv) {
+    if (na == 0 || nb == 0) {
+        for (int i = ex.tid; i < na; i += ex.nt) s.xrow[i] = -1;
+        for (int j = ex.tid; j < nb; j += ex.nt) s.ycol[j] = -1;
+        y7t_sync(ex);
+        return;
+    }
+    int sp = 0;
+    if ((long long)na * nb >= Y7T_SPARSE_MIN &&
+        (sp = y7t_assoc_sparse_fn(ex, s, na, nb, thresh,
+                                  [&](int j) { const double* d = dsv + 3 * (size_t)j; return Y7TAmfC{y7t_box_col(s.dtlbr + 4 * (size_t)j), {d[0], d[1], d[2]}}; },
+                                  [&](int i) { const double* t = tsv + 3 * (size_t)i; return Y7TAmfR{y7t_box_row(s.ttlbr + 4 * (size_t)i), {t[0], t[1], t[2]}}; },
+                                  [&](const Y7TAmfR& rl, int r, const Y7TAmfC& q) {
+                                      const double iou = y7t_box_iou_dist(rl.b, r, q.b);
+                                      if (iou == 1.0) return 1.0;      // (apart: 0.98 + W * S, never a candidate)
+                                      const double u[3] = {y7t_row_at(rl.sv[0], r), y7t_row_at(rl.sv[1], r), y7t_row_at(rl.sv[2], r)};
+                                      return y7t_amf_fuse(iou, y7t_amf_cos_dist(u, q.sv));
+                                  }, Y7TAmfGeo())) == 1)
+        return;
+    Y7TLap L;
+    L.nr = na; L.nc = nb; L.ld = nb; L.n = na + nb; L.half = thresh / 2.0;
+    L.prof = nullptr;
+    const size_t ws = y7t_al(y7t_lap_ws_bytes(L.n)), cb = (size_t)na * nb * sizeof(double);
+    void* lapws = s.lapws;
+    double* cost = s.cost;
+    size_t off = 0;
+    if (ex.fast && ws <= ex.fast_bytes) { lapws = ex.fast; off = ws; }
+    if (ex.fast && off + cb <= ex.fast_bytes) cost = (double*)(ex.fast + off);
+    {   // (as y7t_cost_matrix: a lane per column, a wave per row residue)
+        const int lanes = ex.nt < 64 ? ex.nt : 64, nw = ex.nt / lanes, wave = ex.tid / lanes, lane = ex.tid - wave * lanes;
+        for (int j = lane; j < nb; j += lanes)
+            for (int i = wave; i < na; i += nw)
+                cost[(size_t)i * nb + j] = y7t_amf_fuse(y7t_iou_dist(s.ttlbr + 4 * (size_t)i, s.dtlbr + 4 * (size_t)j), y7t_amf_cos_dist(tsv + 3 * (size_t)i, dsv + 3 * (size_t)j));
+        y7t_sync(ex);
+    }
+    L.c = cost;
+    y7t_lap_bind(L, lapws, L.n);      // (binds only: tsv / dsv in the blob's lapws were consumed by the cost matrix above)
+    if (sp == 2 || y7t_lap_solve_sap(ex, L)) y7t_lap_solve_literal(ex, L);
+    for (int i = ex.tid; i < na; i += ex.nt) s.xrow[i] = (L.x[i] >= nb) ? -1 : L.x[i];
+    for (int j = ex.tid; j < nb; j += ex.nt) s.ycol[j] = (L.y[j] >= na) ? -1 : L.y[j];
+    y7t_sync(ex);
+}
+
+// the first association of UAVMOT after its 0.7 solve (xrow / ycol of pool x D_high, boxes in ttlbr / dtlbr): `if not matched_pair0.any()` keeps that
+// result -- no match, or the single match (0, 0); otherwise the structure vectors of the pool (means after multi_predict) and of D_high (get_xy) and the
+// fused re-solve at 0.8.  The vectors live in the state blob's dense-LAP work array (3 doubles per pool track and per detection: (cap_t + cap_d) x 24 bytes
+// of its >= (cap_t + cap_d) x 40), the centres in the fast scratch or behind the vectors.
+Y7T_FN void y7t_amf_first(const Y7TExec& ex, const Y7TTrk& s, const int* pool, int na, const int* dhi, int nb) {
+    const int any = y7t_compact(ex, na, [&](int i) { return s.xrow[i] > 0 || (i > 0 && s.xrow[i] == 0); }, s.tmpa, 0);
+    if (any == 0) return;
+    double* tsv = (double*)s.lapws;
+    double* dsv = tsv + 3 * (size_t)na;
+    double* txy = dsv + 3 * (size_t)nb;
+    const size_t cbytes = 16 * (size_t)na + 8 * (size_t)nb;
+    if (ex.fast && cbytes <= ex.fast_bytes) txy = (double*)ex.fast;
+    float* dxy = (float*)(txy + 2 * (size_t)na);
+    for (int i = ex.tid; i < na; i += ex.nt) { const double* m = s.mean + 8 * (size_t)pool[i]; txy[2 * i] = m[0]; txy[2 * i + 1] = m[1]; }
+    for (int j = ex.tid; j < nb; j += ex.nt) {      // get_xy: tlwh2xywh(tlwh)[:2] -- tl + wh // 2, float32
+        const float* b = s.dbox + 4 * (size_t)dhi[j];
+        dxy[2 * j] = b[0] + floorf(b[2] / 2); dxy[2 * j + 1] = b[1] + floorf(b[3] / 2);
+    }
+    y7t_sync(ex);
+    for (int k = ex.tid; k < na + nb; k += ex.nt) {      // (a lane per element: an O(n) scan of its list, every lane reading the same centre)
+        if (k < na) y7t_amf_vec<double>(na, k, [&](int b, int c) { return txy[2 * b + c]; }, tsv + 3 * (size_t)k);
+        else y7t_amf_vec<float>(nb, k - na, [&](int b, int c) { return dxy[2 * b + c]; }, dsv + 3 * (size_t)(k - na));
+    }
+    y7t_sync(ex);
+    y7t_assoc_amf(ex, s, na, nb, 0.8, tsv, dsv);
+}
+
 // One frame.  dets: n x 6 float32 rows [x1, y1, x2, y2, conf, cls] (n < 0: update_without_detection)
 // The body is inlined where it is named: y7t_tracker_step (below) is the CALLED copy every launch of more than 256 threads shares; the <= 256-thread kernels
 // (csrc/y7t_tracker.hip) inline it, because a called function does not inherit its kernel's __launch_bounds__ -- compiled for the default 1024 threads a lane has 128
 // registers, and what the frame step keeps live around its Kalman updates spills to scratch memory; under __launch_bounds__(256) a lane may use 512 (round 6)
-Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap,
-                                  int* out_count, const double* gmc_warp) {
+// UAV: UAVMOT (uavmot.py:109-256) -- ByteTrack with a 0.7 first solve, the AMF re-solve behind it (y7t_amf_first) and the second association's unmatched
+// indices applied to the pool (below); its own instances, so that the ByteTrack ones keep their code and register allocation
+template <bool UAV>
+Y7T_FN void y7t_tracker_step_body_t(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap,
+                                    int* out_count, const double* gmc_warp) {
     Y7TTrkHdr* h = (Y7TTrkHdr*)blob;
     const Y7TTrkCfg cfg = h->cfg;
     const Y7TTrk s = y7t_trk_bind_ex(ex, blob, cfg.cap_t, cfg.cap_d);
@@ -1130,7 +1285,11 @@ Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* de
         const int* la; const int* ld;
         int nA, nD, mode;
         double th;
-        if (ph == 0) { la = s.pool; nA = n_pool; ld = s.dhi; nD = n_hi; th = is_sort ? cfg.iou_thresh : 0.9; mode = is_sort ? 1 : 0; }
+        if (ph == 0) {
+            la = s.pool; nA = n_pool; ld = s.dhi; nD = n_hi; mode = is_sort ? 1 : 0;
+            if constexpr (UAV) th = 0.7;      // (uavmot.py:187; the 0.9-keyed profile stamps stay silent for this solve)
+            else th = is_sort ? cfg.iou_thresh : 0.9;
+        }
         else if (ph == 1) {
             if (is_sort) {
                 // unmatched Tracked pool tracks -> Lost
@@ -1155,6 +1314,7 @@ Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* de
         const int stamp = ph == 0 ? 3 : ph == 1 ? 6 : 8;
         Y7T_PROF(h, stamp);
         y7t_assoc(ex, s, nA, nD, th);
+        if constexpr (UAV) { if (ph == 0) y7t_amf_first(ex, s, la, nA, ld, nD); }
         Y7T_PROF(h, stamp + 1);
         y7t_apply_matches(ex, s, la, nA, ld, dets, mode, na, nr);
         if (ph == 0) {
@@ -1165,7 +1325,11 @@ Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* de
             y7t_sync(ex);
         } else if (ph == 1) {
             const int nl_new = y7t_compact(ex, nA, [&](int i) { return s.xrow[i] < 0; }, s.tmpa, 0);
-            for (int k = ex.tid; k < nl_new; k += ex.nt) { const int sl = s.rem[s.tmpa[k]]; s.lostn[k] = sl; s.state[sl] = Y7T_LOST; }
+            if constexpr (UAV) {      // uavmot.py:222-225: the indices point into u_tracks0 but mark strack_pool[idx] lost -- reference quirk, kept
+                for (int k = ex.tid; k < nl_new; k += ex.nt) { const int sl = s.pool[s.tmpa[k]]; s.lostn[k] = sl; s.state[sl] = Y7T_LOST; }
+            } else {
+                for (int k = ex.tid; k < nl_new; k += ex.nt) { const int sl = s.rem[s.tmpa[k]]; s.lostn[k] = sl; s.state[sl] = Y7T_LOST; }
+            }
             if (ex.tid == 0) h->n_lostn_last = nl_new;
             y7t_sync(ex);
         } else {
@@ -1231,6 +1395,14 @@ Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* de
     Y7T_PROF(h, 11);
 }
 
+Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap,
+                                  int* out_count, const double* gmc_warp) {
+    y7t_tracker_step_body_t<false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+}
+Y7T_FN void y7t_tracker_step_uavmot_body(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count) {
+    y7t_tracker_step_body_t<true>(ex, blob, dets, n, out_rows, out_cap, out_count, nullptr);
+}
+
 // initialise a state blob (single thread is enough; called once)
 Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg, unsigned long long idc) {
     Y7TTrkHdr* h = (Y7TTrkHdr*)blob;
@@ -1258,6 +1430,22 @@ Y7T_FN void y7t_tracker_step_any(const Y7TExec& ex, void* blob, const float* det
     else y7t_tracker_step_body(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
 }
 
+// the called copy of the UAVMOT step (its launches of more than 512 threads)
+Y7T_NOINL void y7t_tracker_step_uavmot(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count) {
+    y7t_tracker_step_uavmot_body(ex, blob, dets, n, out_rows, out_cap, out_count);
+}
+
 Y7T_NOINL void y7t_tracker_step(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+#if !Y7T_DEVICE
+    // (the host build steps every kind through here; on the device UAVMOT pools launch kernels of their own -- csrc/y7t_tracker.hip -- so that this called
+    //  copy, which the kernels of more than 512 threads share, keeps its code)
+    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_UAVMOT) { y7t_tracker_step_uavmot(ex, blob, dets, n, out_rows, out_cap, out_count); return; }
+#endif
     y7t_tracker_step_any(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+}
+
+// every kind the plain step serves, UAVMOT included and inlined (k_tracker_step_mixed: a batch that may hold a C-BIoU or UAVMOT pool)
+Y7T_FN void y7t_tracker_step_all(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_UAVMOT) y7t_tracker_step_uavmot_body(ex, blob, dets, n, out_rows, out_cap, out_count);
+    else y7t_tracker_step_any(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
 }

@@ -228,7 +228,54 @@ __global__ void __launch_bounds__(512) k_tracker_step_mixed(void* const* states,
                                                             int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
     const int b = blockIdx.x;
     const Y7TExec ex = make_exec(fast_bytes);
-    y7t_tracker_step_any(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
+    y7t_tracker_step_all(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
+}
+
+// ---- UAVMOT (y7t_track_step.h: y7t_tracker_step_body_t<true>): kernels of their own like C-BIoU's; the <= 512-thread instances inline the step under their
+// own register budget, the 1024-thread ones call y7t_tracker_step_uavmot.  A batch of more than 512 threads that may hold a UAVMOT pool takes
+// k_tracker_step_mixed_wide, which calls either copy ----
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_uavmot(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, unsigned fast_bytes) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    if (MAXT <= 512) y7t_tracker_step_uavmot_body(ex, state, dets, n, out_rows, out_cap, out_count);
+    else y7t_tracker_step_uavmot(ex, state, dets, n, out_rows, out_cap, out_count);
+}
+
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_uavmot_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count,
+                                                                      int out_cap, int n_frames, unsigned fast_bytes, unsigned arena_bytes) {
+    Y7TExec ex = make_exec(fast_bytes);
+    if (arena_bytes) { ex.arena = y7t_smem + Y7T_LDS_HDR + fast_bytes; ex.arena_bytes = arena_bytes; }
+    y7t_arena_load(ex, state);
+    for (int f = 0; f < n_frames; ++f) {
+        if (MAXT <= 512) y7t_tracker_step_uavmot_body(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
+        else y7t_tracker_step_uavmot(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
+        y7t_sync(ex);
+    }
+    y7t_arena_store(ex, state);
+}
+
+__global__ void __launch_bounds__(1024) k_tracker_step_mixed_wide(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
+                                                                  int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
+    const int b = blockIdx.x;
+    const Y7TExec ex = make_exec(fast_bytes);
+    if (((const Y7TTrkHdr*)states[b])->cfg.tracker == Y7T_UAVMOT) y7t_tracker_step_uavmot(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b);
+    else y7t_tracker_step(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
+}
+
+// matching.structure_similarity_distance: one workgroup, the n + m structure vectors in LDS (a lane per element), then the n x m cosine distances
+__global__ void __launch_bounds__(256) k_structure_distance(const double* __restrict__ txy, int n, const double* __restrict__ dxy, int m, double* __restrict__ out) {
+    double* sv = (double*)y7t_smem;
+    for (int k = threadIdx.x; k < n + m; k += blockDim.x) {
+        if (k < n) y7t_amf_vec<double>(n, k, [&](int b, int c) { return txy[2 * b + c]; }, sv + 3 * k);
+        else y7t_amf_vec<float>(m, k - n, [&](int b, int c) { return (float)dxy[2 * b + c]; }, sv + 3 * k);
+    }
+    __syncthreads();
+    const long long tot = (long long)n * m;
+    for (long long e = threadIdx.x; e < tot; e += blockDim.x) {
+        const int i = (int)(e / m), j = (int)(e - (long long)i * m);
+        out[e] = y7t_amf_cos_dist(sv + 3 * i, sv + 3 * (n + j));
+    }
 }
 
 // a step the library refuses on the device side: the pool's status word says why (Y7T_ERR_KIND), no row is returned
@@ -433,6 +480,15 @@ extern "C" int y7t_iou_cost_f64(const double* a, int n, const double* b, int m, 
 
 static int kind_ok(int kind) { return kind == Y7T_KF_XYAH || kind == Y7T_KF_XYWH || kind == Y7T_KF_NSA; }
 
+extern "C" int y7t_structure_distance_f64(const double* track_xy, int n, const double* det_xy, int m, double* out, y7t_stream stream) {
+    Y7T_ARG_CHECK(n >= 0 && m >= 0 && n + m <= 2048);      // (the vectors of both lists in one workgroup's LDS: 48 KiB)
+    if (n == 0 || m == 0) return 0;
+    Y7T_ARG_CHECK(track_xy && det_xy && out);
+    hipLaunchKernelGGL(k_structure_distance, dim3(1), dim3(256), (size_t)(n + m) * 3 * sizeof(double), S(stream), track_xy, n, det_xy, m, out);
+    Y7T_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int y7t_kf_initiate_f64(int kind, const double* z, double* mean, double* cov, int K, int flags, y7t_stream stream) {
     Y7T_ARG_CHECK(K >= 0);
     if (!kind_ok(kind)) { y7t_set_error("kalman kind %d is not implemented on the device (default/botsort/strongsort are)", kind); return Y7T_E_ARG; }
@@ -574,6 +630,11 @@ static bool any_cbiou_state() {
     for (const auto& kv : g_state_kind) if (kv.second == Y7T_C_BIOU) return true;
     return false;
 }
+static bool any_uavmot_state() {
+    std::lock_guard<std::mutex> l(g_kind_mu);
+    for (const auto& kv : g_state_kind) if (kv.second == Y7T_UAVMOT) return true;
+    return false;
+}
 static int state_kind(const void* state) {
     std::lock_guard<std::mutex> l(g_kind_mu);
     auto it = g_state_kind.find(state);
@@ -599,7 +660,7 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
                                 y7t_stream stream) {
     Y7T_ARG_CHECK(state && id_counter && cap_t > 0 && cap_d > 0);
     Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT ||
-                  tracker_kind == Y7T_C_BIOU);
+                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT);
     if (tracker_kind == Y7T_C_BIOU) kalman_kind = Y7T_KF_XYAH;      // (C-BIoU has no Kalman filter: the kind is ignored)
     if (tracker_kind == Y7T_DEEPSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("DeepSORT gates on xyah measurements (deepsort.py:59): kalman_format default / strongsort only");
@@ -650,10 +711,15 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     const int nt = step_threads(threads);
     Y7T_ARG_CHECK(nt > 0);
     static std::atomic<unsigned long long> attr_done{0}, attr_done_m{0};
-    if (nt <= 512 && any_cbiou_state()) {      // (a C-BIoU pool may be among the states: the kernel that branches on each pool's kind)
+    const bool uav = any_uavmot_state();
+    if (nt <= 512 && (uav || any_cbiou_state())) {      // (a C-BIoU or UAVMOT pool may be among the states: the kernel that branches on each pool's kind)
         static std::atomic<unsigned long long> attr_done_x{0};
         if (int e = ensure_lds_once(k_tracker_step_mixed, kFastBytes + Y7T_LDS_HDR, attr_done_x)) return e;
         hipLaunchKernelGGL(k_tracker_step_mixed, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
+    } else if (uav) {                                   // (more than 512 threads: the called copies of the UAVMOT step and of every other kind's)
+        static std::atomic<unsigned long long> attr_done_w{0};
+        if (int e = ensure_lds_once(k_tracker_step_mixed_wide, kFastBytes + Y7T_LDS_HDR, attr_done_w)) return e;
+        hipLaunchKernelGGL(k_tracker_step_mixed_wide, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     } else if (nt <= 512) {
         if (int e = ensure_lds_once(k_tracker_step<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)) return e;
         hipLaunchKernelGGL(k_tracker_step<512>, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
@@ -678,6 +744,21 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
     }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
     const unsigned fb = step_fast_bytes(n);
+    if (state_kind(state) == Y7T_UAVMOT) {
+        static std::atomic<unsigned long long> uv_done{0}, uv_done_s{0}, uv_done_m{0};
+        if (nt <= 256) {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot<256>, kFastBytes + Y7T_LDS_HDR, uv_done_s)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        } else if (nt <= 512) {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot<512>, kFastBytes + Y7T_LDS_HDR, uv_done_m)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        } else {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot<1024>, kFastBytes + Y7T_LDS_HDR, uv_done)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
+        }
+        Y7T_LAUNCH_CHECK();
+        return 0;
+    }
     if (state_kind(state) == Y7T_C_BIOU) {
         static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
         if (nt <= 256) {
@@ -726,6 +807,24 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
     unsigned arena = 0, fast = kFastBytes;
     if (ab && ab + 64 * 1024 + Y7T_LDS_HDR <= kLdsMax) { arena = (unsigned)((ab + 15) & ~(size_t)15); fast = (kLdsMax - Y7T_LDS_HDR - arena) & ~15u; if (fast > kFastBytes) fast = kFastBytes; }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
+    if (state_kind(state) == Y7T_UAVMOT) {
+        static std::atomic<unsigned long long> uv_done{0}, uv_done_s{0}, uv_done_m{0};
+        if (nt <= 256) {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<256>, kLdsMax, uv_done_s)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        } else if (nt <= 512) {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<512>, kLdsMax, uv_done_m)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<512>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        } else {
+            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<1024>, kLdsMax, uv_done)) return e;
+            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<1024>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
+                               n_frames, fast, arena);
+        }
+        Y7T_LAUNCH_CHECK();
+        return 0;
+    }
     if (state_kind(state) == Y7T_C_BIOU) {
         static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
         if (nt <= 256) {
@@ -781,10 +880,11 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     Y7T_ARG_CHECK(cap_tracks <= 64 * Y7T_EMBED_WORKERS);      // (k_embed_dist: a workgroup owns at most 64 live slots)
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
-    if (state_kind(state) == Y7T_C_BIOU) {      // no Kalman state, no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+    if (state_kind(state) == Y7T_C_BIOU || state_kind(state) == Y7T_UAVMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
         hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
         Y7T_LAUNCH_CHECK();
-        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as C-BIoU -- it steps through y7t_tracker_step");
+        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step",
+                      state_kind(state) == Y7T_C_BIOU ? "C-BIoU" : "UAVMOT");
         return Y7T_E_STATE;
     }
     static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};

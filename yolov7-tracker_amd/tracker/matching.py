@@ -1,6 +1,9 @@
 """Association ops with the reference's signatures (/root/reference/tracker/matching.py:30-82),
 computed on the MI355X by liby7t.so: `iou_distance` (IoU with the +1 pixel convention of
-cython_bbox.bbox_overlaps) and `linear_assignment` (lap.lapjv(extend_cost=True, cost_limit=t))."""
+cython_bbox.bbox_overlaps) and `linear_assignment` (lap.lapjv(extend_cost=True, cost_limit=t)); UAVMOT's structure cost
+(matching.py:284-388) with `structure_similarity_distance` on the device."""
+import math
+
 import numpy as np
 import torch
 
@@ -93,3 +96,90 @@ def linear_assignment(cost_matrix, thresh):
         _, x, y = lapjv_host(cost_matrix, thresh)
     matches = np.asarray([[ix, mx] for ix, mx in enumerate(x) if mx >= 0])
     return matches, np.where(x < 0)[0], np.where(y < 0)[0]
+
+
+# ---- UAVMOT's structure cost (matching.py:284-388) ----
+def local_relation_fuse_motion(cost_matrix, tracks, detections, only_position=False, lambda_=0.98):
+    """matching.py:284-311: lambda_ * cost + (1 - lambda_) * structure_similarity_distance(tracks, detections)"""
+    if cost_matrix.size == 0:
+        return cost_matrix
+    structure_distance = structure_similarity_distance(tracks, detections)
+    return lambda_ * cost_matrix + (1 - lambda_) * structure_distance
+
+
+def structure_similarity_distance(tracks, detections):
+    """matching.py:312-319 -> (N, M) float64 max(0, cosine distance) of the structure vectors of the tracks (mean[0:2]) and of the detections
+    (get_xy()), computed on the device (y7t_structure_distance_f64).  The detections' centres must be float32 (AMF_STrack detections: get_xy() of
+    a float32 tlwh) and the tracks' float64 (means after multi_predict), the dtypes of the reference's one call site (uavmot.py:189)."""
+    txy, dxy = _track_xy(tracks), _det_xy(detections)
+    if txy.dtype != np.float64 or dxy.dtype != np.float32:
+        raise ValueError("structure_similarity_distance: float64 track means and float32 detection centres (got %s / %s)" % (txy.dtype, dxy.dtype))
+    n, m = txy.shape[0], dxy.shape[0]
+    if n == 0 or m == 0:
+        return np.zeros((n, m), dtype=np.float64)
+    _lib.require_gpu()
+    a, b = _dev(txy, np.float64), _dev(dxy, np.float64)
+    out = torch.empty((n, m), dtype=torch.float64, device="cuda")
+    _lib.check(_lib.load().y7t_structure_distance_f64(_lib.ptr(a), n, _lib.ptr(b), m, _lib.ptr(out), _lib.stream_ptr()))
+    return out.cpu().numpy()
+
+
+def angle(v1, v2):
+    """matching.py:321-342: the included angle of two offsets, from their atan2 angles truncated to whole degrees"""
+    angle1 = int(math.atan2(v1[1], v1[0]) * 180 / math.pi)
+    angle2 = int(math.atan2(v2[1], v2[0]) * 180 / math.pi)
+    if angle1 * angle2 >= 0:
+        return abs(angle1 - angle2)
+    included_angle = abs(angle1) + abs(angle2)
+    if included_angle > 180:
+        included_angle = 360 - included_angle
+    return included_angle
+
+
+def structure_representation(tracks, mode='trcak'):
+    """matching.py:344-388 -> (N, 3) float64 [max, min, included angle] of every element's neighbours at 0 < distance < 400 (tracks: mean[0:2];
+    mode == "detection": get_xy())"""
+    xy = _det_xy(tracks) if mode == "detection" else _track_xy(tracks)
+    return _structure_vectors(xy)
+
+
+def _track_xy(tracks):
+    return np.asarray([t.mean[0:2] for t in tracks]).reshape(-1, 2)
+
+
+def _det_xy(detections):
+    return np.asarray([d.get_xy() for d in detections]).reshape(-1, 2)
+
+
+def _structure_vectors(xy, dtype=None):
+    """structure_representation of a (N, 2) array of centres, in the reference's arithmetic (its dtype; np.linalg.norm for the distances)"""
+    xy = np.asarray(xy, dtype=dtype)
+    rows = []
+    for a in range(xy.shape[0]):
+        length, index = [], []
+        for b in range(xy.shape[0]):
+            pp = [np.linalg.norm(np.array(xy[a, 0] - xy[b, 0])), np.linalg.norm(np.array(xy[a, 1] - xy[b, 1]))]
+            lgt = np.linalg.norm(pp)
+            if 0 < lgt < 400:
+                length.append(lgt)
+                index.append(b)
+        if not length:
+            rows.append([0.0001, 0.0001, 0.0001])
+            continue
+        mx, mn = max(length), min(length)
+        if mx == mn:
+            rows.append([mx, mn, 0.0001])
+            continue
+        v1 = xy[index[length.index(mx)]] - xy[a]
+        v2 = xy[index[length.index(mn)]] - xy[a]
+        rows.append([mx, mn, angle(v1, v2)])
+    return np.asarray(rows)
+
+
+def _structure_cosine(track_vec, det_vec):
+    """np.maximum(0, cdist(T, D, "cosine")) restated elementwise (unfused left-to-right sums, the cosine clipped to [-1, 1]) -- what the device computes"""
+    u, v = np.asarray(track_vec, np.float64)[:, None, :], np.asarray(det_vec, np.float64)[None, :, :]
+    dot = u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1] + u[..., 2] * v[..., 2]
+    uu = u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1] + u[..., 2] * u[..., 2]
+    vv = v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1] + v[..., 2] * v[..., 2]
+    return np.maximum(0.0, 1.0 - np.clip(dot / (np.sqrt(uu) * np.sqrt(vv)), -1.0, 1.0))

@@ -22,11 +22,12 @@ from .bytetrack import ByteTrack
 from .botsort import BoTSORT
 from .deepsort import DeepSORT
 from .c_biou_tracker import C_BIoUTracker
+from .uavmot import UAVMOT
 from .timer import Timer
 from ..detector import attempt_load, check_img_size, non_max_suppression, scale_coords
 
 TRACKER_DICT = {'sort': BaseTracker, 'bytetrack': ByteTrack, 'botsort': BoTSORT, 'deepsort': DeepSORT,
-                'c_biou': C_BIoUTracker}   # track.py:56-65; the other trackers are out of scope
+                'c_biou': C_BIoUTracker, 'uavmot': UAVMOT}   # track.py:56-65; the other trackers are out of scope
 
 timer = Timer()
 seq_fps = []
