@@ -1,6 +1,6 @@
 // y7t_track_cbiou.h -- the C-BIoU tracker's frame step (reference tracker/c_biou_tracker.py: C_BIoUSTrack :17-209, C_BIoUTracker.update
 // :218-353) as ONE workgroup program over the same struct-of-arrays pool as the Kalman trackers (y7t_track_step.h).  Portable text like the
-// rest of the tracker programs; y7t_tracker_step (end of y7t_track_step.h) runs it for pools of kind Y7T_C_BIOU.
+// rest of the tracker programs; y7t_step_one (end of y7t_track_step.h) runs it for pools of kind Y7T_C_BIOU.
 //
 // C-BIoU has no motion model: a track is its last detection boxes and two "buffered" boxes, and the three associations compare buffered boxes
 // by IoU.  Per slot (the slot's `cov` storage, 64 doubles that only a Kalman filter uses, so the state blob's layout is the same for every tracker):

@@ -1201,9 +1201,7 @@ Y7T_FN void y7t_amf_first(const Y7TExec& ex, const Y7TTrk& s, const int* pool, i
 }
 
 // One frame.  dets: n x 6 float32 rows [x1, y1, x2, y2, conf, cls] (n < 0: update_without_detection)
-// The body is inlined where it is named: y7t_tracker_step (below) is the CALLED copy every launch of more than 256 threads shares; the <= 256-thread kernels
-// (csrc/y7t_tracker.hip) inline it, because a called function does not inherit its kernel's __launch_bounds__ -- compiled for the default 1024 threads a lane has 128
-// registers, and what the frame step keeps live around its Kalman updates spills to scratch memory; under __launch_bounds__(256) a lane may use 512 (round 6)
+// The body is inlined where it is named; which copy a launch runs -- inlined into its kernel or one of the two called ones -- is y7t_step_one's business (end of this file)
 // UAV: UAVMOT (uavmot.py:109-256) -- ByteTrack with a 0.7 first solve, the AMF re-solve behind it (y7t_amf_first) and the second association's unmatched
 // indices applied to the pool (below); its own instances, so that the ByteTrack ones keep their code and register allocation
 template <bool UAV>
@@ -1395,14 +1393,6 @@ Y7T_FN void y7t_tracker_step_body_t(const Y7TExec& ex, void* blob, const float* 
     Y7T_PROF(h, 11);
 }
 
-Y7T_FN void y7t_tracker_step_body(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap,
-                                  int* out_count, const double* gmc_warp) {
-    y7t_tracker_step_body_t<false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
-}
-Y7T_FN void y7t_tracker_step_uavmot_body(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count) {
-    y7t_tracker_step_body_t<true>(ex, blob, dets, n, out_rows, out_cap, out_count, nullptr);
-}
-
 // initialise a state blob (single thread is enough; called once)
 Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg, unsigned long long idc) {
     Y7TTrkHdr* h = (Y7TTrkHdr*)blob;
@@ -1424,28 +1414,65 @@ Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg
 
 #include "y7t_track_cbiou.h"
 
-// the frame step of any pool the plain step serves: C-BIoU pools run their own program (y7t_track_cbiou.h), every other kind y7t_tracker_step_body
-Y7T_FN void y7t_tracker_step_any(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
-    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_C_BIOU) y7t_tracker_step_cbiou_body(ex, blob, dets, n, out_rows, out_cap, out_count);
-    else y7t_tracker_step_body(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+// ---------------------------------------------------------------------------------------------
+// The step-program selector: the one place that knows which body serves which tracker kind, and which called copy stands behind a launch that does not inline.
+//   PLAIN        SORT / ByteTrack / BoT-SORT, and the predict-only step (n < 0) of a DeepSORT pool: y7t_tracker_step_body_t<false>
+//   CBIOU        y7t_tracker_step_cbiou_body (y7t_track_cbiou.h)
+//   UAVMOT       y7t_tracker_step_body_t<true>
+//   PLAIN_CBIOU  PLAIN or CBIOU, whichever the pool's header names: what the called copy of the plain step serves
+//   ANY          UAVMOT or PLAIN_CBIOU by the pool's header (a batch launch cannot see its pools' kinds; the host build steps every kind through it)
+// Why the programs are separate instances and not one body that branches: a branch inside the ByteTrack instances moved their register allocation (SGPR spills
+// 261 -> 492 in the 256-thread single-frame kernel when C-BIoU was tried that way), so every kind has kernels of its own and only the batch launches branch.
+// Why INLINED: a called function does not inherit its kernel's __launch_bounds__ -- compiled for the default 1024 threads a lane has 128 registers, and what the frame
+// step keeps live around its Kalman updates spills to scratch memory; inlined under __launch_bounds__(256) a lane may use 512 (round 6).  So the <= 512-thread
+// instances inline the step under their own register budget and the 1024-thread ones share a called copy, of which there are two:
+//   y7t_step_called         PLAIN_CBIOU (a 1024-thread batch reaches C-BIoU through it; C-BIoU's own kernels inline under every bound).  It does NOT hold the UAVMOT
+//                           body, so that it keeps its code
+//   y7t_step_called_uavmot  UAVMOT
+// (if constexpr throughout: an instance must hold no trace of the bodies it does not run -- inlined into a dead branch and removed later, they still move the live code)
+// A seventh kind with a body of its own: an enumerator, a case below (and a branch of ANY), and a line per entry point of csrc/y7t_tracker.hip.
+// ---------------------------------------------------------------------------------------------
+enum { Y7T_PROG_PLAIN = 0, Y7T_PROG_CBIOU, Y7T_PROG_UAVMOT, Y7T_PROG_PLAIN_CBIOU, Y7T_PROG_ANY };
+
+// is the step inlined into the instance of program PROG compiled for MAXT threads?  (C-BIoU has no called copy of its own)
+constexpr bool y7t_step_inlined(int prog, int maxt) { return prog == Y7T_PROG_CBIOU || maxt <= 512; }
+
+// the C-BIoU program under the bodies' common argument list (it has no camera-motion compensation).  This hop is load-bearing: how many inlined calls lie between a
+// function and a body decides ties of the instruction scheduler inside the body (odd or even, as far as was tried), and before this selector existed the C-BIoU body sat
+// one call nearer than the Kalman bodies wherever both were inlined.  With the hop every instance compiles to the instruction stream that was measured
+// (scripts/isa_identity.py, profiles/tracker_step_refactor_isa.txt); without it the six C-BIoU kernels and y7t_step_called differ in the order of a few stores
+Y7T_FN void y7t_step_cbiou(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double*) {
+    y7t_tracker_step_cbiou_body(ex, blob, dets, n, out_rows, out_cap, out_count);
 }
 
-// the called copy of the UAVMOT step (its launches of more than 512 threads)
-Y7T_NOINL void y7t_tracker_step_uavmot(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count) {
-    y7t_tracker_step_uavmot_body(ex, blob, dets, n, out_rows, out_cap, out_count);
+Y7T_NOINL void y7t_step_called(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp);
+Y7T_NOINL void y7t_step_called_uavmot(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count);
+
+template <int PROG, bool INLINED>
+Y7T_FN void y7t_step_one(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+    static_assert(INLINED || PROG != Y7T_PROG_CBIOU, "there is no called copy of the C-BIoU step alone");
+    if constexpr (PROG == Y7T_PROG_ANY) {
+        if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_UAVMOT) y7t_step_one<Y7T_PROG_UAVMOT, INLINED>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+        else y7t_step_one<Y7T_PROG_PLAIN_CBIOU, INLINED>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    } else if constexpr (!INLINED) {
+        if constexpr (PROG == Y7T_PROG_UAVMOT) y7t_step_called_uavmot(ex, blob, dets, n, out_rows, out_cap, out_count);
+        else y7t_step_called(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);      // (PLAIN too: there is one called copy for both)
+    } else if constexpr (PROG == Y7T_PROG_PLAIN_CBIOU) {
+        if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_C_BIOU) y7t_step_one<Y7T_PROG_CBIOU, true>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+        else y7t_step_one<Y7T_PROG_PLAIN, true>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    } else if constexpr (PROG == Y7T_PROG_PLAIN) y7t_tracker_step_body_t<false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    else if constexpr (PROG == Y7T_PROG_CBIOU) y7t_step_cbiou(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    else y7t_tracker_step_body_t<true>(ex, blob, dets, n, out_rows, out_cap, out_count, nullptr);
 }
 
-Y7T_NOINL void y7t_tracker_step(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
-#if !Y7T_DEVICE
-    // (the host build steps every kind through here; on the device UAVMOT pools launch kernels of their own -- csrc/y7t_tracker.hip -- so that this called
-    //  copy, which the kernels of more than 512 threads share, keeps its code)
-    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_UAVMOT) { y7t_tracker_step_uavmot(ex, blob, dets, n, out_rows, out_cap, out_count); return; }
-#endif
-    y7t_tracker_step_any(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+Y7T_NOINL void y7t_step_called(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+    y7t_step_one<Y7T_PROG_PLAIN_CBIOU, true>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+}
+Y7T_NOINL void y7t_step_called_uavmot(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count) {
+    y7t_step_one<Y7T_PROG_UAVMOT, true>(ex, blob, dets, n, out_rows, out_cap, out_count, nullptr);
 }
 
-// every kind the plain step serves, UAVMOT included and inlined (k_tracker_step_mixed: a batch that may hold a C-BIoU or UAVMOT pool)
-Y7T_FN void y7t_tracker_step_all(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
-    if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_UAVMOT) y7t_tracker_step_uavmot_body(ex, blob, dets, n, out_rows, out_cap, out_count);
-    else y7t_tracker_step_any(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+// one frame of a pool of any kind, the step inlined: the name under which the host build (tests/_hostsim) steps every kind.  The device kernels name their program
+Y7T_FN void y7t_tracker_step(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
+    y7t_step_one<Y7T_PROG_ANY, true>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
 }

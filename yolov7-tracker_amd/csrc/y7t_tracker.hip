@@ -131,6 +131,14 @@ __device__ __forceinline__ Y7TExec make_exec(unsigned fast_bytes) {
     ex.arena = nullptr; ex.arena_bytes = 0;
     return ex;
 }
+// its sibling for the programs that use no LDS: this thread of that many
+__device__ __forceinline__ Y7TExec make_exec_flat(int tid, int nt) {
+    Y7TExec ex;
+    ex.tid = tid; ex.nt = nt;
+    ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0;
+    ex.arena = nullptr; ex.arena_bytes = 0;
+    return ex;
+}
 
 __global__ void k_lapjv(const double* __restrict__ cost, int nr, int nc, double limit, int* x, int* y, double* opt, void* ws_g,
                         unsigned fast_bytes, int jv_extended) {
@@ -162,105 +170,43 @@ __global__ void k_lapjv(const double* __restrict__ cost, int nr, int nc, double 
 }
 
 __global__ void k_tracker_init(void* blob, Y7TTrkCfg cfg, unsigned long long idc) {
-    Y7TExec ex;
-    ex.tid = threadIdx.x; ex.nt = blockDim.x; ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0; ex.arena = nullptr; ex.arena_bytes = 0;
+    const Y7TExec ex = make_exec_flat(threadIdx.x, blockDim.x);
     y7t_tracker_init(ex, blob, cfg, idc);
 }
 
-template <int MAXT>      // (the thread bound of the launch: see k_tracker_step1)
-__global__ void __launch_bounds__(MAXT) k_tracker_step(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
-                                                        int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
-    const int b = blockIdx.x;
+// ---- the frame-step kernels: three launch forms x the step programs of y7t_track_step.h (y7t_step_one: which body a program runs and why the instances are separate).
+// MAXT is the launch's thread bound and the instance's register budget: the host runs a launch of nt threads on the smallest MAXT >= nt (launch_step).
+// Only the instances the entry points name exist.  `warp` is the ByteTrack family's camera-motion matrix; the C-BIoU and UAVMOT programs ignore it. ----
+template <int PROG, int MAXT>      // one frame of one pool
+__global__ void __launch_bounds__(MAXT) k_tracker_step(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, unsigned fast_bytes,
+                                                        const double* warp) {
     const Y7TExec ex = make_exec(fast_bytes);
-    if (MAXT <= 512) y7t_tracker_step_body(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
-    else y7t_tracker_step(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
-}
-
-// MAXT: the launch's thread bound.  Compiled for 1024 threads a lane has 128 registers and the frame step spills what it keeps live around its Kalman updates to SCRATCH
-// memory; the <= 256-thread launches (scenes of up to ~384 objects: step_threads) run an instance compiled for 256 threads with the step's body inlined (round 6)
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_tracker_step1(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count,
-                                                         unsigned fast_bytes, const double* warp) {
-    const Y7TExec ex = make_exec(fast_bytes);
-    if (MAXT <= 512) y7t_tracker_step_body(ex, state, dets, n, out_rows, out_cap, out_count, warp);      // inlined: under this kernel's register budget
-    else y7t_tracker_step(ex, state, dets, n, out_rows, out_cap, out_count, warp);
+    y7t_step_one<PROG, y7t_step_inlined(PROG, MAXT)>(ex, state, dets, n, out_rows, out_cap, out_count, warp);
 }
 
 // n_frames consecutive frames of ONE tracker in one launch: the same frame step, frame after frame, by the same workgroup (the state stays hot in
 // this CU's caches and nothing is launched between frames).  For pipelines that have a whole batch's detections before the tracker runs.
-template <int MAXT>
+template <int PROG, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_tracker_step_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count, int out_cap,
                                                                int n_frames, unsigned fast_bytes, unsigned arena_bytes, const double* const* warps) {
     Y7TExec ex = make_exec(fast_bytes);
     if (arena_bytes) { ex.arena = y7t_smem + Y7T_LDS_HDR + fast_bytes; ex.arena_bytes = arena_bytes; }      // the index lists live in LDS for the whole launch
     y7t_arena_load(ex, state);
     for (int f = 0; f < n_frames; ++f) {
-        if (MAXT <= 512) y7t_tracker_step_body(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f], warps ? warps[f] : nullptr);
-        else y7t_tracker_step(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f], warps ? warps[f] : nullptr);
+        y7t_step_one<PROG, y7t_step_inlined(PROG, MAXT)>(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f], warps ? warps[f] : nullptr);
         y7t_sync(ex);
     }
     y7t_arena_store(ex, state);
 }
 
-// ---- C-BIoU (y7t_track_cbiou.h): kernels of their own, so that the instances above keep their register allocation.  The host picks them for a pool
-// initialised as Y7T_C_BIOU (note_state_kind); a batch launch cannot see its pools' kinds, so it takes k_tracker_step_mixed -- which branches on every
-// workgroup's pool -- while a C-BIoU pool exists in the process ----
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_tracker_step_cbiou(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, unsigned fast_bytes) {
-    const Y7TExec ex = make_exec(fast_bytes);
-    y7t_tracker_step_cbiou_body(ex, state, dets, n, out_rows, out_cap, out_count);
-}
-
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_tracker_step_cbiou_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count,
-                                                                     int out_cap, int n_frames, unsigned fast_bytes, unsigned arena_bytes) {
-    Y7TExec ex = make_exec(fast_bytes);
-    if (arena_bytes) { ex.arena = y7t_smem + Y7T_LDS_HDR + fast_bytes; ex.arena_bytes = arena_bytes; }
-    y7t_arena_load(ex, state);
-    for (int f = 0; f < n_frames; ++f) {
-        y7t_tracker_step_cbiou_body(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
-        y7t_sync(ex);
-    }
-    y7t_arena_store(ex, state);
-}
-
-__global__ void __launch_bounds__(512) k_tracker_step_mixed(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
-                                                            int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
+// one workgroup per pool of a batch.  PLAIN: while no C-BIoU / UAVMOT pool exists in the process (its 1024-thread instance runs the called copy, which serves C-BIoU
+// too); ANY: a launch cannot see its pools' kinds, so this one branches on every workgroup's pool
+template <int PROG, int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_batch(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
+                                                              int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
     const int b = blockIdx.x;
     const Y7TExec ex = make_exec(fast_bytes);
-    y7t_tracker_step_all(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
-}
-
-// ---- UAVMOT (y7t_track_step.h: y7t_tracker_step_body_t<true>): kernels of their own like C-BIoU's; the <= 512-thread instances inline the step under their
-// own register budget, the 1024-thread ones call y7t_tracker_step_uavmot.  A batch of more than 512 threads that may hold a UAVMOT pool takes
-// k_tracker_step_mixed_wide, which calls either copy ----
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_tracker_step_uavmot(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, unsigned fast_bytes) {
-    const Y7TExec ex = make_exec(fast_bytes);
-    if (MAXT <= 512) y7t_tracker_step_uavmot_body(ex, state, dets, n, out_rows, out_cap, out_count);
-    else y7t_tracker_step_uavmot(ex, state, dets, n, out_rows, out_cap, out_count);
-}
-
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_tracker_step_uavmot_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count,
-                                                                      int out_cap, int n_frames, unsigned fast_bytes, unsigned arena_bytes) {
-    Y7TExec ex = make_exec(fast_bytes);
-    if (arena_bytes) { ex.arena = y7t_smem + Y7T_LDS_HDR + fast_bytes; ex.arena_bytes = arena_bytes; }
-    y7t_arena_load(ex, state);
-    for (int f = 0; f < n_frames; ++f) {
-        if (MAXT <= 512) y7t_tracker_step_uavmot_body(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
-        else y7t_tracker_step_uavmot(ex, state, dets[f], n_dets[f], out_rows[f], out_cap, out_count[f]);
-        y7t_sync(ex);
-    }
-    y7t_arena_store(ex, state);
-}
-
-__global__ void __launch_bounds__(1024) k_tracker_step_mixed_wide(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
-                                                                  int* out_count, int out_cap, unsigned fast_bytes, const double* const* warps) {
-    const int b = blockIdx.x;
-    const Y7TExec ex = make_exec(fast_bytes);
-    if (((const Y7TTrkHdr*)states[b])->cfg.tracker == Y7T_UAVMOT) y7t_tracker_step_uavmot(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b);
-    else y7t_tracker_step(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
+    y7t_step_one<PROG, y7t_step_inlined(PROG, MAXT)>(ex, states[b], dets[b], n_dets[b], out_rows[b], out_cap, out_count + b, warps ? warps[b] : nullptr);
 }
 
 // matching.structure_similarity_distance: one workgroup, the n + m structure vectors in LDS (a lane per element), then the n x m cosine distances
@@ -288,16 +234,14 @@ __global__ void k_tracker_refuse(void* state, int* out_count) {
 
 // ---- DeepSORT (y7t_track_deepsort.h) ----
 __global__ void k_feat_init(void* fblob, int cap_t, int cap_d, int dim, int budget) {
-    Y7TExec ex;
-    ex.tid = threadIdx.x; ex.nt = blockDim.x; ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0; ex.arena = nullptr; ex.arena_bytes = 0;
+    const Y7TExec ex = make_exec_flat(threadIdx.x, blockDim.x);
     y7t_feat_init(ex, fblob, cap_t, cap_d, dim, budget);
 }
 
 // detection features of the frame -> normalised rows (a wave per detection)
 __global__ void __launch_bounds__(256) k_ds_normalize(void* fblob, const float* __restrict__ det_feats, int n) {
     const Y7TFeat f = y7t_feat_bind(fblob);
-    Y7TExec ex;
-    ex.tid = blockIdx.x * blockDim.x + threadIdx.x; ex.nt = gridDim.x * blockDim.x; ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0; ex.arena = nullptr; ex.arena_bytes = 0;
+    const Y7TExec ex = make_exec_flat(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     if (n > f.h->cap_d) n = f.h->cap_d;      // (the step reports Y7T_ERR_CAP_D; nothing is written past the state)
     y7t_feat_normalize_dets(ex, f, det_feats, n);
 }
@@ -343,8 +287,7 @@ __global__ void __launch_bounds__(256) k_embed_dist(void* blob, void* fblob, int
         const int nf = f.nfeat[slot];
         if (dim & 31) {      // feature dimensions that are not a multiple of the k chunk: the plain form, one workgroup per slot
             if (blockIdx.y == 0) {
-                Y7TExec ex;
-                ex.tid = threadIdx.x; ex.nt = blockDim.x; ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0; ex.arena = nullptr; ex.arena_bytes = 0;
+                const Y7TExec ex = make_exec_flat(threadIdx.x, blockDim.x);
                 y7t_embed_slot(ex, f, slot, n, s.tsu[slot]);
             }
             continue;
@@ -406,8 +349,7 @@ __global__ void __launch_bounds__(256) k_embed_dist(void* blob, void* fblob, int
 // the appearance vectors the step queued -> the rings (a wave per vector, across the grid)
 __global__ void __launch_bounds__(256) k_ds_store(void* fblob, const float* __restrict__ det_feats) {
     const Y7TFeat f = y7t_feat_bind(fblob);
-    Y7TExec ex;
-    ex.tid = blockIdx.x * blockDim.x + threadIdx.x; ex.nt = gridDim.x * blockDim.x; ex.rv = nullptr; ex.ri = nullptr; ex.fast = nullptr; ex.fast_bytes = 0; ex.arena = nullptr; ex.arena_bytes = 0;
+    const Y7TExec ex = make_exec_flat(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
     y7t_feat_store_pending(ex, f, det_feats);
 }
 
@@ -454,17 +396,40 @@ static int ensure_lds(K kernel, unsigned bytes) {
     Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
 }
-// the attribute is per device and the callers may be threads of several trackers: done-bits per device, set after the call succeeded
-template <class K>
-static int ensure_lds_once(K kernel, unsigned bytes, std::atomic<unsigned long long>& done) {
+// the attribute is per device and the callers may be threads of several trackers: done-bits per device, set after the call succeeded.  The done-word is a
+// static of this function, which is instantiated once per kernel instance: no launch can pair a kernel with another kernel's word
+template <auto KERNEL>
+static int ensure_lds_once(unsigned bytes) {
+    static std::atomic<unsigned long long> done{0};
     int dev = 0;
     Y7T_HIP_CHECK(hipGetDevice(&dev));
     const unsigned long long bit = 1ull << (dev & 63);
     if (done.load(std::memory_order_acquire) & bit) return 0;
-    if (int e = ensure_lds(kernel, bytes)) return e;
+    if (int e = ensure_lds(KERNEL, bytes)) return e;
     done.fetch_or(bit, std::memory_order_release);
     return 0;
 }
+
+// A frame-step launch: FAMILY::k<MAXT> is a kernel template's instance for MAXT threads, FAMILY::kMinT the smallest one that exists.  This is the one place that maps a
+// launch's thread count to an instance: the smallest MAXT >= nt of 256 / 512 / 1024 (register budgets: y7t_step_one, y7t_track_step.h; thread counts: step_threads).
+// lds_max: what the instance is allowed once per device; lds: what this launch asks for
+template <auto KERNEL, class... A>
+static int launch_instance(int blocks, int nt, unsigned lds_max, unsigned lds, y7t_stream stream, A... args) {
+    if (int e = ensure_lds_once<KERNEL>(lds_max)) return e;
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(nt), lds, S(stream), args...);
+    Y7T_LAUNCH_CHECK();
+    return 0;
+}
+template <class FAMILY, class... A>
+static int launch_step(int blocks, int nt, unsigned lds_max, unsigned lds, y7t_stream stream, A... args) {
+    if constexpr (FAMILY::kMinT <= 256) if (nt <= 256) return launch_instance<FAMILY::template k<256>>(blocks, nt, lds_max, lds, stream, args...);
+    if (nt <= 512) return launch_instance<FAMILY::template k<512>>(blocks, nt, lds_max, lds, stream, args...);
+    return launch_instance<FAMILY::template k<1024>>(blocks, nt, lds_max, lds, stream, args...);
+}
+template <int PROG> struct StepSingle { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step<PROG, MAXT>; };
+template <int PROG> struct StepFrames { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_frames<PROG, MAXT>; };
+template <int PROG> struct StepBatch { static const int kMinT = 512; template <int MAXT> static constexpr auto k = &k_tracker_step_batch<PROG, MAXT>; };      // (launches of <= 256 threads take the 512 instance)
+struct StepDeepsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_deepsort<MAXT>; };
 
 extern "C" int y7t_iou_cost_f64(const double* a, int n, const double* b, int m, double* cost, y7t_stream stream) {
     Y7T_ARG_CHECK(n >= 0 && m >= 0);
@@ -566,8 +531,7 @@ extern "C" int y7t_lapjv_f64(const double* cost, int n, int m, double cost_limit
         return 0;
     }
     Y7T_ARG_CHECK(cost && x && y && workspace);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (int e = ensure_lds_once(k_lapjv, kFastBytes + Y7T_LDS_HDR, attr_done)) return e;
+    if (int e = ensure_lds_once<&k_lapjv>(kFastBytes + Y7T_LDS_HDR)) return e;
     const int nn = n + m;
     const int threads = nn <= 128 ? 64 : (nn <= 512 ? 256 : 1024);
     static int jv = -1;
@@ -609,44 +573,40 @@ extern "C" int y7t_lapjv_f64_host(const double* cost_host, int n, int m, double 
     return 0;
 }
 
-// tracker kind of every initialised state blob (host side; the header itself lives in device memory): the plain frame step refuses a DeepSORT pool
-// with detections -- it would create / update tracks without the appearance-ring bookkeeping, and a reused slot would keep its previous
-// occupant's vectors.  Only the predict-only form (n < 0) is shared between the trackers.
-static std::mutex g_kind_mu;
-static std::unordered_map<const void*, int> g_state_kind;
-static std::unordered_map<const void*, size_t> g_state_arena;      // bytes of LDS the pool's index lists take (y7t_arena_bytes of its capacities)
-static void note_state_kind(const void* state, int kind, int cap_t = 0, int cap_d = 0) {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    g_state_kind[state] = kind;
-    g_state_arena[state] = cap_t > 0 ? y7t_arena_bytes(cap_t, cap_d) : 0;
+// what the host side knows of every initialised state blob (the header itself lives in device memory): its tracker kind and the bytes of LDS its index lists take
+// (y7t_arena_bytes of its capacities).  The plain frame step refuses a DeepSORT pool with detections -- it would create / update tracks without the appearance-ring
+// bookkeeping, and a reused slot would keep its previous occupant's vectors.  Only the predict-only form (n < 0) is shared between the trackers.
+struct PoolInfo { int kind; size_t arena_bytes; };
+static std::mutex g_pool_mu;
+static std::unordered_map<const void*, PoolInfo> g_pools;
+static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
+static void count_kind(int kind, int d) {
+    if (kind == Y7T_C_BIOU) g_n_cbiou += d;
+    else if (kind == Y7T_UAVMOT) g_n_uavmot += d;
 }
-static size_t state_arena_bytes(const void* state) {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    auto it = g_state_arena.find(state);
-    return it == g_state_arena.end() ? 0 : it->second;
+static void forget_pool(const void* state) {      // (g_pool_mu held; an address that was never noted changes nothing)
+    auto it = g_pools.find(state);
+    if (it == g_pools.end()) return;
+    count_kind(it->second.kind, -1);
+    g_pools.erase(it);
 }
-static bool any_cbiou_state() {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    for (const auto& kv : g_state_kind) if (kv.second == Y7T_C_BIOU) return true;
-    return false;
+static void note_pool(const void* state, int kind, int cap_t, int cap_d) {
+    std::lock_guard<std::mutex> l(g_pool_mu);
+    forget_pool(state);      // (a pool re-initialised at the same address, maybe with another kind)
+    g_pools[state] = PoolInfo{kind, y7t_arena_bytes(cap_t, cap_d)};
+    count_kind(kind, +1);
 }
-static bool any_uavmot_state() {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    for (const auto& kv : g_state_kind) if (kv.second == Y7T_UAVMOT) return true;
-    return false;
-}
-static int state_kind(const void* state) {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    auto it = g_state_kind.find(state);
-    return it == g_state_kind.end() ? -1 : it->second;
+static PoolInfo pool_info(const void* state) {
+    std::lock_guard<std::mutex> l(g_pool_mu);
+    auto it = g_pools.find(state);
+    return it == g_pools.end() ? PoolInfo{-1, 0} : it->second;
 }
 
 // the caller is about to free / reuse `state`: forget what the host side knows about it, so that a later blob at the same address is judged by its own
 // y7t_tracker_init (the registry only ever grew, and a stale DEEPSORT entry made the plain step refuse a valid pool)
 extern "C" int y7t_tracker_release(void* state) {
-    std::lock_guard<std::mutex> l(g_kind_mu);
-    g_state_kind.erase(state);
-    g_state_arena.erase(state);
+    std::lock_guard<std::mutex> l(g_pool_mu);
+    forget_pool(state);
     return 0;
 }
 
@@ -677,7 +637,7 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
     c.iou_thresh = iou_thresh;
     hipLaunchKernelGGL(k_tracker_init, dim3(1), dim3(256), 0, S(stream), state, c, (unsigned long long)(uintptr_t)id_counter);
     Y7T_LAUNCH_CHECK();
-    note_state_kind(state, tracker_kind, cap_t, cap_d);
+    note_pool(state, tracker_kind, cap_t, cap_d);
     return 0;
 }
 
@@ -686,7 +646,7 @@ static int step_threads(int threads, int n_hint = -1) {
     // chose ONE wave for ~100-object scenes from stand-alone timings (no cross-wave barriers in the LAP reductions); inside the pipeline, where the step
     // runs beside the detector's kernels, four waves hide the longer memory round trips: tracker chain 14.1 -> 12.1 ms per 32 frames on the same box
     // (bench.py --tracker_threads 0 / 256, profiles/r02_bench_variants.txt), and stand-alone they are no slower any more (179 vs 186 us).
-    // Round 6: the <= 512-thread launches run instances with the step's body inlined under their own register budget (no scratch spills: k_tracker_step1<MAXT>); 80 objects
+    // Round 6: the <= 512-thread launches run instances with the step's body inlined under their own register budget (no scratch spills: k_tracker_step<PROG, MAXT>); 80 objects
     // 169 -> 98 us with four waves (105 with eight), 500 objects 434 us with sixteen waves (the called copy, 128 registers a lane) -> 362 with four -> 261 with eight
     if (threads == 0) return (n_hint > 384) ? 512 : 256;
     if (threads != 64 && threads != 128 && threads != 256 && threads != 512 && threads != 1024) return -1;
@@ -710,25 +670,12 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     Y7T_ARG_CHECK(states && dets && n_dets && out_rows && out_count);
     const int nt = step_threads(threads);
     Y7T_ARG_CHECK(nt > 0);
-    static std::atomic<unsigned long long> attr_done{0}, attr_done_m{0};
-    const bool uav = any_uavmot_state();
-    if (nt <= 512 && (uav || any_cbiou_state())) {      // (a C-BIoU or UAVMOT pool may be among the states: the kernel that branches on each pool's kind)
-        static std::atomic<unsigned long long> attr_done_x{0};
-        if (int e = ensure_lds_once(k_tracker_step_mixed, kFastBytes + Y7T_LDS_HDR, attr_done_x)) return e;
-        hipLaunchKernelGGL(k_tracker_step_mixed, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
-    } else if (uav) {                                   // (more than 512 threads: the called copies of the UAVMOT step and of every other kind's)
-        static std::atomic<unsigned long long> attr_done_w{0};
-        if (int e = ensure_lds_once(k_tracker_step_mixed_wide, kFastBytes + Y7T_LDS_HDR, attr_done_w)) return e;
-        hipLaunchKernelGGL(k_tracker_step_mixed_wide, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
-    } else if (nt <= 512) {
-        if (int e = ensure_lds_once(k_tracker_step<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)) return e;
-        hipLaunchKernelGGL(k_tracker_step<512>, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
-    } else {
-        if (int e = ensure_lds_once(k_tracker_step<1024>, kFastBytes + Y7T_LDS_HDR, attr_done)) return e;
-        hipLaunchKernelGGL(k_tracker_step<1024>, dim3(batch), dim3(nt), kFastBytes + Y7T_LDS_HDR, S(stream), states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
-    }
-    Y7T_LAUNCH_CHECK();
-    return 0;
+    // a C-BIoU or UAVMOT pool may be among the states while one exists in the process: the kernel that branches on each pool's kind.  Above 512 threads only UAVMOT
+    // needs it (the called copy of the plain program serves C-BIoU)
+    const bool uav = g_n_uavmot.load() > 0, any = nt <= 512 ? (uav || g_n_cbiou.load() > 0) : uav;
+    const unsigned lds = kFastBytes + Y7T_LDS_HDR;
+    if (any) return launch_step<StepBatch<Y7T_PROG_ANY>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
+    return launch_step<StepBatch<Y7T_PROG_PLAIN>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
 }
 
 extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* out_rows, int out_cap, int* out_count, int threads,
@@ -737,55 +684,18 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
     Y7T_ARG_CHECK(n <= 0 || dets);
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
-    if (n >= 0 && state_kind(state) == Y7T_DEEPSORT) {
+    const int kind = pool_info(state).kind;
+    if (n >= 0 && kind == Y7T_DEEPSORT) {
         y7t_set_error("y7t_tracker_step: this pool was initialised as DeepSORT -- frames with detections go through y7t_tracker_step_deepsort "
                       "(appearance rings); only the predict-only step (n < 0) is shared");
         return Y7T_E_STATE;
     }
-    static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
-    const unsigned fb = step_fast_bytes(n);
-    if (state_kind(state) == Y7T_UAVMOT) {
-        static std::atomic<unsigned long long> uv_done{0}, uv_done_s{0}, uv_done_m{0};
-        if (nt <= 256) {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot<256>, kFastBytes + Y7T_LDS_HDR, uv_done_s)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        } else if (nt <= 512) {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot<512>, kFastBytes + Y7T_LDS_HDR, uv_done_m)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        } else {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot<1024>, kFastBytes + Y7T_LDS_HDR, uv_done)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        }
-        Y7T_LAUNCH_CHECK();
-        return 0;
+    const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
+    switch (kind) {
+    case Y7T_UAVMOT: return launch_step<StepSingle<Y7T_PROG_UAVMOT>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
+    case Y7T_C_BIOU: return launch_step<StepSingle<Y7T_PROG_CBIOU>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
+    default: return launch_step<StepSingle<Y7T_PROG_PLAIN>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
     }
-    if (state_kind(state) == Y7T_C_BIOU) {
-        static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
-        if (nt <= 256) {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou<256>, kFastBytes + Y7T_LDS_HDR, cb_done_s)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        } else if (nt <= 512) {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou<512>, kFastBytes + Y7T_LDS_HDR, cb_done_m)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        } else {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou<1024>, kFastBytes + Y7T_LDS_HDR, cb_done)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb);
-        }
-        Y7T_LAUNCH_CHECK();
-        return 0;
-    }
-    if (nt <= 256) {
-        if (int e = ensure_lds_once(k_tracker_step1<256>, kFastBytes + Y7T_LDS_HDR, attr_done_s)) return e;
-        hipLaunchKernelGGL(k_tracker_step1<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
-    } else if (nt <= 512) {
-        if (int e = ensure_lds_once(k_tracker_step1<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)) return e;
-        hipLaunchKernelGGL(k_tracker_step1<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
-    } else {
-        if (int e = ensure_lds_once(k_tracker_step1<1024>, kFastBytes + Y7T_LDS_HDR, attr_done)) return e;
-        hipLaunchKernelGGL(k_tracker_step1<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
-    }
-    Y7T_LAUNCH_CHECK();
-    return 0;
 }
 
 extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, const int* n_dets, double* const* out_rows, int* const* out_count, int out_cap,
@@ -795,7 +705,8 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
     Y7T_ARG_CHECK(dets && n_dets && out_rows && out_count);
     const int nt = step_threads(threads);
     Y7T_ARG_CHECK(nt > 0);
-    if (state_kind(state) == Y7T_DEEPSORT) {
+    const PoolInfo pool = pool_info(state);
+    if (pool.kind == Y7T_DEEPSORT) {
         y7t_set_error("y7t_tracker_step_frames: a DeepSORT pool steps through y7t_tracker_step_deepsort (appearance rings)");
         return Y7T_E_STATE;
     }
@@ -803,61 +714,15 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
     // CU's 160 KiB hold them beside at least 64 KiB of fast scratch (the default capacities, 1024 tracks x 1024 detections: 68 KiB of lists, 91 KiB of scratch)
     static const unsigned kLdsMax = 160 * 1024;
     static const int use_arena = y7t_switch("Y7T_TRACKER_ARENA", 1);      // (thread-safe static initialisation)
-    const size_t ab = use_arena ? state_arena_bytes(state) : 0;
+    const size_t ab = use_arena ? pool.arena_bytes : 0;
     unsigned arena = 0, fast = kFastBytes;
     if (ab && ab + 64 * 1024 + Y7T_LDS_HDR <= kLdsMax) { arena = (unsigned)((ab + 15) & ~(size_t)15); fast = (kLdsMax - Y7T_LDS_HDR - arena) & ~15u; if (fast > kFastBytes) fast = kFastBytes; }
-    static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
-    if (state_kind(state) == Y7T_UAVMOT) {
-        static std::atomic<unsigned long long> uv_done{0}, uv_done_s{0}, uv_done_m{0};
-        if (nt <= 256) {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<256>, kLdsMax, uv_done_s)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        } else if (nt <= 512) {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<512>, kLdsMax, uv_done_m)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<512>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        } else {
-            if (int e = ensure_lds_once(k_tracker_step_uavmot_frames<1024>, kLdsMax, uv_done)) return e;
-            hipLaunchKernelGGL(k_tracker_step_uavmot_frames<1024>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        }
-        Y7T_LAUNCH_CHECK();
-        return 0;
+    const unsigned lds = Y7T_LDS_HDR + fast + arena;
+    switch (pool.kind) {
+    case Y7T_UAVMOT: return launch_step<StepFrames<Y7T_PROG_UAVMOT>>(1, nt, kLdsMax, lds, stream, state, dets, n_dets, out_rows, out_count, out_cap, n_frames, fast, arena, gmc_warps);
+    case Y7T_C_BIOU: return launch_step<StepFrames<Y7T_PROG_CBIOU>>(1, nt, kLdsMax, lds, stream, state, dets, n_dets, out_rows, out_count, out_cap, n_frames, fast, arena, gmc_warps);
+    default: return launch_step<StepFrames<Y7T_PROG_PLAIN>>(1, nt, kLdsMax, lds, stream, state, dets, n_dets, out_rows, out_count, out_cap, n_frames, fast, arena, gmc_warps);
     }
-    if (state_kind(state) == Y7T_C_BIOU) {
-        static std::atomic<unsigned long long> cb_done{0}, cb_done_s{0}, cb_done_m{0};
-        if (nt <= 256) {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<256>, kLdsMax, cb_done_s)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        } else if (nt <= 512) {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<512>, kLdsMax, cb_done_m)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<512>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        } else {
-            if (int e = ensure_lds_once(k_tracker_step_cbiou_frames<1024>, kLdsMax, cb_done)) return e;
-            hipLaunchKernelGGL(k_tracker_step_cbiou_frames<1024>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap,
-                               n_frames, fast, arena);
-        }
-        Y7T_LAUNCH_CHECK();
-        return 0;
-    }
-    if (nt <= 256) {
-        if (int e = ensure_lds_once(k_tracker_step_frames<256>, kLdsMax, attr_done_s)) return e;
-        hipLaunchKernelGGL(k_tracker_step_frames<256>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap, n_frames,
-                           fast, arena, gmc_warps);
-    } else if (nt <= 512) {
-        if (int e = ensure_lds_once(k_tracker_step_frames<512>, kLdsMax, attr_done_m)) return e;
-        hipLaunchKernelGGL(k_tracker_step_frames<512>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap, n_frames,
-                           fast, arena, gmc_warps);
-    } else {
-        if (int e = ensure_lds_once(k_tracker_step_frames<1024>, kLdsMax, attr_done)) return e;
-        hipLaunchKernelGGL(k_tracker_step_frames<1024>, dim3(1), dim3(nt), Y7T_LDS_HDR + fast + arena, S(stream), state, dets, n_dets, out_rows, out_count, out_cap, n_frames,
-                           fast, arena, gmc_warps);
-    }
-    Y7T_LAUNCH_CHECK();
-    return 0;
 }
 
 extern "C" size_t y7t_deepsort_feature_bytes(int cap_t, int cap_d, int feat_dim, int budget) {
@@ -880,17 +745,13 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     Y7T_ARG_CHECK(cap_tracks <= 64 * Y7T_EMBED_WORKERS);      // (k_embed_dist: a workgroup owns at most 64 live slots)
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
-    if (state_kind(state) == Y7T_C_BIOU || state_kind(state) == Y7T_UAVMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+    const int kind = pool_info(state).kind;
+    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
         hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
         Y7T_LAUNCH_CHECK();
-        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step",
-                      state_kind(state) == Y7T_C_BIOU ? "C-BIoU" : "UAVMOT");
+        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : "UAVMOT");
         return Y7T_E_STATE;
     }
-    static std::atomic<unsigned long long> attr_done{0}, attr_done_s{0}, attr_done_m{0};
-    if (int e = nt <= 256 ? ensure_lds_once(k_tracker_step_deepsort<256>, kFastBytes + Y7T_LDS_HDR, attr_done_s)
-              : nt <= 512 ? ensure_lds_once(k_tracker_step_deepsort<512>, kFastBytes + Y7T_LDS_HDR, attr_done_m)
-                          : ensure_lds_once(k_tracker_step_deepsort<1024>, kFastBytes + Y7T_LDS_HDR, attr_done)) return e;
     if (n > 0) {
         hipLaunchKernelGGL(k_ds_normalize, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats, n);      // a wave per detection
         Y7T_LAUNCH_CHECK();
@@ -898,10 +759,7 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
         Y7T_LAUNCH_CHECK();
     }
     const unsigned fb = step_fast_bytes(n);
-    if (nt <= 256) hipLaunchKernelGGL(k_tracker_step_deepsort<256>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb);
-    else if (nt <= 512) hipLaunchKernelGGL(k_tracker_step_deepsort<512>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb);
-    else hipLaunchKernelGGL(k_tracker_step_deepsort<1024>, dim3(1), dim3(nt), fb + Y7T_LDS_HDR, S(stream), state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb);
-    Y7T_LAUNCH_CHECK();
+    if (int e = launch_step<StepDeepsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb)) return e;
     if (n > 0) {
         hipLaunchKernelGGL(k_ds_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);
         Y7T_LAUNCH_CHECK();
