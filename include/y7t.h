@@ -31,7 +31,7 @@ enum { Y7T_OK = 0, Y7T_E_ARG = -1, Y7T_E_HIP = -2, Y7T_E_CAPACITY = -3, Y7T_E_ST
 enum { Y7T_KALMAN_DEFAULT = 0, Y7T_KALMAN_NAIVE = 1, Y7T_KALMAN_BOTSORT = 2, Y7T_KALMAN_STRONGSORT = 3 };
 /* tracker kinds == TRACKER_DICT keys implemented on the device, tracker/track.py:56-65 */
 enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4,
-       Y7T_TRACKER_UAVMOT = 5 };
+       Y7T_TRACKER_UAVMOT = 5, Y7T_TRACKER_STRONGSORT = 6 };
 
 const char* y7t_last_error(void);
 int y7t_version(void);
@@ -173,6 +173,34 @@ size_t y7t_deepsort_feature_bytes(int cap_tracks, int cap_dets, int feat_dim, in
 int y7t_deepsort_init(void* feat_state, size_t bytes, int cap_tracks, int cap_dets, int feat_dim, int budget, y7t_stream stream);
 int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_tracks, const float* dets, int n, const float* det_feats, double* out_rows,
                               int out_cap, int* out_count, int threads, y7t_stream stream);
+
+/* StrongSORT (tracker/strongsort.py:91-250, tracker kind Y7T_TRACKER_STRONGSORT; Kalman kinds default / strongsort -- tracker/track.py:70-71 sets
+ * strongsort, the NSA filter): the first and the unconfirmed association solve the fused cost gamma * IoU distance + (1 - gamma) * appearance distance
+ * at 0.7, the appearance distance being matching.embedding_distance(..., 'euclidean') (tracker/matching.py:84-103: np.maximum(0, scipy cdist) of
+ * features[-1] in float64); between them an IoU association at 0.5 whose unmatched indices mark strack_pool[idx] lost, as in the reference.  The
+ * pool blob keeps its layout and size.  Next to it the tracker owns a FEATURE STATE of its own (y7t_strongsort_feature_bytes, y7t_strongsort_init):
+ * per slot ONE float32 vector of feat_dim (STrack.features with use_avg_of_feature=True, basetrack.py:324-332: the raw vector of the track's first
+ * detection, then smooth = 0.9 * smooth + (1 - 0.9) * f / |f|, smooth /= |smooth|, all float32), the frame's float64 appearance matrix
+ * (cap_tracks x cap_dets), the frame's list of pending vector stores, and a header whose status word sits at byte 20 as in DeepSORT's
+ * (bit 2: the feature state is smaller than the pool it is stepped with; bit 16: more queued vectors than detections).  gamma = opts.gamma.
+ * y7t_tracker_step_strongsort = StrongSORT.update for one frame, n known on the host as for DeepSORT:
+ *   det_feats   n x feat_dim float32, row j = what StrongSORT.get_feature (strongsort.py:66-89 -> OSNet x0.25 on 256 x 128 crops) returns for
+ *               detection row j, NOT normalised (rows with conf <= conf_thresh are never read)
+ *   gmc_warp    the frame's 2x3 camera-motion matrix (what GMC(method='ecc').apply returns, out of scope; 6 doubles in DEVICE memory) or NULL for no
+ *               compensation; multi_gmc is applied to strack_pool BEFORE the Kalman prediction and not to the unconfirmed tracks (strongsort.py:138-145)
+ *   launches (three, on `stream`): the Euclidean distances of every slot of the tracked / lost lists to every detection above the threshold (a grid
+ *   over list entries x 64-detection tiles; each pair's sum is the sequential float64 chain of cdist); ONE workgroup for multi_gmc, multi_predict, the
+ *   three associations and the list bookkeeping; a wave per queued vector for the moving averages of the updated tracks and the raw copies of the new
+ *   ones (re_activate keeps a track's vector).  update_without_detection: y7t_tracker_step(state, NULL, -1, ...) as for every tracker.
+ * (For this kind that call runs StrongSORT's own program without a feature state: its tracked and lost lists may share a track, which strack_pool holds once.)
+ * Misuse is refused with Y7T_E_STATE and status bit 8 in the pool: y7t_tracker_step with detections and y7t_tracker_step_frames on a StrongSORT pool
+ * (y7t_tracker_step_batch: status bit 8 and no rows for that pool of the batch, whatever its n_dets; the launch cannot see its pools' kinds on the host,
+ * so it returns 0 as for a DeepSORT pool), y7t_tracker_step_deepsort on a StrongSORT pool, y7t_tracker_step_strongsort on a pool of another kind.  Frames depend on each
+ * other through the smoothed vectors, so there is no multi-frame or batch form: a host loop of the three launches is the form. */
+size_t y7t_strongsort_feature_bytes(int cap_tracks, int cap_dets, int feat_dim);
+int y7t_strongsort_init(void* feat_state, size_t bytes, int cap_tracks, int cap_dets, int feat_dim, double gamma, y7t_stream stream);
+int y7t_tracker_step_strongsort(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
+                                int* out_count, int threads, const double* gmc_warp, y7t_stream stream);
 
 /* byte offsets of the arrays inside a state blob, for host-side views (tracked_stracks, lost_stracks, ...).
  * names/offsets: see y7t_tracker_field_name(i); returns the number of fields. */

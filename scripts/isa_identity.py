@@ -8,7 +8,8 @@ experiment is added to a translation unit or its launch layer is rewritten: the 
         --table FILE       write the comparison, one line per function, to FILE
 
 Compiles each file at <git-rev> (its csrc/ and include/ extracted to a temporary directory) and in the working tree to gfx950 assembly (hipcc -S --cuda-device-only with
-the file's flags of yolov7-tracker_amd/build.py) and compares function by function -- kernels and the device functions they call: label numbers and the names of the
+the file's flags of yolov7-tracker_amd/build.py) and compares function by function -- kernels and the device functions they call: label numbers (basic blocks, relaxed
+long branches) and the names of the
 file's own functions are normalised (a renamed function, or one whose template or argument list changed, has another mangled name), everything else must match.  For
 kernels the resource numbers of the code object's metadata are compared as well (.vgpr_count .agpr_count .sgpr_count .private_segment_fixed_size .vgpr_spill_count
 .sgpr_spill_count .group_segment_fixed_size .max_flat_workgroup_size); a device function has the first four of them (its "Function info" block).  A function whose
@@ -84,7 +85,8 @@ def functions(path):
             name, j = m.group(1), i + 1
             while j < len(t) and not t[j].startswith(".Lfunc_end"):
                 j += 1
-            body = [re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].rstrip()) for l in t[i + 1:j]]
+            # (label numbers count the file's functions / long branches in front of this one: .LBB<function>_<block>, .Lpost_getpc<n> of a relaxed branch)
+            body = [re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].rstrip())) for l in t[i + 1:j]]
             body = [l for l in body if l.strip() and not l.strip().startswith((".loc", ".file", ".cfi", ".section", ".text"))]      # (.section / .text behind a kernel's descriptor: where the NEXT function goes)
             nums, k = {}, j
             while k < len(t) and not t[k].startswith("; Function info:") and ".amdhsa_kernel" not in t[k] and "@function" not in t[k]:

@@ -8,6 +8,7 @@
 #include "y7t_common.h"
 #include "y7t_track_step.h"
 #include "y7t_track_deepsort.h"
+#include "y7t_track_strongsort.h"
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
@@ -360,6 +361,109 @@ __global__ void __launch_bounds__(MAXT) k_tracker_step_deepsort(void* state, voi
     y7t_tracker_step_deepsort(ex, state, fblob, dets, n, det_feats, out_rows, out_cap, out_count);
 }
 
+// ---- StrongSORT (y7t_track_strongsort.h): three launches per frame -- k_ss_appearance, k_tracker_step_strongsort, k_ss_store ----
+__global__ void k_ss_init(void* fblob, int cap_t, int cap_d, int dim, double gamma) {
+    const Y7TExec ex = make_exec_flat(threadIdx.x, blockDim.x);
+    y7t_ss_init(ex, fblob, cap_t, cap_d, dim, gamma);
+}
+
+// matching.embedding_distance(tracks, detections, 'euclidean') for every slot of the tracked / lost lists (confirmed and unconfirmed alike: the unconfirmed association
+// reads the same matrix) against every detection row above det_thresh, tiled like k_embed_dist: a workgroup takes 32 list entries x 64 detections, 32-deep k chunks of
+// both operands in LDS, 2 x 4 pairs per thread, the next chunk's global loads issued before the current chunk's arithmetic.  Every pair's sum is the sequential float64
+// chain over k = 0 .. dim-1 of y7t_ss_dist (= scipy's cdist), so the distances -- and the assignments that follow them -- are bit-identical to the plain form; only the
+// order in which DIFFERENT pairs advance changes.  The grid is (workers, detection tiles): a worker walks the groups of 32 list entries whose number is its blockIdx.x
+// modulo the worker count (the lists' lengths are only known on the device).  The rows are the LISTS, not the state column: a lost track that aged out last frame is
+// Removed but still in the lost list for this frame's association (basetrack's sub_stracks runs before removed_stracks.extend), and its row takes part in the solve.
+// vec_ok: both operands are 16-byte aligned (float4 loads); otherwise, and for dimensions that are not a multiple of the k chunk, the plain lane-per-pair form.
+#define Y7T_SS_WORKERS 64
+__global__ void __launch_bounds__(256) k_ss_appearance(void* blob, void* fblob, const float* __restrict__ dets, const float* __restrict__ det_feats, int n, int vec_ok) {
+    const Y7TTrkHdr* h = (const Y7TTrkHdr*)blob;
+    const int cap_t = h->cfg.cap_t;
+    const Y7TTrk s = y7t_trk_bind(blob, cap_t, h->cfg.cap_d);
+    const Y7TSs f = y7t_ss_bind(fblob);
+    if (h->cfg.tracker != Y7T_STRONGSORT || f.h->cap_t < cap_t || f.h->cap_d < h->cfg.cap_d) return;      // (the step reports it; nothing is read or written past either state)
+    if (n > h->cfg.cap_d) n = h->cfg.cap_d;
+    const int j0 = blockIdx.y * 64;
+    if (j0 >= n) return;
+    const int dim = f.h->dim, ld = f.h->cap_d, tid = threadIdx.x;
+    const int nt0 = h->n_tracked < cap_t ? h->n_tracked : cap_t, nl0 = h->n_lost < cap_t ? h->n_lost : cap_t, n_live = nt0 + nl0;
+    const float det_t = (float)h->cfg.det_thresh;
+    __shared__ float sA[32][33], sB[64][33];
+    __shared__ int s_slot[32], s_use[64];
+    if (tid < 64) s_use[tid] = (j0 + tid < n && y7t_ss_row_used(dets, j0 + tid, det_t)) ? 1 : 0;
+    const int ty = tid >> 4, tx = tid & 15, lrow = tid >> 3, kq = (tid & 7) * 4;
+    for (int g = blockIdx.x; g * 32 < n_live; g += gridDim.x) {
+        __syncthreads();                                   // (the previous group's pairs have read s_slot)
+        if (tid < 32) {
+            const int r = g * 32 + tid;
+            int sl = r < n_live ? y7t_ss_live_slot(s, nt0, r) : -1;
+            if (sl < 0 || sl >= cap_t) sl = -1;
+            s_slot[tid] = sl;
+        }
+        __syncthreads();
+        if ((dim & 31) || !vec_ok) {                       // the plain form: the group's 32 x 64 pairs, a lane per pair
+            for (int e = tid; e < 32 * 64; e += 256) {
+                const int sl = s_slot[e >> 6], c = e & 63;
+                if (sl < 0 || !s_use[c]) continue;
+                f.app[(size_t)sl * ld + j0 + c] = y7t_ss_dist(f.vec + (size_t)sl * dim, det_feats + (size_t)(j0 + c) * dim, dim);
+            }
+            continue;
+        }
+        const int sla = s_slot[lrow];
+        const float* pa = sla >= 0 ? f.vec + (size_t)sla * dim + kq : nullptr;
+        const float* pb0 = s_use[lrow] ? det_feats + (size_t)(j0 + lrow) * dim + kq : nullptr;
+        const float* pb1 = s_use[32 + lrow] ? det_feats + (size_t)(j0 + 32 + lrow) * dim + kq : nullptr;
+        auto fetch = [&](int k0, float4& va, float4& vb0, float4& vb1) {
+            va = make_float4(0.f, 0.f, 0.f, 0.f); vb0 = va; vb1 = va;
+            if (pa) va = *(const float4*)(pa + k0);
+            if (pb0) vb0 = *(const float4*)(pb0 + k0);
+            if (pb1) vb1 = *(const float4*)(pb1 + k0);
+        };
+        double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+        float4 va, vb0, vb1;
+        fetch(0, va, vb0, vb1);
+        for (int k0 = 0; k0 < dim; k0 += 32) {
+            __syncthreads();
+            sA[lrow][kq] = va.x; sA[lrow][kq + 1] = va.y; sA[lrow][kq + 2] = va.z; sA[lrow][kq + 3] = va.w;
+            sB[lrow][kq] = vb0.x; sB[lrow][kq + 1] = vb0.y; sB[lrow][kq + 2] = vb0.z; sB[lrow][kq + 3] = vb0.w;
+            sB[32 + lrow][kq] = vb1.x; sB[32 + lrow][kq + 1] = vb1.y; sB[32 + lrow][kq + 2] = vb1.z; sB[32 + lrow][kq + 3] = vb1.w;
+            __syncthreads();
+            if (k0 + 32 < dim) fetch(k0 + 32, va, vb0, vb1);
+#pragma unroll 8
+            for (int k = 0; k < 32; ++k) {
+                const float a0 = sA[2 * ty][k], a1 = sA[2 * ty + 1][k];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float b = sB[tx + 16 * c][k];
+                    acc[0][c] = y7t_ss_sqstep(acc[0][c], a0, b);
+                    acc[1][c] = y7t_ss_sqstep(acc[1][c], a1, b);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int sl = s_slot[2 * ty + r];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (sl >= 0 && s_use[tx + 16 * c]) f.app[(size_t)sl * ld + j0 + tx + 16 * c] = y7t_ss_root(acc[r][c]);
+        }
+    }
+}
+
+// the appearance vectors the step queued -> the slots' vectors: the float32 moving average of STrack.update or the raw copy of a new track (a wave per vector, across the grid)
+__global__ void __launch_bounds__(256) k_ss_store(void* fblob, const float* __restrict__ det_feats) {
+    const Y7TSs f = y7t_ss_bind(fblob);
+    const Y7TExec ex = make_exec_flat(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    y7t_ss_store_pending(ex, f, det_feats);
+}
+
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_strongsort(void* state, void* fblob, const float* dets, int n, const float* det_feats, double* out_rows,
+                                                                   int out_cap, int* out_count, unsigned fast_bytes, const double* warp) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_tracker_step_strongsort(ex, state, fblob, dets, n, det_feats, out_rows, out_cap, out_count, warp);
+}
+
 __global__ void __launch_bounds__(64) k_kf_gmc(double* mean, double* cov, const double* __restrict__ warp, int N) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N) return;
@@ -430,6 +534,7 @@ template <int PROG> struct StepSingle { static const int kMinT = 256; template <
 template <int PROG> struct StepFrames { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_frames<PROG, MAXT>; };
 template <int PROG> struct StepBatch { static const int kMinT = 512; template <int MAXT> static constexpr auto k = &k_tracker_step_batch<PROG, MAXT>; };      // (launches of <= 256 threads take the 512 instance)
 struct StepDeepsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_deepsort<MAXT>; };
+struct StepStrongsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_strongsort<MAXT>; };
 
 extern "C" int y7t_iou_cost_f64(const double* a, int n, const double* b, int m, double* cost, y7t_stream stream) {
     Y7T_ARG_CHECK(n >= 0 && m >= 0);
@@ -576,13 +681,14 @@ extern "C" int y7t_lapjv_f64_host(const double* cost_host, int n, int m, double 
 // what the host side knows of every initialised state blob (the header itself lives in device memory): its tracker kind and the bytes of LDS its index lists take
 // (y7t_arena_bytes of its capacities).  The plain frame step refuses a DeepSORT pool with detections -- it would create / update tracks without the appearance-ring
 // bookkeeping, and a reused slot would keep its previous occupant's vectors.  Only the predict-only form (n < 0) is shared between the trackers.
-struct PoolInfo { int kind; size_t arena_bytes; };
+struct PoolInfo { int kind; size_t arena_bytes; int cap_t; };
 static std::mutex g_pool_mu;
 static std::unordered_map<const void*, PoolInfo> g_pools;
-static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
+static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0}, g_n_strongsort{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
 static void count_kind(int kind, int d) {
     if (kind == Y7T_C_BIOU) g_n_cbiou += d;
     else if (kind == Y7T_UAVMOT) g_n_uavmot += d;
+    else if (kind == Y7T_STRONGSORT) g_n_strongsort += d;
 }
 static void forget_pool(const void* state) {      // (g_pool_mu held; an address that was never noted changes nothing)
     auto it = g_pools.find(state);
@@ -593,13 +699,13 @@ static void forget_pool(const void* state) {      // (g_pool_mu held; an address
 static void note_pool(const void* state, int kind, int cap_t, int cap_d) {
     std::lock_guard<std::mutex> l(g_pool_mu);
     forget_pool(state);      // (a pool re-initialised at the same address, maybe with another kind)
-    g_pools[state] = PoolInfo{kind, y7t_arena_bytes(cap_t, cap_d)};
+    g_pools[state] = PoolInfo{kind, y7t_arena_bytes(cap_t, cap_d), cap_t};
     count_kind(kind, +1);
 }
 static PoolInfo pool_info(const void* state) {
     std::lock_guard<std::mutex> l(g_pool_mu);
     auto it = g_pools.find(state);
-    return it == g_pools.end() ? PoolInfo{-1, 0} : it->second;
+    return it == g_pools.end() ? PoolInfo{-1, 0, 0} : it->second;
 }
 
 // the caller is about to free / reuse `state`: forget what the host side knows about it, so that a later blob at the same address is judged by its own
@@ -620,10 +726,14 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
                                 y7t_stream stream) {
     Y7T_ARG_CHECK(state && id_counter && cap_t > 0 && cap_d > 0);
     Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT ||
-                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT);
+                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT || tracker_kind == Y7T_STRONGSORT);
     if (tracker_kind == Y7T_C_BIOU) kalman_kind = Y7T_KF_XYAH;      // (C-BIoU has no Kalman filter: the kind is ignored)
     if (tracker_kind == Y7T_DEEPSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("DeepSORT gates on xyah measurements (deepsort.py:59): kalman_format default / strongsort only");
+        return Y7T_E_ARG;
+    }
+    if (tracker_kind == Y7T_STRONGSORT && kalman_kind == Y7T_KF_XYWH) {
+        y7t_set_error("StrongSORT fuses the IoU of xyah means (strongsort.py:150, track.py:70-71): kalman_format default / strongsort only");
         return Y7T_E_ARG;
     }
     if (!kind_ok(kalman_kind)) { y7t_set_error("kalman kind %d is not implemented on the device", kalman_kind); return Y7T_E_ARG; }
@@ -662,6 +772,16 @@ extern "C" int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* war
     return 0;
 }
 
+// frames with detections of a StrongSORT pool belong to y7t_tracker_step_strongsort (the smoothed appearance vectors): the plain entry points refuse them like a
+// DeepSORT pool's, and say so in the pool's status word too
+static int refuse_strongsort(const char* who, void* state, int* out_count, y7t_stream stream) {
+    hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+    Y7T_LAUNCH_CHECK();
+    y7t_set_error("%s: this pool was initialised as StrongSORT -- frames with detections go through y7t_tracker_step_strongsort (appearance vectors); only the "
+                  "predict-only step (n < 0) is shared", who);
+    return Y7T_E_STATE;
+}
+
 extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
                                       int* out_count, int out_cap, int batch, int threads, const double* const* gmc_warps,
                                       y7t_stream stream) {
@@ -674,6 +794,8 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     // needs it (the called copy of the plain program serves C-BIoU)
     const bool uav = g_n_uavmot.load() > 0, any = nt <= 512 ? (uav || g_n_cbiou.load() > 0) : uav;
     const unsigned lds = kFastBytes + Y7T_LDS_HDR;
+    // ... and while a StrongSORT pool exists, the kernel that refuses such a pool (status bit 8; it steps through y7t_tracker_step_strongsort / y7t_tracker_step)
+    if (g_n_strongsort.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_SS>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     if (any) return launch_step<StepBatch<Y7T_PROG_ANY>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     return launch_step<StepBatch<Y7T_PROG_PLAIN>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
 }
@@ -690,8 +812,11 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
                       "(appearance rings); only the predict-only step (n < 0) is shared");
         return Y7T_E_STATE;
     }
+    if (n >= 0 && kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step", state, out_count, stream);
     const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
     switch (kind) {
+    // (predict-only: StrongSORT's own program without a feature state -- its lists may share a track, which its pool holds once, as joint_stracks does)
+    case Y7T_STRONGSORT: return launch_step<StepStrongsort>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, (void*)nullptr, (const float*)nullptr, -1, (const float*)nullptr, out_rows, out_cap, out_count, fb, (const double*)nullptr);
     case Y7T_UAVMOT: return launch_step<StepSingle<Y7T_PROG_UAVMOT>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
     case Y7T_C_BIOU: return launch_step<StepSingle<Y7T_PROG_CBIOU>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
     default: return launch_step<StepSingle<Y7T_PROG_PLAIN>>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, out_rows, out_cap, out_count, fb, gmc_warp);
@@ -710,6 +835,7 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
         y7t_set_error("y7t_tracker_step_frames: a DeepSORT pool steps through y7t_tracker_step_deepsort (appearance rings)");
         return Y7T_E_STATE;
     }
+    if (pool.kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step_frames", state, nullptr, stream);      // (the frames' counts are device arrays: none is written)
     // LDS of the launch: header | fast scratch (cost matrix, assignment work arrays) | the pool's index lists for the length of the launch (y7t_arena_*), when the
     // CU's 160 KiB hold them beside at least 64 KiB of fast scratch (the default capacities, 1024 tracks x 1024 detections: 68 KiB of lists, 91 KiB of scratch)
     static const unsigned kLdsMax = 160 * 1024;
@@ -746,10 +872,10 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const int kind = pool_info(state).kind;
-    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
         hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
         Y7T_LAUNCH_CHECK();
-        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : "UAVMOT");
+        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : "StrongSORT (y7t_tracker_step_strongsort)");
         return Y7T_E_STATE;
     }
     if (n > 0) {
@@ -762,6 +888,49 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     if (int e = launch_step<StepDeepsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb)) return e;
     if (n > 0) {
         hipLaunchKernelGGL(k_ds_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);
+        Y7T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" size_t y7t_strongsort_feature_bytes(int cap_t, int cap_d, int feat_dim) {
+    if (cap_t <= 0 || cap_d <= 0 || feat_dim <= 0) return 0;
+    return y7t_ss_layout(cap_t, cap_d, feat_dim).total;
+}
+
+extern "C" int y7t_strongsort_init(void* feat_state, size_t bytes, int cap_t, int cap_d, int feat_dim, double gamma, y7t_stream stream) {
+    Y7T_ARG_CHECK(feat_state && cap_t > 0 && cap_d > 0 && feat_dim > 0);
+    Y7T_ARG_CHECK(bytes >= y7t_ss_layout(cap_t, cap_d, feat_dim).total);
+    hipLaunchKernelGGL(k_ss_init, dim3(1), dim3(64), 0, S(stream), feat_state, cap_t, cap_d, feat_dim, gamma);
+    Y7T_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int y7t_tracker_step_strongsort(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
+                                           int* out_count, int threads, const double* gmc_warp, y7t_stream stream) {
+    Y7T_ARG_CHECK(state && feat_state && out_rows && out_count && out_cap >= 0 && n >= 0);
+    Y7T_ARG_CHECK(n == 0 || (dets && det_feats));
+    const int nt = step_threads(threads, n);
+    Y7T_ARG_CHECK(nt > 0);
+    const PoolInfo pool = pool_info(state);
+    if (pool.kind != Y7T_STRONGSORT) {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+        if (pool.kind >= 0) {
+            hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+            Y7T_LAUNCH_CHECK();
+        }
+        y7t_set_error("y7t_tracker_step_strongsort: this pool was not initialised as StrongSORT (tracker kind %d)", pool.kind);
+        return Y7T_E_STATE;
+    }
+    if (n > 0) {
+        const int groups = (pool.cap_t + 31) / 32;
+        const int vec_ok = (((uintptr_t)feat_state | (uintptr_t)det_feats) & 15) == 0;
+        hipLaunchKernelGGL(k_ss_appearance, dim3(groups < Y7T_SS_WORKERS ? groups : Y7T_SS_WORKERS, (n + 63) / 64), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n, vec_ok);
+        Y7T_LAUNCH_CHECK();
+    }
+    const unsigned fb = step_fast_bytes(n);
+    if (int e = launch_step<StepStrongsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, gmc_warp)) return e;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_ss_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most one per detection)
         Y7T_LAUNCH_CHECK();
     }
     return 0;

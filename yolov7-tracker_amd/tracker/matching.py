@@ -1,7 +1,7 @@
 """Association ops with the reference's signatures (/root/reference/tracker/matching.py:30-82),
 computed on the MI355X by liby7t.so: `iou_distance` (IoU with the +1 pixel convention of
 cython_bbox.bbox_overlaps) and `linear_assignment` (lap.lapjv(extend_cost=True, cost_limit=t)); UAVMOT's structure cost
-(matching.py:284-388) with `structure_similarity_distance` on the device."""
+(matching.py:284-388) with `structure_similarity_distance` on the device; `embedding_distance` (matching.py:84-103) on the track views' vectors."""
 import math
 
 import numpy as np
@@ -39,6 +39,36 @@ def iou_distance(atracks, btracks):
     if len(atlbrs) == 0 or len(btlbrs) == 0:
         return np.zeros((len(atlbrs), len(btlbrs)), dtype=np.float64)
     return _cost(atlbrs, btlbrs)
+
+
+def cal_cosine_distance(mat1, mat2):
+    """matching.py:165-178: the rows divided by their norms, then mat1 . mat2^T (in the arrays' own dtype)"""
+    mat1 = mat1 / np.linalg.norm(mat1, axis=1, keepdims=True)
+    mat2 = mat2 / np.linalg.norm(mat2, axis=1, keepdims=True)
+    return np.dot(mat1, mat2.T)
+
+
+def embedding_distance(tracks, detections, metric='cosine'):
+    """matching.py:84-103: the appearance distance of features[-1] of both sides, cast to float64 -> (N, M) float64.  'euclidean' (StrongSORT):
+    np.maximum(0.0, cdist) -- per pair one sequential float64 chain d = u[k] - v[k]; s += d * d over k, then sqrt, which is what scipy's cdist computes
+    and what the device step's k_ss_appearance restates; 'cosine': 1 - cal_cosine_distance.  Host arithmetic on the (host-side) vectors of the track
+    views, for code written against the reference's matching module; the fused device step does not go through it."""
+    cost_matrix = np.zeros((len(tracks), len(detections)), dtype=np.float64)
+    if cost_matrix.size == 0:
+        return cost_matrix
+    det_features = np.asarray([track.features[-1] for track in detections], dtype=np.float64)
+    track_features = np.asarray([track.features[-1] for track in tracks], dtype=np.float64)
+    if metric == 'euclidean':
+        s = np.zeros_like(cost_matrix)
+        for k in range(track_features.shape[1]):      # (scipy's chain, a k at a time for every pair: numpy fuses nothing)
+            d = track_features[:, k, None] - det_features[None, :, k]
+            s += d * d
+        cost_matrix = np.maximum(0.0, np.sqrt(s))
+    elif metric == 'cosine':
+        cost_matrix = 1. - cal_cosine_distance(track_features, det_features)
+    else:
+        raise NotImplementedError
+    return cost_matrix
 
 
 def buffered_iou_distance(atracks, btracks, level=1):

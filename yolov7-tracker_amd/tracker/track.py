@@ -23,11 +23,12 @@ from .botsort import BoTSORT
 from .deepsort import DeepSORT
 from .c_biou_tracker import C_BIoUTracker
 from .uavmot import UAVMOT
+from .strongsort import StrongSORT
 from .timer import Timer
 from ..detector import attempt_load, check_img_size, non_max_suppression, scale_coords
 
 TRACKER_DICT = {'sort': BaseTracker, 'bytetrack': ByteTrack, 'botsort': BoTSORT, 'deepsort': DeepSORT,
-                'c_biou': C_BIoUTracker, 'uavmot': UAVMOT}   # track.py:56-65; the other trackers are out of scope
+                'c_biou': C_BIoUTracker, 'uavmot': UAVMOT, 'strongsort': StrongSORT}   # track.py:56-65; deepmot (weights/DHN.pth) is out of scope
 
 timer = Timer()
 seq_fps = []
@@ -85,6 +86,8 @@ def main(opts, cfgs):
         raise NotImplementedError("tracker %r: only %s run on the device path" % (opts.tracker, sorted(TRACKER_DICT)))
     if opts.tracker == 'botsort':
         opts.kalman_format = 'botsort'      # track.py:68-69
+    elif opts.tracker == 'strongsort':
+        opts.kalman_format = 'strongsort'   # track.py:70-71
     img_size = opts.img_size[0] if isinstance(opts.img_size, (list, tuple)) else opts.img_size
     model = attempt_load(opts.model_path, cfg=opts.model_cfg, nc=opts.nc, img_size=img_size, max_batch=max(1, opts.batch))
     stride = int(model.stride.max())
