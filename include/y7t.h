@@ -31,7 +31,7 @@ enum { Y7T_OK = 0, Y7T_E_ARG = -1, Y7T_E_HIP = -2, Y7T_E_CAPACITY = -3, Y7T_E_ST
 enum { Y7T_KALMAN_DEFAULT = 0, Y7T_KALMAN_NAIVE = 1, Y7T_KALMAN_BOTSORT = 2, Y7T_KALMAN_STRONGSORT = 3 };
 /* tracker kinds == TRACKER_DICT keys implemented on the device, tracker/track.py:56-65 */
 enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4,
-       Y7T_TRACKER_UAVMOT = 5, Y7T_TRACKER_STRONGSORT = 6 };
+       Y7T_TRACKER_UAVMOT = 5, Y7T_TRACKER_STRONGSORT = 6, Y7T_TRACKER_DEEPMOT = 7 };
 
 const char* y7t_last_error(void);
 int y7t_version(void);
@@ -201,6 +201,32 @@ size_t y7t_strongsort_feature_bytes(int cap_tracks, int cap_dets, int feat_dim);
 int y7t_strongsort_init(void* feat_state, size_t bytes, int cap_tracks, int cap_dets, int feat_dim, double gamma, y7t_stream stream);
 int y7t_tracker_step_strongsort(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
                                 int* out_count, int threads, const double* gmc_warp, y7t_stream stream);
+
+/* DeepMOT (tracker/deepmot.py:143-324, tracker kind Y7T_TRACKER_DEEPMOT; the pool blob and the Kalman kinds of ByteTrack): ByteTrack whose first association
+ * solves 1 - DHN(D) at 0.9, D = matching.ecu_iou_distance(strack_pool, D_high, image shape) cast to float32 and DHN the Deep Hungarian Net (class Munkrs,
+ * deepmot.py:10-140): two stacked bidirectional 2-layer GRUs of hidden size 256 over the h x w matrix flattened row-major, then column-major, three linear layers
+ * and a sigmoid.  The port is the eval() network: the reference never calls .eval(), so its dropout between the GRU layers is live and its output random.
+ *
+ * The DHN OBJECT is caller-owned device memory of y7t_dhn_weight_bytes() + y7t_dhn_workspace_bytes(max_h, max_w) bytes at a 256-byte aligned address; several
+ * trackers may share one (their frames then run one after the other on one stream).  Supported sizes: any h, w >= 1 with h * w <= max_h * max_w <= 1048576; the
+ * workspace holds two T x 512 float32 layer outputs (T = max_h * max_w) and the input projections of one chunk of 2048 positions, so it grows by 4 KiB a position.
+ * y7t_dhn_init: `weights` = the y7t_dhn_num_weights() = 4093825 float32 values of the 38 tensors of Munkrs.state_dict() in its order, packed, in host or device
+ *   memory (INTEGRATION.md lists the offsets).  Synchronous.  y7t_dhn_release: the object's memory is about to be freed.
+ * y7t_dhn_forward_f32: out (h x w, device) = the network's sigmoid output for D (h x w float32, device).  fp32 throughout.  Synchronous: it returns Y7T_E_STATE if
+ *   a workgroup of the recurrence waited for a peer past its bound (the recurrence's workgroups exchange the hidden state every step; every wait is bounded).
+ * y7t_tracker_step_deepmot = DeepMOT.update for one frame (n >= 0 known on the host; img_h, img_w = ori_img.shape[:2]).  Synchronous.  Y7T_E_STATE with no rows if the
+ *   network gave up (pool status bit 64); pool status bit 32 if the frame's pool x high-detection matrix exceeds the object's max_h * max_w.
+ * y7t_tracker_step(state, NULL, -1, ...) is update_without_detection.  Misuse is refused with Y7T_E_STATE and status bit 8 in the pool: y7t_tracker_step with
+ * detections and y7t_tracker_step_frames on a DeepMOT pool, y7t_tracker_step_batch for such a pool (device-side: the call returns 0), y7t_tracker_step_deepsort /
+ * y7t_tracker_step_strongsort on a DeepMOT pool, y7t_tracker_step_deepmot on a pool of another kind. */
+size_t y7t_dhn_num_weights(void);
+size_t y7t_dhn_weight_bytes(void);
+size_t y7t_dhn_workspace_bytes(int max_h, int max_w);
+int y7t_dhn_init(void* dhn, size_t bytes, const float* weights, int max_h, int max_w, y7t_stream stream);
+int y7t_dhn_release(void* dhn);
+int y7t_dhn_forward_f32(void* dhn, const float* D, int h, int w, float* out, y7t_stream stream);
+int y7t_tracker_step_deepmot(void* state, void* dhn, const float* dets, int n, int img_h, int img_w, double* out_rows, int out_cap, int* out_count, int threads,
+                             y7t_stream stream);
 
 /* byte offsets of the arrays inside a state blob, for host-side views (tracked_stracks, lost_stracks, ...).
  * names/offsets: see y7t_tracker_field_name(i); returns the number of fields. */

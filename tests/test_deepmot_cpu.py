@@ -1,0 +1,217 @@
+"""DeepMOT without a GPU: the CPU build of its two workgroup programs (tests/_hostsim_deepmot, nt = 1) with the Deep Hungarian Net between them evaluated by the
+package's own fp32 torch module, against the reference's golden vectors (tests/golden/tracker_deepmot_*.npz, dhn_*.npz; tests/golden/make_golden_deepmot.py) and,
+where the reference sources exist, against the live reference; the seeded weights, the dhn_path loader, matching.ecu_iou_distance and the CLI surface."""
+import importlib.util
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _hostsim_deepmot as hdm
+from tests import util
+from tests.test_uavmot_cpu import id_lists
+from yolov7_tracker_amd import synth
+from yolov7_tracker_amd.tracker import deepmot as dm
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NAMES = ["default", "miss", "conf04", "empty", "gaps", "reject", "crowd"]
+DHN_NAMES = ["1x1", "1x7", "7x1", "3x5", "12x9", "33x20", "64x48"]
+COUNTS = ["first_matches", "first_rejected", "second_matches", "unconfirmed_removed", "reactivated", "quirk_frames"]
+
+
+def maker():
+    spec = importlib.util.spec_from_file_location("make_golden_deepmot", os.path.join(GOLDEN, "make_golden_deepmot.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    return mg
+
+
+_NETS = {}
+
+
+def torch_net(seed, scale):
+    """the package's torch module with the seeded weights as a numpy -> numpy callable (built once per weight set, never modified)"""
+    key = (int(seed), float(scale))
+    if key not in _NETS:
+        net = dm.TorchDHN(synth.make_dhn_weights(*key))
+        _NETS[key] = lambda D, _n=net: _n(torch.from_numpy(np.ascontiguousarray(D, np.float32))).numpy()
+    return _NETS[key]
+
+
+def load_golden(name):
+    g = np.load(os.path.join(GOLDEN, "tracker_deepmot_%s.npz" % name))
+
+    def split(counts, flat):
+        o = np.concatenate([[0], np.cumsum(counts)])
+        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
+    dets = maker().frames_from_golden(g)
+    frames = []
+    for f in range(len(dets)):
+        sel = g["frame"] == f
+        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
+    return dict(dets=dets, frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]), lost=split(g["lost_counts"], g["lost_ids"]), conf=float(g["conf_thresh"]),
+                kalman_format=str(g["kalman_format"]), img_shape=tuple(int(v) for v in g["img_shape"]), seed=int(g["weight_seed"]), scale=float(g["weight_scale"]),
+                counts={k: int(g["count_" + k]) for k in COUNTS}, E=float(g["E"]))
+
+
+def check_rows(rows, want, f):
+    ids, tlwh, cls, score = want["frames"][f]
+    assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
+    np.testing.assert_allclose(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL, err_msg="frame %d: tlwh" % f)
+    assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score), "frame %d" % f
+
+
+def replay(want, **kw):
+    trk = hdm.HostDeepMOT(torch_net(want["seed"], want["scale"]), want["img_shape"], conf_thresh=want["conf"], kalman_format=want["kalman_format"], **kw)
+    for f, d in enumerate(want["dets"]):
+        check_rows(trk.update(d), want, f)
+        assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
+    return trk
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_hostsim_deepmot_matches_reference_golden(name):
+    """ids, classes and scores exactly, tlwh at util's tolerance, the tracked and lost lists exactly on every frame"""
+    want = load_golden(name)
+    trk = replay(want)
+    assert trk.net_shapes and max(h * w for h, w in trk.net_shapes) <= 24 * 30
+    if name == "crowd":
+        assert max(trk.net_shapes, key=lambda s: s[0] * s[1]) == (23, 14)      # the non-square crowd
+
+
+def test_golden_set_holds_every_event():
+    """what the maker enforced when it recorded the set: each event occurs somewhere"""
+    total = {k: 0 for k in COUNTS}
+    for name in NAMES:
+        for k, v in load_golden(name)["counts"].items():
+            total[k] += v
+    assert all(v > 0 for v in total.values()), total
+    es = {float(np.load(os.path.join(GOLDEN, "dhn_%s.npz" % n))["E"]) for n in DHN_NAMES}
+    assert len(es) == 1 and 0.0 < es.pop() < 1e-5
+
+
+@pytest.mark.parametrize("name", DHN_NAMES)
+def test_torch_module_matches_reference_network(name):
+    """the package's torch module (which the host build's tests use as the network) against the reference module's recorded outputs: within 4 E of the float64
+    evaluation in float32, and to 1e-12 of it when evaluated in float64"""
+    g = np.load(os.path.join(GOLDEN, "dhn_%s.npz" % name))
+    w = synth.make_dhn_weights(int(g["seed"]), float(g["scale"]))
+    out = dm.TorchDHN(w)(torch.from_numpy(g["D"])).numpy()
+    assert out.shape == g["out64"].shape and out.dtype == np.float32
+    assert np.abs(out.astype(np.float64) - g["out64"]).max() <= 4 * float(g["E"])
+    out64 = dm.TorchDHN(w).double()(torch.from_numpy(g["D"]).double()).numpy()
+    assert np.abs(out64 - g["out64"]).max() <= 1e-12
+
+
+def test_seeded_weights_are_reproducible_and_shaped():
+    a, b = synth.make_dhn_weights(7, 3.0), synth.make_dhn_weights(7, 3.0)
+    shapes = synth.dhn_tensor_shapes()
+    assert list(a) == [n for n, _ in shapes] and len(shapes) == 38 and sum(int(np.prod(s)) for _, s in shapes) == 4093825
+    assert all(a[n].dtype == np.float32 and a[n].shape == s and np.array_equal(a[n], b[n]) for n, s in shapes)
+    assert not np.array_equal(a["lstm_row.weight_hh_l0"], synth.make_dhn_weights(8, 3.0)["lstm_row.weight_hh_l0"])
+    assert np.abs(a["lstm_col.weight_ih_l1"]).max() <= 3.0 / 16 and np.abs(a["hidden2tag_2.bias"]).max() <= 3.0 / 16 and np.abs(a["hidden2tag_3.weight"]).max() <= 3.0 / 8
+    # the names and shapes are torch's own for this architecture
+    sd = dm.TorchDHN(a).state_dict()
+    assert list(sd) == list(a) and all(tuple(sd[n].shape) == a[n].shape for n in a)
+
+
+def test_dhn_path_forms(tmp_path):
+    w = synth.make_dhn_weights(3, 2.0)
+    got = dm.load_dhn_weights("random:dhn:3:2.0")
+    assert all(np.array_equal(got[n], w[n]) for n in w)
+    assert np.array_equal(dm.load_dhn_weights("random:dhn")["hidden2tag_1.bias"], synth.make_dhn_weights(0, 1.0)["hidden2tag_1.bias"])
+    path = str(tmp_path / "DHN.pth")
+    torch.save({k: torch.from_numpy(v) for k, v in w.items()}, path)
+    got = dm.load_dhn_weights(path)
+    assert list(got) == list(w) and all(np.array_equal(got[n], w[n]) for n in w)
+    assert dm.pack_dhn_weights(got).shape == (4093825,)
+    bad = {k: torch.from_numpy(v) for k, v in w.items()}
+    bad["lstm_col.weight_ih_l0"] = torch.zeros(768, 256)
+    torch.save(bad, path)
+    with pytest.raises(ValueError):
+        dm.load_dhn_weights(path)
+    del bad["lstm_col.weight_ih_l0"]
+    torch.save(bad, path)
+    with pytest.raises(ValueError):
+        dm.load_dhn_weights(path)
+    with pytest.raises(ValueError):
+        dm.load_dhn_weights("random:osnet")
+
+
+def test_cli_accepts_deepmot():
+    from yolov7_tracker_amd.tracker import track
+    assert track.TRACKER_DICT["deepmot"] is dm.DeepMOT and len(track.TRACKER_DICT) == 8
+    opts = track.build_parser().parse_args(["--dataset", "synthetic", "--tracker", "deepmot", "--dhn_path", "random:dhn:7:4", "--model_path", "random:yolov7-w6", "--nc", "10",
+                                            "--synthetic_dets"])
+    assert opts.tracker == "deepmot" and opts.dhn_path == "random:dhn:7:4"
+
+
+def test_refusals_and_skipped_network():
+    """a pool of another kind is refused by both programs (status bit 8); the plain step refuses a DeepMOT pool's frames only on the device library's side (its
+    host-side registry), so here: the empty first frame and the frame without high detections skip the network; a network that gave up yields no rows (bit 64);
+    a matrix larger than the network's workspace is refused (bit 32)"""
+    want = load_golden("default")
+    net = torch_net(want["seed"], want["scale"])
+    other = hdm.HostDeepMOT(net, want["img_shape"], kind=1)
+    with pytest.raises(RuntimeError, match="status 8"):
+        other.update(want["dets"][0])
+    trk = hdm.HostDeepMOT(net, want["img_shape"])
+    trk.update(want["dets"][0])
+    assert trk.net_shapes == []                                   # frame 1: the pool is empty
+    trk.update(want["dets"][1])
+    assert len(trk.net_shapes) == 1
+    low = want["dets"][2].copy()
+    low[:, 4] = 0.1
+    trk.update(low)
+    assert len(trk.net_shapes) == 1                               # no high detections
+    trk.net_status = 1
+    with pytest.raises(RuntimeError, match="status 64"):
+        trk.update(want["dets"][3])
+    small = hdm.HostDeepMOT(net, want["img_shape"], net_cap=4)
+    small.update(want["dets"][0])
+    with pytest.raises(RuntimeError, match="status 32"):
+        small.update(want["dets"][1])
+
+
+# ---- against the live reference ----
+from oracle import ref_harness  # noqa: E402
+
+needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference sources not present")
+
+
+@needs_ref
+def test_port_ecu_iou_distance_equals_reference():
+    """the program's element (y7t_dm_ecu_iou) and the reference's matrix on float64 track boxes and float32 detection boxes: equal to the last bit but for exp's last ulp"""
+    rm = ref_harness.load_tracker().matching
+    rng = np.random.default_rng(71)
+
+    class T:
+        def __init__(self, tlwh):
+            self.tlwh = tlwh
+            self.tlbr = np.concatenate([tlwh[:2], tlwh[:2] + tlwh[2:]])
+    for n, m, shape in ((1, 1, (720, 1280)), (7, 5, (1080, 1920)), (24, 12, (1280, 1280))):
+        a = [T(np.concatenate([rng.uniform(0, 1000, 2), rng.uniform(8, 200, 2)])) for _ in range(n)]
+        b = [T(np.concatenate([rng.uniform(0, 1000, 2), rng.uniform(8, 200, 2)]).astype(np.float32)) for _ in range(m)]
+        want = rm.ecu_iou_distance(a, b, shape)
+        iou = rm.iou_distance(a, b)
+        got = np.array([[hdm.ecu_iou(t.tlwh, d.tlwh, iou[i, j], shape) for j, d in enumerate(b)] for i, t in enumerate(a)])
+        assert want.dtype == np.float64 and np.abs(got - want).max() <= 2.3e-16      # (one ulp of a value under 1: numpy's vector exp against libm's)
+        assert np.array_equal(got.astype(np.float32), want.astype(np.float32))
+    assert rm.ecu_iou_distance([], b, (720, 1280)).shape == (0, len(b))
+
+
+@needs_ref
+@pytest.mark.parametrize("seed", range(4))
+def test_hostsim_deepmot_matches_live_reference(seed):
+    """random small scenes (6..14 objects x 10 frames, misses, a frame without detections, conf_thresh and the Kalman kind varied) against the reference run live"""
+    mg = maker()
+    mod = mg.load_deepmot()
+    nobj, conf, kform = [6, 14, 10, 8][seed], [0.2, 0.3, 0.4, 0.25][seed], ["default", "botsort", "strongsort", "default"][seed]
+    dets = mg.make_scene(10, nobj, 700 + seed, {"miss": 0.15 * (seed % 3)}, 0, 6 if seed == 2 else 0)
+    ref = mg.run_reference(dets, mod, conf, kform, 7, 3.0)
+    want = dict(dets=dets, conf=conf, kalman_format=kform, img_shape=mg.IMG_SHAPE, seed=7, scale=3.0, tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref],
+                frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
+                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref])
+    replay(want)

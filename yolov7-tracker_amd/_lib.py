@@ -60,6 +60,13 @@ SIGNATURES = {
     "y7t_strongsort_feature_bytes": (c_size_t, [c_int, c_int, c_int]),
     "y7t_strongsort_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_void_p]),
     "y7t_tracker_step_strongsort": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "y7t_dhn_num_weights": (c_size_t, []),
+    "y7t_dhn_weight_bytes": (c_size_t, []),
+    "y7t_dhn_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "y7t_dhn_init": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p]),
+    "y7t_dhn_release": (c_int, [c_void_p]),
+    "y7t_dhn_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "y7t_tracker_step_deepmot": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "y7t_kf_multi_gmc_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "y7t_tracker_layout": (c_int, [c_int, c_int, c_void_p, c_int]),
     "y7t_tracker_field_name": (ctypes.c_char_p, [c_int]),

@@ -16,7 +16,7 @@
 #include "y7t_track_core.h"
 
 struct Y7TTrkCfg {
-    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT / Y7T_DEEPSORT / Y7T_C_BIOU / Y7T_UAVMOT / Y7T_STRONGSORT
+    int tracker;        // Y7T_SORT / Y7T_BYTETRACK / Y7T_BOTSORT / Y7T_DEEPSORT / Y7T_C_BIOU / Y7T_UAVMOT / Y7T_STRONGSORT / Y7T_DEEPMOT
     int kf;             // Kalman kind
     int cap_t, cap_d;   // capacities: live tracks (tracked+lost), detections per frame
     int max_time_lost;  // int(frame_rate / 30 * track_buffer)
@@ -1424,6 +1424,8 @@ Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg
 //   ANY_SS       ANY through the called copies, after refusing a StrongSORT pool (Y7T_ERR_KIND): what a batch launch runs while a StrongSORT pool exists in the
 //                process.  StrongSORT's own step (y7t_track_strongsort.h) takes a feature state and has its own kernel, like DeepSORT's; its predict-only step
 //                (n < 0) is that program's too, because its tracked and lost lists may share a track, which PLAIN's pool would hold twice
+//   ANY_DM       ANY_SS that also refuses the frames with detections of a DeepMOT pool: what a batch launch runs while a DeepMOT pool exists in the process.  DeepMOT's
+//                frame is two programs around the Deep Hungarian Net (y7t_track_deepmot.h); its predict-only step is PLAIN's
 // Why the programs are separate instances and not one body that branches: a branch inside the ByteTrack instances moved their register allocation (SGPR spills
 // 261 -> 492 in the 256-thread single-frame kernel when C-BIoU was tried that way), so every kind has kernels of its own and only the batch launches branch.
 // Why INLINED: a called function does not inherit its kernel's __launch_bounds__ -- compiled for the default 1024 threads a lane has 128 registers, and what the frame
@@ -1435,10 +1437,10 @@ Y7T_FN void y7t_tracker_init(const Y7TExec& ex, void* blob, const Y7TTrkCfg& cfg
 // (if constexpr throughout: an instance must hold no trace of the bodies it does not run -- inlined into a dead branch and removed later, they still move the live code)
 // A seventh kind with a body of its own: an enumerator, a case below (and a branch of ANY), and a line per entry point of csrc/y7t_tracker.hip.
 // ---------------------------------------------------------------------------------------------
-enum { Y7T_PROG_PLAIN = 0, Y7T_PROG_CBIOU, Y7T_PROG_UAVMOT, Y7T_PROG_PLAIN_CBIOU, Y7T_PROG_ANY, Y7T_PROG_ANY_SS };
+enum { Y7T_PROG_PLAIN = 0, Y7T_PROG_CBIOU, Y7T_PROG_UAVMOT, Y7T_PROG_PLAIN_CBIOU, Y7T_PROG_ANY, Y7T_PROG_ANY_SS, Y7T_PROG_ANY_DM };
 
 // is the step inlined into the instance of program PROG compiled for MAXT threads?  (C-BIoU has no called copy of its own)
-constexpr bool y7t_step_inlined(int prog, int maxt) { return prog == Y7T_PROG_CBIOU || (maxt <= 512 && prog != Y7T_PROG_ANY_SS); }
+constexpr bool y7t_step_inlined(int prog, int maxt) { return prog == Y7T_PROG_CBIOU || (maxt <= 512 && prog != Y7T_PROG_ANY_SS && prog != Y7T_PROG_ANY_DM); }
 
 // the C-BIoU program under the bodies' common argument list (it has no camera-motion compensation).  This hop is load-bearing: how many inlined calls lie between a
 // function and a body decides ties of the instruction scheduler inside the body (odd or even, as far as was tried), and before this selector existed the C-BIoU body sat
@@ -1454,7 +1456,11 @@ Y7T_NOINL void y7t_step_called_uavmot(const Y7TExec& ex, void* blob, const float
 template <int PROG, bool INLINED>
 Y7T_FN void y7t_step_one(const Y7TExec& ex, void* blob, const float* dets, int n, double* out_rows, int out_cap, int* out_count, const double* gmc_warp) {
     static_assert(INLINED || PROG != Y7T_PROG_CBIOU, "there is no called copy of the C-BIoU step alone");
-    if constexpr (PROG == Y7T_PROG_ANY_SS) {
+    if constexpr (PROG == Y7T_PROG_ANY_DM) {
+        if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_DEEPMOT && n >= 0) {
+            if (ex.tid == 0) { ((Y7TTrkHdr*)blob)->status |= Y7T_ERR_KIND; if (out_count) *out_count = 0; }
+        } else y7t_step_one<Y7T_PROG_ANY_SS, false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
+    } else if constexpr (PROG == Y7T_PROG_ANY_SS) {
         if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_STRONGSORT) {      // (its predict-only step too: y7t_tracker_step runs StrongSORT's own program for it)
             if (ex.tid == 0) { ((Y7TTrkHdr*)blob)->status |= Y7T_ERR_KIND; if (out_count) *out_count = 0; }
         } else y7t_step_one<Y7T_PROG_ANY, false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);

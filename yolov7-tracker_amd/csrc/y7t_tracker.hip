@@ -9,6 +9,8 @@
 #include "y7t_track_step.h"
 #include "y7t_track_deepsort.h"
 #include "y7t_track_strongsort.h"
+#include "y7t_track_deepmot.h"
+#include "y7t_dhn.h"
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
@@ -464,6 +466,19 @@ __global__ void __launch_bounds__(MAXT) k_tracker_step_strongsort(void* state, v
     y7t_tracker_step_strongsort(ex, state, fblob, dets, n, det_feats, out_rows, out_cap, out_count, warp);
 }
 
+// ---- DeepMOT (y7t_track_deepmot.h): the two programs of a frame, on either side of the Deep Hungarian Net's launches (y7t_dhn.hip) ----
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_deepmot_front(void* state, const float* dets, int n, int img_h, int img_w, float* D, long long d_cap, int* hw, unsigned fast_bytes) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_deepmot_front(ex, state, dets, n, img_h, img_w, D, d_cap, hw);
+}
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_deepmot_back(void* state, const float* dets, const float* net_out, const unsigned* net_status, double* out_rows, int out_cap,
+                                                        int* out_count, unsigned fast_bytes) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_deepmot_back(ex, state, dets, net_out, net_status, out_rows, out_cap, out_count);
+}
+
 __global__ void __launch_bounds__(64) k_kf_gmc(double* mean, double* cov, const double* __restrict__ warp, int N) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N) return;
@@ -535,6 +550,8 @@ template <int PROG> struct StepFrames { static const int kMinT = 256; template <
 template <int PROG> struct StepBatch { static const int kMinT = 512; template <int MAXT> static constexpr auto k = &k_tracker_step_batch<PROG, MAXT>; };      // (launches of <= 256 threads take the 512 instance)
 struct StepDeepsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_deepsort<MAXT>; };
 struct StepStrongsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_strongsort<MAXT>; };
+struct StepDeepmotFront { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_deepmot_front<MAXT>; };
+struct StepDeepmotBack { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_deepmot_back<MAXT>; };
 
 extern "C" int y7t_iou_cost_f64(const double* a, int n, const double* b, int m, double* cost, y7t_stream stream) {
     Y7T_ARG_CHECK(n >= 0 && m >= 0);
@@ -684,11 +701,12 @@ extern "C" int y7t_lapjv_f64_host(const double* cost_host, int n, int m, double 
 struct PoolInfo { int kind; size_t arena_bytes; int cap_t; };
 static std::mutex g_pool_mu;
 static std::unordered_map<const void*, PoolInfo> g_pools;
-static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0}, g_n_strongsort{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
+static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0}, g_n_strongsort{0}, g_n_deepmot{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
 static void count_kind(int kind, int d) {
     if (kind == Y7T_C_BIOU) g_n_cbiou += d;
     else if (kind == Y7T_UAVMOT) g_n_uavmot += d;
     else if (kind == Y7T_STRONGSORT) g_n_strongsort += d;
+    else if (kind == Y7T_DEEPMOT) g_n_deepmot += d;
 }
 static void forget_pool(const void* state) {      // (g_pool_mu held; an address that was never noted changes nothing)
     auto it = g_pools.find(state);
@@ -726,7 +744,7 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
                                 y7t_stream stream) {
     Y7T_ARG_CHECK(state && id_counter && cap_t > 0 && cap_d > 0);
     Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT ||
-                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT || tracker_kind == Y7T_STRONGSORT);
+                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT || tracker_kind == Y7T_STRONGSORT || tracker_kind == Y7T_DEEPMOT);
     if (tracker_kind == Y7T_C_BIOU) kalman_kind = Y7T_KF_XYAH;      // (C-BIoU has no Kalman filter: the kind is ignored)
     if (tracker_kind == Y7T_DEEPSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("DeepSORT gates on xyah measurements (deepsort.py:59): kalman_format default / strongsort only");
@@ -774,6 +792,14 @@ extern "C" int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* war
 
 // frames with detections of a StrongSORT pool belong to y7t_tracker_step_strongsort (the smoothed appearance vectors): the plain entry points refuse them like a
 // DeepSORT pool's, and say so in the pool's status word too
+// (DeepMOT's frames with detections belong to y7t_tracker_step_deepmot -- the Deep Hungarian Net sits between its two programs: refused the same way)
+static int refuse_deepmot(const char* who, void* state, int* out_count, y7t_stream stream) {
+    hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+    Y7T_LAUNCH_CHECK();
+    y7t_set_error("%s: this pool was initialised as DeepMOT -- frames with detections go through y7t_tracker_step_deepmot (the Deep Hungarian Net); only the "
+                  "predict-only step (n < 0) is shared", who);
+    return Y7T_E_STATE;
+}
 static int refuse_strongsort(const char* who, void* state, int* out_count, y7t_stream stream) {
     hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
     Y7T_LAUNCH_CHECK();
@@ -795,6 +821,8 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     const bool uav = g_n_uavmot.load() > 0, any = nt <= 512 ? (uav || g_n_cbiou.load() > 0) : uav;
     const unsigned lds = kFastBytes + Y7T_LDS_HDR;
     // ... and while a StrongSORT pool exists, the kernel that refuses such a pool (status bit 8; it steps through y7t_tracker_step_strongsort / y7t_tracker_step)
+    // ... and while a DeepMOT pool exists, the one that refuses its frames with detections as well (they step through y7t_tracker_step_deepmot)
+    if (g_n_deepmot.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_DM>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     if (g_n_strongsort.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_SS>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     if (any) return launch_step<StepBatch<Y7T_PROG_ANY>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     return launch_step<StepBatch<Y7T_PROG_PLAIN>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
@@ -813,6 +841,7 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
         return Y7T_E_STATE;
     }
     if (n >= 0 && kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step", state, out_count, stream);
+    if (n >= 0 && kind == Y7T_DEEPMOT) return refuse_deepmot("y7t_tracker_step", state, out_count, stream);      // (its predict-only step is the plain program's: default below)
     const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
     switch (kind) {
     // (predict-only: StrongSORT's own program without a feature state -- its lists may share a track, which its pool holds once, as joint_stracks does)
@@ -835,6 +864,7 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
         y7t_set_error("y7t_tracker_step_frames: a DeepSORT pool steps through y7t_tracker_step_deepsort (appearance rings)");
         return Y7T_E_STATE;
     }
+    if (pool.kind == Y7T_DEEPMOT) return refuse_deepmot("y7t_tracker_step_frames", state, nullptr, stream);
     if (pool.kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step_frames", state, nullptr, stream);      // (the frames' counts are device arrays: none is written)
     // LDS of the launch: header | fast scratch (cost matrix, assignment work arrays) | the pool's index lists for the length of the launch (y7t_arena_*), when the
     // CU's 160 KiB hold them beside at least 64 KiB of fast scratch (the default capacities, 1024 tracks x 1024 detections: 68 KiB of lists, 91 KiB of scratch)
@@ -872,10 +902,10 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const int kind = pool_info(state).kind;
-    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
         hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
         Y7T_LAUNCH_CHECK();
-        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : "StrongSORT (y7t_tracker_step_strongsort)");
+        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : "StrongSORT (y7t_tracker_step_strongsort)");
         return Y7T_E_STATE;
     }
     if (n > 0) {
@@ -932,6 +962,46 @@ extern "C" int y7t_tracker_step_strongsort(void* state, void* feat_state, const 
     if (n > 0) {
         hipLaunchKernelGGL(k_ss_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most one per detection)
         Y7T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// DeepMOT.update for one frame: the front program, the Deep Hungarian Net on the pool x high-detection matrix it wrote (skipped where either side is empty), the back
+// program.  The network's launches depend on the matrix's size, which only the device knows: the call reads two ints back between the front program and the network, and
+// the network's status word at the end -- it returns when the frame is done (a frame's network takes milliseconds: four passes of h x w sequential steps).
+extern "C" int y7t_tracker_step_deepmot(void* state, void* dhn, const float* dets, int n, int img_h, int img_w, double* out_rows, int out_cap, int* out_count, int threads,
+                                        y7t_stream stream) {
+    Y7T_ARG_CHECK(state && dhn && out_rows && out_count && out_cap >= 0 && n >= 0 && img_h > 0 && img_w > 0);
+    Y7T_ARG_CHECK(n == 0 || dets);
+    const int nt = step_threads(threads, n);
+    Y7T_ARG_CHECK(nt > 0);
+    const PoolInfo pool = pool_info(state);
+    if (pool.kind != Y7T_DEEPMOT) {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+        if (pool.kind >= 0) {
+            hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+            Y7T_LAUNCH_CHECK();
+        }
+        y7t_set_error("y7t_tracker_step_deepmot: this pool was not initialised as DeepMOT (tracker kind %d)", pool.kind);
+        return Y7T_E_STATE;
+    }
+    Y7TDhnView v;
+    if (int e = y7t_dhn_view(dhn, &v)) return e;
+    const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
+    if (int e = launch_step<StepDeepmotFront>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, n, img_h, img_w, v.D, (long long)v.max_h * v.max_w, v.hw, fb)) return e;
+    int hw[2] = {0, 0};
+    Y7T_HIP_CHECK(hipMemcpyAsync(hw, v.hw, sizeof(hw), hipMemcpyDeviceToHost, S(stream)));
+    Y7T_HIP_CHECK(hipStreamSynchronize(S(stream)));
+    const bool net = hw[0] > 0 && hw[1] > 0;
+    if (net) { if (int e = y7t_dhn_enqueue(dhn, v.D, hw[0], hw[1], v.out, S(stream))) return e; }
+    if (int e = launch_step<StepDeepmotBack>(1, nt, lds_max, fb + Y7T_LDS_HDR, stream, state, dets, (const float*)v.out, (const unsigned*)(net ? v.status : nullptr), out_rows, out_cap, out_count, fb)) return e;
+    if (net) {
+        unsigned status = 0;
+        Y7T_HIP_CHECK(hipMemcpyAsync(&status, v.status, 4, hipMemcpyDeviceToHost, S(stream)));
+        Y7T_HIP_CHECK(hipStreamSynchronize(S(stream)));
+        if (status) {
+            y7t_set_error("y7t_tracker_step_deepmot: the Deep Hungarian Net's forward gave up waiting for a peer workgroup (status %u); the frame produced no rows", status);
+            return Y7T_E_STATE;
+        }
     }
     return 0;
 }

@@ -178,3 +178,32 @@ def make_warps(n_frames=100, seq_idx=0, rot=0.002, shift=2.0):
     H[:, :2, :2] = np.eye(2) + rng.normal(0, rot, (n_frames, 2, 2))
     H[:, :, 2] = rng.normal(0, shift, (n_frames, 2))
     return H
+
+
+# ---- the Deep Hungarian Net of DeepMOT (/root/reference/tracker/deepmot.py:10-140, class Munkrs) ----
+def dhn_tensor_shapes():
+    """-> [(name, shape)]: the 38 tensors of Munkrs(element_dim=1, hidden_dim=256, target_size=1, bidirectional=True).state_dict(), in its order
+    (4,093,825 values): two 2-layer bidirectional GRUs (input widths 1 and 512, hidden 256; gate rows r, z, n) and three linear layers"""
+    out = []
+    for gru, first in (("lstm_row", 1), ("lstm_col", 512)):
+        for layer in (0, 1):
+            for suffix in ("", "_reverse"):
+                width = first if layer == 0 else 512
+                out += [("%s.weight_ih_l%d%s" % (gru, layer, suffix), (768, width)), ("%s.weight_hh_l%d%s" % (gru, layer, suffix), (768, 256)),
+                        ("%s.bias_ih_l%d%s" % (gru, layer, suffix), (768,)), ("%s.bias_hh_l%d%s" % (gru, layer, suffix), (768,))]
+    for i, (fin, fout) in enumerate(((512, 256), (256, 64), (64, 1)), 1):
+        out += [("hidden2tag_%d.weight" % i, (fout, fin)), ("hidden2tag_%d.bias" % i, (fout,))]
+    return out
+
+
+def make_dhn_weights(seed=0, scale=1.0):
+    """seeded weights of the Deep Hungarian Net (no DHN.pth ships with the reference) -> {name: float32 array} in state_dict() order.  One
+    numpy.random.RandomState(seed), tensor by tensor: uniform(-scale / sqrt(fan), +scale / sqrt(fan)) with fan = 256 for every GRU tensor, in_features for a
+    linear layer's weight and its bias.  scale = 1 (PyTorch's own initialisation range) makes the network nearly constant; scale >= 3 spreads its output."""
+    rng = np.random.RandomState(int(seed))
+    out = {}
+    for name, shape in dhn_tensor_shapes():
+        fan = 256 if name.startswith("lstm_") else {"1": 512, "2": 256, "3": 64}[name.split(".")[0][-1]]
+        bound = float(scale) / np.sqrt(float(fan))
+        out[name] = rng.uniform(-bound, bound, size=shape).astype(np.float32)
+    return out

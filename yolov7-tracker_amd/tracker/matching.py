@@ -1,7 +1,7 @@
 """Association ops with the reference's signatures (/root/reference/tracker/matching.py:30-82),
 computed on the MI355X by liby7t.so: `iou_distance` (IoU with the +1 pixel convention of
 cython_bbox.bbox_overlaps) and `linear_assignment` (lap.lapjv(extend_cost=True, cost_limit=t)); UAVMOT's structure cost
-(matching.py:284-388) with `structure_similarity_distance` on the device; `embedding_distance` (matching.py:84-103) on the track views' vectors."""
+(matching.py:284-388) with `structure_similarity_distance` on the device; `embedding_distance` (matching.py:84-103) on the track views' vectors; DeepMOT's `ecu_iou_distance` (matching.py:129-162)."""
 import math
 
 import numpy as np
@@ -39,6 +39,24 @@ def iou_distance(atracks, btracks):
     if len(atlbrs) == 0 or len(btlbrs) == 0:
         return np.zeros((len(atlbrs), len(btlbrs)), dtype=np.float64)
     return _cost(atlbrs, btlbrs)
+
+
+def ecu_iou_distance(tracks, detections, img0_shape):
+    """matching.py:129-162 (DeepMOT): 0.5 * ((1 - exp(-5 * centre distance / image diagonal)) + iou_distance) -> (N, M) float64.  The centres are taken in the
+    boxes' own dtypes (a detection's tlwh is float32, a predicted track's float64), their differences in float64, as numpy evaluates the reference's lines.
+    Host arithmetic beside the device IoU, for code written against the reference's matching module; the fused device step computes the same per pair
+    (csrc/y7t_track_deepmot.h: y7t_dm_ecu_iou)."""
+    cost_matrix = np.zeros((len(tracks), len(detections)), dtype=np.float64)
+    if cost_matrix.size == 0:
+        return cost_matrix
+    det_bbox = np.asarray([det.tlwh for det in detections])
+    trk_bbox = np.asarray([trk.tlwh for trk in tracks])
+    det_cx, det_cy = det_bbox[:, 0] + 0.5 * det_bbox[:, 2], det_bbox[:, 1] + 0.5 * det_bbox[:, 3]
+    trk_cx, trk_cy = trk_bbox[:, 0] + 0.5 * trk_bbox[:, 2], trk_bbox[:, 1] + 0.5 * trk_bbox[:, 3]
+    ecu_dist = np.asarray([np.sqrt((det_cx - trk_cx[i]) ** 2 + (det_cy - trk_cy[i]) ** 2) for i in range(len(tracks))])
+    norm_factor = float((img0_shape[0] ** 2 + img0_shape[1] ** 2) ** 0.5)
+    ecu_dist = 1. - np.exp(-5 * ecu_dist / norm_factor)
+    return 0.5 * (ecu_dist + iou_distance(tracks, detections))
 
 
 def cal_cosine_distance(mat1, mat2):

@@ -24,11 +24,12 @@ from .deepsort import DeepSORT
 from .c_biou_tracker import C_BIoUTracker
 from .uavmot import UAVMOT
 from .strongsort import StrongSORT
+from .deepmot import DeepMOT
 from .timer import Timer
 from ..detector import attempt_load, check_img_size, non_max_suppression, scale_coords
 
 TRACKER_DICT = {'sort': BaseTracker, 'bytetrack': ByteTrack, 'botsort': BoTSORT, 'deepsort': DeepSORT,
-                'c_biou': C_BIoUTracker, 'uavmot': UAVMOT, 'strongsort': StrongSORT}   # track.py:56-65; deepmot (weights/DHN.pth) is out of scope
+                'c_biou': C_BIoUTracker, 'uavmot': UAVMOT, 'strongsort': StrongSORT, 'deepmot': DeepMOT}   # track.py:56-65: all eight keys
 
 timer = Timer()
 seq_fps = []
