@@ -476,16 +476,8 @@ def test_decode_nms_matches_oracle():
         assert (d[:, :4] - rr[:, :4]).abs().max().item() <= 1.0          # |dcoord| <= 1 px after round
         assert ((d[:, :4] - rr[:, :4]).abs() > 0).float().mean().item() < 0.02
     # exact greedy semantics on identical inputs: oracle NMS over the device's own candidates keeps the same set
-    cap = det.max_cand
-    ws = p.ws
-    B = det.max_batch
-    cbox = ws[:B * cap * 16].view(torch.float32).view(B, cap, 4).cpu().numpy()
-    off = (B * cap * 16 + 255) // 256 * 256
-    cscore = ws[off:off + B * cap * 4].view(torch.float32).view(B, cap).cpu().numpy()
-    off2 = off + (B * cap * 4 + 255) // 256 * 256
-    ccls = ws[off2:off2 + B * cap * 4].view(torch.float32).view(B, cap).cpu().numpy()
-    off3 = off2 + (B * cap * 4 + 255) // 256 * 256
-    cidx = ws[off3:off3 + B * cap * 4].view(torch.int32).view(B, cap).cpu().numpy()
+    from tests import post_scenes
+    cbox, cscore, ccls, cidx, _ = post_scenes.unpack_candidates(p.ws.cpu().numpy(), det.max_batch, det.max_cand)      # the workspace's documented head
     cnt = p.cand.cpu().numpy()
     keep = p.keep.cpu().numpy()
     for b in range(2):

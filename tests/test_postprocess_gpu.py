@@ -1,0 +1,389 @@
+"""Per-kernel parity tests of the post-processing chain in csrc/y7t_post.hip -- k_decode_filter -> k_rank_sort -> k_nms_keep behind y7t_det_postprocess -- through the
+C ABI, at the shapes and edges where these kernels can go wrong: empty images, candidate counts around a wave / a sort chunk, the max_det / max_nms / cap cuts, exact
+ties, thresholds on and off 0.45, one class and eighty.
+
+Planted candidates (head == NULL): the candidate arrays are written into the head of the workspace (tests/post_scenes.py::pack_candidates), so every box, score,
+class, anchor row and count is under the test's control, and ndets / keep_idx / the (B, max_det, 6) rows are compared EXACTLY with the reference walk
+(post_scenes.reference_walk: oracle.detector_torch.nms_rows on arrays) -- identical inputs, the same float32 expressions and a build without contraction leave nothing
+to tolerate.  Planted head logits (head != NULL) at tiny grids put k_decode_filter itself under test against oracle.detector_torch.decode_level + candidates.
+tests/test_post_scenes.py shows on the CPU that every scene has the property its case is about."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests import post_scenes as ps
+
+pytestmark = pytest.mark.gpu
+
+IDENT = (1.0, 0.0, 0.0, 4096.0, 4096.0)      # identity letterbox: gain 1, no padding, a frame larger than every ordinary scene
+DSENT, ISENT, TAIL = -12345.0, -7, 4096      # what the outputs hold before a call; sentinel bytes allocated behind the workspace
+
+
+@pytest.fixture(scope="module")
+def L():
+    from yolov7_tracker_amd import _lib
+    _lib.require_gpu()
+    return _lib.load()
+
+
+class Chain:
+    """one workspace + output set of y7t_det_postprocess for B images of `cap` candidate slots"""
+
+    def __init__(self, L, B, cap):
+        self.L, self.B, self.cap = L, B, cap
+        self.lay = ps.ws_layout(B, cap)
+        assert self.lay["total"] == int(L.y7t_det_postprocess_workspace_bytes(B, cap, 30000))
+        self.ws = torch.full((self.lay["total"] + TAIL,), ps.SENTINEL, dtype=torch.uint8, device="cuda")
+        self.cand = torch.zeros(B, dtype=torch.int32, device="cuda")
+        self.out = {}
+
+    def plant(self, scenes, counts=None):
+        assert len(scenes) == self.B
+        self.planted = ps.pack_candidates(scenes, self.cap, counts)
+        self.ws[:len(self.planted)].copy_(torch.from_numpy(self.planted))
+
+    def run(self, iou=0.45, max_det=300, max_nms=30000, lb=IDENT, conf=0.01, heads=None):
+        """-> dets (B, max_det, 6), ndets (B,), keep_idx (B, max_det), cand_count (B,) as numpy; the outputs are the same tensors from call to call (per max_det),
+        refilled with their sentinels.  heads: a post_scenes.decode_scene (head != NULL: the decode pass runs first)"""
+        from yolov7_tracker_amd import _lib
+        B = self.B
+        if max_det not in self.out:
+            self.out[max_det] = (torch.empty((B, max_det, 6), device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda"),
+                                 torch.empty((B, max_det), dtype=torch.int32, device="cuda"))
+        dets, nd, keep = self.out[max_det]
+        dets.fill_(DSENT); nd.fill_(ISENT); keep.fill_(ISENT); self.cand.fill_(ISENT)
+        lbt = torch.tensor(np.broadcast_to(np.asarray(lb, np.float32), (B, 5)).copy(), device="cuda")
+        if heads is None:
+            hp = ny = nx = st = an = None
+            nl, na, no = 4, 3, 15                                                    # (unused with head == NULL, but validated)
+        else:
+            nl, na, no = heads["nl"], heads["na"], heads["no"]
+            self._heads = [torch.from_numpy(h).cuda() for h in heads["heads"]]
+            hp = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in self._heads] + [None] * (4 - nl))
+            ny = (ctypes.c_int * 4)(*[s[0] for s in heads["shapes"]] + [0] * (4 - nl))
+            nx = (ctypes.c_int * 4)(*[s[1] for s in heads["shapes"]] + [0] * (4 - nl))
+            st = (ctypes.c_float * 4)(*[float(v) for v in heads["strides"]] + [0.0] * (4 - nl))
+            flat = [float(v) for v in heads["anchors"].ravel()]
+            an = (ctypes.c_float * 24)(*(flat + [0.0] * (24 - len(flat))))
+        _lib.check(self.L.y7t_det_postprocess(hp, ny, nx, st, an, nl, na, no, B, float(conf), float(iou), max_det, max_nms, self.cap, _lib.ptr(lbt), _lib.ptr(dets),
+                                              _lib.ptr(nd), _lib.ptr(keep), _lib.ptr(self.cand), _lib.ptr(self.ws), self.lay["total"], _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        return dets.cpu().numpy(), nd.cpu().numpy(), keep.cpu().numpy(), self.cand.cpu().numpy()
+
+    def candidates(self):
+        """what the workspace's candidate arrays hold, as scenes (image b's first min(count, cap) slots) + the raw counts"""
+        cbox, cscore, ccls, cidx, count = ps.unpack_candidates(self.ws.cpu().numpy(), self.B, self.cap)
+        return [{"box": cbox[b, :min(n, self.cap)], "score": cscore[b, :min(n, self.cap)], "cls": ccls[b, :min(n, self.cap)], "rows": cidx[b, :min(n, self.cap)]}
+                for b, n in enumerate(count)], count.copy()
+
+
+def check_image(out, b, scene, iou=0.45, max_det=300, max_nms=30000, lb=IDENT, ref=None):
+    """image b of a call's outputs against the reference walk over `scene` (what the chain saw of the image): ndets, the kept slots and their anchor rows in order,
+    the six columns of every row exactly, and nothing written past ndets"""
+    dets, nd, keep, _ = out
+    ref = ps.reference_walk(scene, iou, max_nms, max_det) if ref is None else ref
+    n = int(nd[b])
+    assert n == len(ref), "image %d: ndets %d, the reference keeps %d" % (b, n, len(ref))
+    np.testing.assert_array_equal(scene["rows"][keep[b, :n]], scene["rows"][ref], err_msg="image %d: kept anchor rows" % b)
+    np.testing.assert_array_equal(keep[b, :n], ref, err_msg="image %d: kept slots" % b)
+    np.testing.assert_array_equal(dets[b, :n], ps.expected_rows(scene, ref, lb), err_msg="image %d: rows" % b)
+    assert (dets[b, n:] == np.float32(DSENT)).all() and (keep[b, n:] == ISENT).all(), "image %d: rows past ndets were written" % b
+    return n
+
+
+# ------------------------------------------------------------------------------------------------ planted candidates: k_rank_sort, k_nms_keep
+def test_candidate_counts_at_the_wave_and_chunk_boundaries(L):
+    """case 1: sixteen images of one call with 0, 1, 2, 63 ... 513, 1000 candidates -- around a wave (64), a sort chunk (256), two and four of them.  The batch in
+    reverse image order gives every image the same result (results are per image)."""
+    scenes = [ps.clustered(n, seed=n) for n in ps.BOUNDARY_COUNTS]
+    ch = Chain(L, len(scenes), 1024)
+    ch.plant(scenes)
+    out = ch.run()
+    kept = [check_image(out, b, s) for b, s in enumerate(scenes)]
+    assert kept[0] == 0 and out[3].tolist() == list(ps.BOUNDARY_COUNTS)
+    ch.plant(scenes[::-1])
+    rev = ch.run()
+    for b, s in enumerate(scenes[::-1]):
+        check_image(rev, b, s)
+        a = len(scenes) - 1 - b
+        assert rev[1][b] == out[1][a] and np.array_equal(rev[0][b], out[0][a]) and np.array_equal(rev[2][b], out[2][a])
+
+
+def test_empty_image_after_a_full_one(L):
+    """case 2: a second call on the same workspace and outputs with count = [5, 0, 300, 0] after a call with ~300 candidates in every image: the empty images report
+    ndets = 0 (k_rank_sort publishes nsorted for an image without candidates too; nothing else resets it), the others their own candidates"""
+    full = [ps.clustered(300 + b, seed=300 + b) for b in range(4)]
+    ch = Chain(L, 4, 1024)
+    ch.plant(full)
+    out = ch.run()
+    assert all(check_image(out, b, s) > 20 for b, s in enumerate(full))
+    second = [ps.clustered(5, seed=5), ps.clustered(0, seed=0), ps.clustered(300, seed=1300), ps.clustered(0, seed=0)]
+    ch.plant(second)
+    out = ch.run()
+    want = [len(ps.reference_walk(s)) for s in second]
+    assert want[1] == want[3] == 0 and want[0] > 0 and want[2] > 20
+    assert out[1].tolist() == want and out[3].tolist() == [5, 0, 300, 0]
+    for b, s in enumerate(second):
+        check_image(out, b, s)
+
+
+def _tiny(nc):
+    from yolov7_tracker_amd.detector import arch, model
+    return model.Detector(arch.ARCHS["yolov7-tiny"](nc), None, img_size=(128, 192), max_batch=2, seed=0)
+
+
+def test_detector_empty_image_after_a_full_one_plain_forward():
+    """case 2 at the product level, decode pass: Detector.postprocess on random planted heads, then again with image 1's objectness logits at -20 -> no candidate, no detection"""
+    det = _tiny(80)
+    g = torch.Generator().manual_seed(11)
+    out = det(torch.rand((2, 3, 128, 192), generator=g))[0]
+    no = det.plan.det["no"]
+    for l in range(len(det.plan.heads)):
+        t = det.head_tensor(l, 2)
+        t.copy_((torch.randn(t.shape, generator=g) * 1.5).cuda())
+    d0, n0 = det.postprocess(out, 0.01, 0.45, None)
+    d0, n0, c0 = d0.clone(), n0.cpu().numpy().copy(), det.plan.post[out.pset].cand.cpu().numpy().copy()
+    assert n0.min() > 10 and c0.min() > 100
+    for l in range(len(det.plan.heads)):
+        t = det.head_tensor(l, 2)
+        t.view(2, t.shape[1], t.shape[2], 3, no)[1, ..., 4] = -20.0
+    d1, n1 = det.postprocess(out, 0.01, 0.45, None)
+    torch.cuda.synchronize()
+    c1 = det.plan.post[out.pset].cand.cpu().numpy()
+    assert c1.tolist() == [int(c0[0]), 0]
+    assert n1.cpu().numpy().tolist() == [int(n0[0]), 0]
+    assert torch.equal(d1[0, :int(n0[0])], d0[0, :int(n0[0])])
+
+
+def test_detector_empty_image_after_a_full_one_fused_forward():
+    """case 2 at the product level, fused Detect epilogues (y7t_det_forward_fused + head == NULL): a forward at conf_thres = 0.01 fills both images' candidate lists; the
+    next forward on the same post-processing set runs at a threshold between the two images' best confidences, which leaves one image without a candidate -> ndets = 0 there"""
+    det = _tiny(10)
+    assert det.plan.fusable
+    img = torch.rand((2, 3, 128, 192), generator=torch.Generator().manual_seed(12))
+    out = det.forward(img, fuse_decode=0.01)
+    _, n0 = det.postprocess(out, 0.01, 0.45, None)
+    torch.cuda.synchronize()
+    _, cscore, _, _, count = det.candidate_arrays(out.pset)
+    count = count.cpu().numpy()
+    assert n0.cpu().numpy().min() > 0 and count.min() > 0
+    best = np.array([float(cscore[b, :count[b]].max()) for b in range(2)], np.float32)
+    lo, hi = int(np.argmin(best)), int(np.argmax(best))
+    thr = float(np.float32((float(best[lo]) + float(best[hi])) / 2))
+    assert best[lo] < np.float32(thr) < best[hi], best                    # (two random images: their best confidences differ)
+    out = det.forward(img, fuse_decode=thr)
+    _, n1 = det.postprocess(out, thr, 0.45, None)
+    torch.cuda.synchronize()
+    c1, n1 = det.plan.post[out.pset].cand.cpu().numpy(), n1.cpu().numpy()
+    assert c1[lo] == 0 and c1[hi] >= 1
+    assert n1[lo] == 0 and n1[hi] >= 1
+
+
+@pytest.mark.parametrize("max_det", [1, 2, 63, 64, 65, 300])
+def test_max_det_cut(L, max_det):
+    """case 3: the output is the first max_det of the uncut keep list -- cuts in the middle of a wave's keep loop (63, 65), at its end (64) and in a later sort chunk (300)"""
+    s = ps.separated()
+    ch = Chain(L, 2, 1024)
+    ch.plant([s, ps.clustered(1000, seed=1000)])                           # (image 1 stays under the cut: the images end their walks at different places)
+    out = ch.run(max_det=max_det)
+    uncut = ps.reference_walk(s, max_det=10 ** 9)
+    assert len(uncut) >= 400
+    assert check_image(out, 0, s, max_det=max_det, ref=uncut[:max_det]) == max_det
+    check_image(out, 1, ps.clustered(1000, seed=1000), max_det=max_det)
+
+
+@pytest.mark.parametrize("max_nms", [64, 100, 257])
+def test_max_nms_cut(L, max_nms):
+    """case 4: only the max_nms best candidates (distinct scores: the cut is unambiguous) enter the walk; sbox / sorder are addressed with mcap = max_nms"""
+    scenes = [ps.clustered(600, seed=600), ps.clustered(600, seed=601)]
+    ch = Chain(L, 2, 1024)
+    ch.plant(scenes)
+    out = ch.run(max_nms=max_nms)
+    for b, s in enumerate(scenes):
+        assert check_image(out, b, s, max_nms=max_nms) < len(ps.reference_walk(s))
+
+
+def test_smallest_cap(L):
+    """case 4: cap = 64 with max_nms = 30000 -- the ABI clamps max_nms to cap: mcap = cap addressing at its smallest"""
+    scenes = [ps.prefix(ps.clustered(600, seed=600), 64), ps.prefix(ps.clustered(600, seed=601), 64), ps.clustered(0, seed=0)]
+    ch = Chain(L, 3, 64)
+    ch.plant(scenes)
+    out = ch.run()
+    assert [check_image(out, b, s) for b, s in enumerate(scenes)][2] == 0
+
+
+def test_greedy_order_along_a_chain(L):
+    """case 5: 300 boxes, neighbours at IoU 0.5 > 0.45: a suppressed candidate must not suppress -- its mask row is never applied -- across wave and chunk boundaries;
+    scores descending and ascending along the chain (150 kept; "suppressed by any better box" keeps 1) and permuted"""
+    scenes = [ps.chain("descending"), ps.chain("ascending"), ps.chain("permuted")]
+    ch = Chain(L, 3, 1024)
+    ch.plant(scenes)
+    out = ch.run()
+    kept = [check_image(out, b, s) for b, s in enumerate(scenes)]
+    assert kept[:2] == [150, 150] and kept[2] >= 100
+
+
+def test_tight_cluster_ties_and_duplicates(L):
+    """case 6: 512 candidates within 3 % of one box -> one detection; groups of 8 bit-identical scores come out in ascending anchor row (and the max_det cut falls inside
+    a group); bit-identical duplicate boxes: the first is kept at 0.45, all of them at iou_thres = 1.0"""
+    scenes = [ps.tight_cluster(), ps.ties(), ps.duplicates()]
+    ch = Chain(L, 3, 1024)
+    ch.plant(scenes)
+    out = ch.run()
+    assert [check_image(out, b, s) for b, s in enumerate(scenes)] == [1, 300, 8]
+    out = ch.run(iou=1.0)
+    assert [check_image(out, b, s, iou=1.0) for b, s in enumerate(scenes)] == [300, 300, 64]
+
+
+@pytest.mark.parametrize("iou", [0.0, 0.45, 0.65, 1.0])
+def test_thresholds(L, iou):
+    """case 7: at 0.0 every intersecting pair of a class suppresses and touching boxes (zero intersection) do not; at 1.0 nothing is suppressed"""
+    scenes = [ps.clustered(1000, seed=1000), ps.touching(), ps.class_offsets()]
+    ch = Chain(L, 3, 1024)
+    ch.plant(scenes)
+    out = ch.run(iou=iou)
+    kept = [check_image(out, b, s, iou=iou) for b, s in enumerate(scenes)]
+    if iou == 0.0:
+        assert out[2][1, :3].tolist() == [0, 1, 3]
+    if iou == 1.0:
+        assert kept == [300, 4, 300]
+
+
+def test_iou_exactly_at_the_threshold(L):
+    """case 7: [0, 0, 4, 4] and [0, 0, 4, 2], IoU exactly 0.5: kept at iou_thres = 0.5 (the test is >), suppressed at the float32 just below"""
+    s = ps.exact_half()
+    ch = Chain(L, 1, 64)
+    ch.plant([s])
+    assert check_image(ch.run(iou=0.5), 0, s, iou=0.5) == 2
+    below = float(np.nextafter(np.float32(0.5), np.float32(0)))
+    assert check_image(ch.run(iou=below), 0, s, iou=below) == 1
+
+
+def test_class_offsets(L):
+    """case 8: 80 classes, fractional coordinates: box + cls x 4096 is inexact past 2^18 and must round like the oracle's; identical boxes of different classes are all
+    kept; a zero-area box and a 4000-px box among ordinary ones"""
+    s = ps.class_offsets()
+    ch = Chain(L, 2, 1024)
+    ch.plant([s, ps.clustered(0, seed=0)])
+    for iou in (0.45, 0.65):
+        out = ch.run(iou=iou, lb=(1.0, 0.0, 0.0, 1280.0, 1280.0))
+        assert 50 < check_image(out, 0, s, iou=iou, lb=(1.0, 0.0, 0.0, 1280.0, 1280.0)) < 300
+        assert out[1][1] == 0
+
+
+@pytest.mark.parametrize("cap", [1024, 1000])
+def test_overflow_walks_cap_candidates_and_writes_nothing_else(L, cap):
+    """case 9: count = cap + 1000 with the cap slots filled: the walk runs over exactly cap candidates, cand_count returns the planted count, and the candidate arrays,
+    the padding behind every array of the workspace (cap = 1000: the arrays do not end on 256 bytes), the bytes behind the workspace and the rows past ndets are untouched"""
+    scenes = [ps.prefix(ps.clustered(1024, seed=9000 + b), cap) for b in range(2)]
+    ch = Chain(L, 2, cap)
+    ch.plant(scenes, counts=[cap + 1000, cap + 1000])
+    out = ch.run()
+    assert out[3].tolist() == [cap + 1000] * 2
+    for b, s in enumerate(scenes):
+        assert check_image(out, b, s) > 20
+    ws = ch.ws.cpu().numpy()
+    assert np.array_equal(ws[:len(ch.planted)], ch.planted)                           # candidate arrays, count and their padding
+    names = [k for k in ch.lay if k != "total"]
+    ends = [ch.lay[k][0] for k in names[1:]] + [ch.lay["total"]]
+    for k, end in zip(names, ends):
+        o, nbytes = ch.lay[k]
+        assert (ws[o + nbytes:end] == ps.SENTINEL).all(), "bytes behind %s were written" % k
+    assert (ws[ch.lay["total"]:] == ps.SENTINEL).all()
+
+
+def test_rescale_clip_round(L):
+    """case 10: with letterbox parameters that are exact in float32 (gain 2 / pad 0; gain 1 / pad 28) the rows are bit-equal to oracle.detector_torch.scale_coords_round:
+    boxes past every edge are clipped to [0, W0] x [0, H0], x.5 rounds half to even.  At 1080 x 1920 -> 1280 (gain 2/3 is not a float32) the bar of
+    test_decode_nms_matches_oracle holds: |d| <= 1 px, fewer than 2 % of the coordinates differ."""
+    from oracle import detector_torch as dt
+    s = ps.rescale_scene()
+    ref = ps.reference_walk(s)
+    box = torch.from_numpy(s["box"][ref].copy())
+    ch = Chain(L, 1, 1024)
+    ch.plant([s])
+    for img1, img0, lb in (((256, 320), (128, 160), (2.0, 0.0, 0.0, 128.0, 160.0)), ((256, 320), (200, 320), (1.0, 0.0, 28.0, 200.0, 320.0))):
+        out = ch.run(lb=lb)
+        assert check_image(out, 0, s, lb=lb) == len(ref)
+        want = dt.scale_coords_round(img1, box, img0).numpy()
+        assert np.array_equal(out[0][0, :len(ref), :4], want)
+        assert want.min() == 0 and want[:, [0, 2]].max() == img0[1] and want[:, [1, 3]].max() == img0[0]
+    H, W = 768, 1280                                                                  # letterbox of a 1080 x 1920 frame at 1280 (Detector.letterbox_params)
+    gain = min(H / 1080, W / 1920)
+    lb = (gain, (W - 1920 * gain) / 2, (H - 1080 * gain) / 2, 1080.0, 1920.0)         # as Detector.postprocess computes them
+    out = ch.run(lb=lb)
+    n = int(out[1][0])
+    assert n == len(ref) and np.array_equal(out[2][0, :n], ref)
+    d = np.abs(out[0][0, :n, :4] - dt.scale_coords_round((H, W), box, (1080, 1920)).numpy())
+    print("1080 x 1920: max |d| %.1f px, %.2f %% of the coordinates differ" % (d.max(), 100 * (d > 0).mean()))
+    assert d.max() <= 1.0 and (d > 0).mean() < 0.02
+    assert np.array_equal(out[0][0, :n, 4], s["score"][ref]) and np.array_equal(out[0][0, :n, 5], s["cls"][ref])
+
+
+def test_determinism(L):
+    """case 11: the 1000-candidate clustered scene and the chain, each 20 times in one process as 16 identical images: dets, ndets and keep_idx are bit-identical from call
+    to call and from image to image (the turn-counter protocol between the waves decides WHEN a wave tests, never what is kept)"""
+    for s in (ps.clustered(1000, seed=1000), ps.chain("permuted")):
+        ch = Chain(L, 16, 1024)
+        ch.plant([s] * 16)
+        first = ch.run()
+        check_image(first, 0, s)
+        for b in range(1, 16):
+            assert first[1][b] == first[1][0] and np.array_equal(first[0][b], first[0][0]) and np.array_equal(first[2][b], first[2][0])
+        for _ in range(19):
+            out = ch.run()
+            assert all(np.array_equal(a, b) for a, b in zip(out, first))
+
+
+# ------------------------------------------------------------------------------------------------ planted head logits: k_decode_filter
+def _check_decoded(sc, ref, scenes, count, cap):
+    """the candidate arrays the decode pass left (scenes / count) against the oracle's candidates `ref` of the same logits"""
+    for b in range(sc["B"]):
+        got, want = scenes[b], ref[b]
+        n = len(got["rows"])
+        assert n == min(int(count[b]), cap)
+        rows = got["rows"].tolist()
+        assert len(set(rows)) == n and set(rows) <= set(want)
+        if count[b] <= cap:
+            assert count[b] == len(want) and set(rows) == set(want)
+        for j, r in enumerate(rows):
+            wbox, wconf, wcls, wvec = want[r]
+            top2 = np.sort(wvec)[-2:] if len(wvec) > 1 else np.array([-1.0, wvec[0]])
+            assert int(got["cls"][j]) == wcls or top2[1] - top2[0] <= 1e-6, (b, r)
+            np.testing.assert_allclose(got["score"][j], wconf, rtol=1e-5, atol=1e-6, err_msg="image %d row %d score" % (b, r))
+            np.testing.assert_allclose(got["box"][j], wbox, rtol=1e-5, atol=1e-4, err_msg="image %d row %d box" % (b, r))
+
+
+@pytest.mark.parametrize("conf", [0.01, 0.25])
+@pytest.mark.parametrize("gi", range(len(ps.GRIDS)))
+def test_decode_filter_matches_oracle(L, gi, conf):
+    """head != NULL on tiny grids with arbitrary strides and anchors: the set of candidate rows, count, and per row class, score (rtol 1e-5 / atol 1e-6) and box
+    (rtol 1e-5 / atol 1e-4) against oracle.detector_torch.decode_level + candidates.  No score lies within 1e-4 of conf_thres (tests/test_post_scenes.py), so membership
+    is unambiguous and no row is left out.  The rest of the chain then runs on what the decode wrote: its output equals the reference walk over those candidates."""
+    sc = ps.decode_scene(gi, conf)
+    ref = ps.decode_reference(sc, conf)
+    ch = Chain(L, sc["B"], 1024)
+    out = ch.run(conf=conf, heads=sc)
+    scenes, count = ch.candidates()
+    assert np.array_equal(out[3], count) and count.tolist() == [len(r) for r in ref]
+    _check_decoded(sc, ref, scenes, count, 1024)
+    for b, s in enumerate(scenes):
+        check_image(out, b, s)
+
+
+def test_decode_filter_overflow(L):
+    """every objectness logit at +6 with cap = 64: cand_count is the number of anchors, B x A in all, and the slots below cap are self-consistent -- each cidx is a real row
+    and its box, score and class are that row's; the walk runs over those 64"""
+    sc = ps.decode_scene(2, 0.01, obj_logit=6.0)
+    ref = ps.decode_reference(sc, 0.01)
+    ch = Chain(L, sc["B"], 64)
+    out = ch.run(heads=sc)
+    scenes, count = ch.candidates()
+    assert out[3].tolist() == count.tolist() == [sc["A"]] * sc["B"] and int(out[3].sum()) == sc["B"] * sc["A"]
+    assert all(len(s["rows"]) == 64 for s in scenes)
+    _check_decoded(sc, ref, scenes, count, 64)
+    for b, s in enumerate(scenes):
+        check_image(out, b, s)
+    assert (ch.ws.cpu().numpy()[ch.lay["total"]:] == ps.SENTINEL).all()

@@ -384,6 +384,9 @@ __global__ void __launch_bounds__(256) k_rank_sort(const float* __restrict__ cbo
     const int b = blockIdx.y;
     int n = count[b]; if (n > cap) n = cap;
     const int i = blockIdx.x * 256 + threadIdx.x;
+    // published for EVERY image, before the early return: block 0 of an image without candidates leaves here too, and k_nms_keep would otherwise walk whatever the
+    // previous call on this workspace sorted (nothing else resets nsorted) and report that frame's detections for an empty one
+    if (i == 0) nsorted[b] = n < max_nms ? n : max_nms;
     if (blockIdx.x * 256 >= n) return;
     const float* sc = cscore + (size_t)b * cap;
     const int* ix = cidx + (size_t)b * cap;
@@ -416,7 +419,6 @@ __global__ void __launch_bounds__(256) k_rank_sort(const float* __restrict__ cbo
         so[0] = bo[0] + off; so[1] = bo[1] + off; so[2] = bo[2] + off; so[3] = bo[3] + off;
         sorder[(size_t)b * mcap + rank] = i;
     }
-    if (i == 0) nsorted[b] = n < max_nms ? n : max_nms;
 }
 
 // ------------------------------------------------------------------------------------------------ greedy NMS, kept-list form
