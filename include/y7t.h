@@ -141,9 +141,30 @@ int y7t_tracker_step(void* state, const float* dets, int n, double* out_rows, in
 
 /* BoT-SORT (tracker/botsort.py:313-493, tracker kind Y7T_TRACKER_BOTSORT, Kalman kind botsort): `gmc_warp` / `gmc_warps[b]` is the
  * 2x3 camera-motion matrix of the frame (row-major, 6 doubles in DEVICE memory; NULL = no compensation) that the reference's
- * GMC.apply returns (botsort.py:13-248 -- OpenCV ORB/RANSAC estimation, out of scope); the step applies multi_gmc
+ * GMC.apply returns (botsort.py:13-248; the 'ecc' method is y7t_ecc_align below, ORB / SIFT / file are out of scope); the step applies multi_gmc
  * (botsort.py:250-269) to the predicted pool and the unconfirmed tracks.  Same op on its own: */
 int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* warp, int N, y7t_stream stream);
+
+/* Camera-motion ESTIMATION: GMC(method='ecc') of the reference (tracker/botsort.py:78-109 = cv2.findTransformECC, MOTION_EUCLIDEAN, identity start) in exact
+ * arithmetic (DESIGN.md section 4 "GMC / ECC" states the specification and what is not claimed against OpenCV's fixed-point 8-bit routines).
+ * A PLANE is h x w pixels of 16 bytes {I, gx, gy, 0} float32 (the gray level and its central-difference gradients), 16-byte aligned, in DEVICE memory.
+ * y7t_ecc_prepare_u8: bgr = (H, W, 3) uint8 frame (device) -> the plane of (H / downscale) x (W / downscale) pixels: gray, 3x3 Gaussian blur sigma 1.5, bilinear
+ *   resize, gradients, in one launch.  downscale >= 1; 1 skips blur and resize (botsort.py:86).
+ * y7t_ecc_workspace_bytes: bytes of DEVICE workspace (8-byte aligned) one alignment of h x w planes needs; no initialisation required.
+ * y7t_ecc_align: warp_out6_f64 (6 doubles, device, row-major 2x3) = the Euclidean warp that maps template coordinates into the image, identity when the
+ *   alignment fails (botsort.py:104-107); status_out (4 doubles, device) = {iterations run, Y7T_ECC_* flag, final rho, |rho - rho_last|}.  At most max_iters
+ *   iterations, stopping when |rho - rho_last| < eps as OpenCV does; eps < 0 never stops early.  motion other than Y7T_ECC_MOTION_EUCLIDEAN: Y7T_E_ARG.
+ *   Asynchronous: max_iters + 3 launches on `stream`, nothing is read back; the same inputs give the same bits on every run.
+ * y7t_ecc_iteration_sums_f64 (tests): the 21 combined sums of ONE iteration at the parameters (theta, tx, ty) -> sums_out21_f64 (device): N, sum I, sum I^2,
+ *   sum T, sum T^2, sum IT, sum J (3), sum J I (3), sum J T (3), sum J J^T (00 01 02 11 12 22) over the mask. */
+enum { Y7T_ECC_MOTION_TRANSLATION = 0, Y7T_ECC_MOTION_EUCLIDEAN = 1, Y7T_ECC_MOTION_AFFINE = 2, Y7T_ECC_MOTION_HOMOGRAPHY = 3 };   /* cv2.MOTION_* */
+enum { Y7T_ECC_STATUS_CONVERGED = 1, Y7T_ECC_STATUS_EXHAUSTED = 2, Y7T_ECC_STATUS_FAILED = 3 };
+int y7t_ecc_prepare_u8(const uint8_t* bgr, int H, int W, int downscale, void* plane_out, y7t_stream stream);
+int y7t_ecc_workspace_bytes(int h, int w, size_t* out);
+int y7t_ecc_align(const void* tmpl_plane, const void* img_plane, int h, int w, int motion, int max_iters, double eps, void* workspace,
+                  double* warp_out6_f64, double* status_out, y7t_stream stream);
+int y7t_ecc_iteration_sums_f64(const void* tmpl_plane, const void* img_plane, int h, int w, double theta, double tx, double ty, void* workspace,
+                               double* sums_out21_f64, y7t_stream stream);
 
 /* C-BIoU (tracker/c_biou_tracker.py:212-353, tracker kind Y7T_TRACKER_C_BIOU; the Kalman kind of y7t_tracker_init is ignored): no motion model, three
  * IoU associations of buffered boxes.  Same pool blob, same layout and the same entry points as SORT / ByteTrack: y7t_tracker_step, y7t_tracker_step_frames,

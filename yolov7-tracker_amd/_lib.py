@@ -68,6 +68,10 @@ SIGNATURES = {
     "y7t_dhn_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "y7t_tracker_step_deepmot": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "y7t_kf_multi_gmc_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "y7t_ecc_prepare_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "y7t_ecc_workspace_bytes": (c_int, [c_int, c_int, c_void_p]),
+    "y7t_ecc_align": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y7t_ecc_iteration_sums_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "y7t_tracker_layout": (c_int, [c_int, c_int, c_void_p, c_int]),
     "y7t_tracker_field_name": (ctypes.c_char_p, [c_int]),
     "y7t_det_create": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),

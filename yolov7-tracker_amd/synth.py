@@ -8,6 +8,8 @@ benchmark in this repo runs on seeded synthetic sequences:
   `post_process_v7` hands them over (integer-rounded corners, float32;
   /root/reference/tracker/track.py:234-244).
 * `make_frames` -- uint8 BGR frames of VisDrone-like shape for the detector.
+* `make_camera_frames` -- uint8 BGR frames of an analytic textured scene under a moving camera, with the planted
+  per-frame Euclidean warps (the camera-motion estimate's input and ground truth).
 """
 import numpy as np
 
@@ -178,6 +180,64 @@ def make_warps(n_frames=100, seq_idx=0, rot=0.002, shift=2.0):
     H[:, :2, :2] = np.eye(2) + rng.normal(0, rot, (n_frames, 2, 2))
     H[:, :, 2] = rng.normal(0, shift, (n_frames, 2))
     return H
+
+
+# ---- frames under a moving camera (the input of the camera-motion estimate, tracker/gmc.py) ----
+_BG_TERMS = 12
+
+
+def camera_background(x, y, seq_idx=0):
+    """-> (..., 3) float64 BGR levels of the analytic scene of sequence `seq_idx` at the (real-valued) scene coordinates x, y: 128 plus a seeded sum of
+    12 sinusoids with wavelengths of 8 - 200 px, mixed differently into the three channels.  Analytic, so a frame under any warp is EVALUATED, never
+    interpolated."""
+    rng = np.random.default_rng(BASE_SEED + 7000 + seq_idx)
+    lam = np.exp(rng.uniform(np.log(8.0), np.log(200.0), _BG_TERMS))
+    phi = rng.uniform(0.0, np.pi, _BG_TERMS)
+    psi = rng.uniform(0.0, 2.0 * np.pi, _BG_TERMS)
+    mix = rng.uniform(0.5, 1.0, (3, _BG_TERMS)) * np.sqrt(lam / lam.max())[None, :]      # longer waves carry more contrast, like natural footage
+    mix *= 90.0 / mix.sum(axis=1, keepdims=True)                                          # |level - 128| <= 90: no clipping
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    out = np.full(x.shape + (3,), 128.0)
+    for k in range(_BG_TERMS):
+        wave = np.sin((2.0 * np.pi / lam[k]) * (x * np.cos(phi[k]) + y * np.sin(phi[k])) + psi[k])
+        out += wave[..., None] * mix[:, k]
+    return out
+
+
+def euclidean_warp(theta, tx, ty):
+    """-> (2, 3) float64 [[cos, -sin, tx], [sin, cos, ty]]"""
+    c, s = np.cos(theta), np.sin(theta)
+    return np.array([[c, -s, tx], [s, c, ty]], np.float64)
+
+
+def render_camera_frame(size, pose, seq_idx=0):
+    """-> uint8 (H, W, 3) BGR frame whose pixel X shows the scene at pose @ [X, 1] (pose: (2, 3)); size = side or (H, W); levels rounded half up"""
+    H, W = (size, size) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    sx = pose[0, 0] * xs + pose[0, 1] * ys + pose[0, 2]
+    sy = pose[1, 0] * xs + pose[1, 1] * ys + pose[1, 2]
+    return np.clip(np.floor(camera_background(sx, sy, seq_idx) + 0.5), 0, 255).astype(np.uint8)
+
+
+def make_camera_frames(n_frames=8, size=1280, seq_idx=0, rot=0.004, shift=1.5):
+    """-> (frames uint8 (n_frames, H, W, 3) BGR, warps float64 (n_frames, 2, 3)): the analytic scene of camera_background seen by a camera that moves by a
+    seeded Euclidean step per frame (rotation ~ N(0, rot) rad, translation ~ N(0, shift) px, clipped at 2 sigma).  warps[t] is the PLANTED motion from frame
+    t - 1 to frame t in full-resolution pixel coordinates -- frame_t(warps[t] @ [X, 1]) shows what frame_{t-1}(X) shows, which is the matrix GMC.apply
+    estimates (template = previous frame) -- and warps[0] is the identity.  size = side or (H, W)."""
+    rng = np.random.default_rng(BASE_SEED + 7500 + seq_idx)
+    pose = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])      # frame pixel -> scene
+    frames, warps = [], np.zeros((n_frames, 2, 3))
+    for t in range(n_frames):
+        if t == 0:
+            step = np.eye(3)
+        else:
+            th = float(np.clip(rng.normal(0.0, rot), -2 * rot, 2 * rot))
+            tr = np.clip(rng.normal(0.0, shift, 2), -2 * shift, 2 * shift)
+            step = np.vstack([euclidean_warp(th, tr[0], tr[1]), [0.0, 0.0, 1.0]])
+        warps[t] = step[:2]
+        pose = pose @ np.linalg.inv(step)                                        # pose_t = pose_{t-1} W_t^-1
+        frames.append(render_camera_frame(size, pose[:2], seq_idx))
+    return np.stack(frames), warps
 
 
 # ---- the Deep Hungarian Net of DeepMOT (/root/reference/tracker/deepmot.py:10-140, class Munkrs) ----

@@ -4,13 +4,24 @@ botsort.py:250-269) and BoT-SORT's association variant -- including its two quir
 Tracked ones, goes to the low-score association, botsort.py:411; new tracks are spawned from the detections left after the
 FIRST association, botsort.py:462-466).
 
-Out of scope: the camera-motion ESTIMATION (`GMC`, OpenCV ORB / RANSAC, botsort.py:13-248) and the ReID
-appearance branch (off by default in the reference too: use_apperance_model = False).  The 2x3 warp of a frame is an input:
-`update(dets, img, warp=H)` or a user-supplied `tracker.gmc = callable(raw_frame, detections) -> H`."""
+The camera-motion ESTIMATION (`GMC`, botsort.py:13-248) is tracker/gmc.py for method 'ecc' (findTransformECC as HIP kernels); ORB / SIFT matching and the
+GMC files stay out of scope, and so does the ReID appearance branch (off by default in the reference too: use_apperance_model = False).  The 2x3 warp of a
+frame is an input: `update(dets, img, warp=H)` or `tracker.gmc = callable(raw_frame, detections) -> H`, e.g. `GMC('ecc').apply_device`, whose (6,) float64
+DEVICE tensor goes to the step without a host copy.  `tracker.gmc` is None by default, as before."""
 import numpy as np
 import torch
 
 from .basetrack import BaseTracker, STrack, TrackState, joint_stracks, sub_stracks  # noqa: F401
+
+
+def _device_warp(warp, buf):
+    """the frame's 2x3 matrix as a (6,) float64 device tensor: an estimator's CUDA tensor as it is (no host copy), anything else through `buf`"""
+    if isinstance(warp, torch.Tensor) and warp.is_cuda:
+        return warp.to(torch.float64).reshape(6).contiguous()
+    if isinstance(warp, torch.Tensor):
+        warp = warp.detach().numpy()
+    buf.copy_(torch.as_tensor(np.ascontiguousarray(warp, dtype=np.float64).reshape(6)), non_blocking=True)
+    return buf
 
 
 class BoTSORT(BaseTracker):
@@ -37,12 +48,11 @@ class BoTSORT(BaseTracker):
         if warp is None and self.use_GMC and not BoTSORT._warned:
             import warnings
             warnings.warn("BoTSORT: use_GMC is set but no camera-motion matrix was supplied (update(..., warp=H) or tracker.gmc = callable): "
-                          "the reference estimates one per frame with OpenCV (botsort.py:13-248, out of scope here); running WITHOUT "
+                          "the reference estimates one per frame with OpenCV (botsort.py:13-248; tracker.gmc = GMC('ecc').apply_device does it here); running WITHOUT "
                           "compensation, results on moving-camera footage will differ from the reference", RuntimeWarning)
             BoTSORT._warned = True
         w = None
         if warp is not None and self.use_GMC:
-            self._warp.copy_(torch.as_tensor(np.ascontiguousarray(warp, dtype=np.float64).reshape(6)), non_blocking=True)
-            w = self._warp
+            w = self._warp_keep = _device_warp(warp, self._warp)      # (alive until the step has run)
         self._launch(det_results, warp=w)
         return self._collect()

@@ -7,8 +7,9 @@ The reference's quirks are kept: the second association's unmatched indices, whi
 to strack_pool (strongsort.py:195-198); re_activate keeps the appearance vector; a new track starts with the detection's raw vector.
 
 Seams, as in the reference: `get_feature(tlbrs, ori_img) -> (N, D)` (strongsort.py:66-89: crops resized to width 256, height 128 -> OSNet x0.25) and
-the camera motion, shaped like BoTSORT's: `update(dets, img, warp=H)` or `tracker.ECC = object with apply(raw_frame, detections) -> (2, 3)`.  The ECC
-estimation itself (OpenCV findTransformECC, botsort.py:13-248) is out of scope.  matching_thresh, num_of_budget, use_AFLink and use_GSI are never
+the camera motion, shaped like BoTSORT's: `update(dets, img, warp=H)` or `tracker.ECC = object with apply(raw_frame, detections) -> (2, 3)` (or a (6,)
+CUDA tensor, which goes to the step without a host copy).  The ECC estimation itself (findTransformECC, botsort.py:78-109) is tracker/gmc.py:
+`tracker.ECC = GMC('ecc')`; `ECC` is None by default, as before.  matching_thresh, num_of_budget, use_AFLink and use_GSI are never
 read by the reference and do nothing here either."""
 import ctypes
 import os
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .botsort import _device_warp
 from .basetrack import BaseTracker, STrack, TrackState, _PoolTrack, joint_stracks, sub_stracks, remove_duplicate_stracks  # noqa: F401
 
 REID_SIZE = (256, 128)      # (W, H): cv2.resize(..., dsize=(256, 128)), strongsort.py:56
@@ -174,13 +176,12 @@ class StrongSORT(BaseTracker):
         if warp is None and self.use_ECC and not StrongSORT._warned:
             import warnings
             warnings.warn("StrongSORT: use_ECC is set but no camera-motion matrix was supplied (update(..., warp=H) or tracker.ECC = object with "
-                          "apply(raw_frame, detections)): the reference estimates one per frame with OpenCV (botsort.py:13-248, out of scope here); "
+                          "apply(raw_frame, detections), e.g. tracker/gmc.py's GMC('ecc')): the reference estimates one per frame with OpenCV (botsort.py:13-248); "
                           "running WITHOUT compensation, results on moving-camera footage will differ from the reference", RuntimeWarning)
             StrongSORT._warned = True
         w = None
         if warp is not None and self.use_ECC:
-            self._warp.copy_(torch.as_tensor(np.ascontiguousarray(warp, dtype=np.float64).reshape(6)), non_blocking=True)
-            w = self._warp
+            w = _device_warp(warp, self._warp)
         d = torch.from_numpy(det_host).cuda()
         allf = torch.zeros((max(n, 1), self._feat_dim), dtype=torch.float32, device="cuda")
         if feats is not None:

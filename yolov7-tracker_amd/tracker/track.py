@@ -6,7 +6,8 @@ device-resident SORT / ByteTrack trackers.
     python tracker/track.py --dataset synthetic --tracker bytetrack --model_path random:yolov7-w6 --synthetic_dets
 
 Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / arch name for state-dict checkpoints),
---nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch.
+--nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch,
+--gmc {none,ecc} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
 """
 import argparse
 import os
@@ -89,6 +90,8 @@ def main(opts, cfgs):
         opts.kalman_format = 'botsort'      # track.py:68-69
     elif opts.tracker == 'strongsort':
         opts.kalman_format = 'strongsort'   # track.py:70-71
+    if opts.gmc != 'none' and opts.tracker not in ('strongsort', 'botsort'):
+        raise ValueError("--gmc %s: only strongsort and botsort compensate camera motion (tracker %r does not)" % (opts.gmc, opts.tracker))
     img_size = opts.img_size[0] if isinstance(opts.img_size, (list, tuple)) else opts.img_size
     model = attempt_load(opts.model_path, cfg=opts.model_cfg, nc=opts.nc, img_size=img_size, max_batch=max(1, opts.batch))
     stride = int(model.stride.max())
@@ -106,7 +109,7 @@ def main(opts, cfgs):
         print(f'--------------tracking seq {seq}--------------')
         if synthetic:
             loader = tracker_dataloader.SyntheticLoader(opts.synthetic_frames, opts.synthetic_objs, opts.img_size, si,
-                                                        device_preprocess=opts.device_preprocess)
+                                                        device_preprocess=opts.device_preprocess, moving_camera=opts.gmc != 'none')
         else:
             # track.py:126: the sequence folder ('origin') or the path file every sequence is filtered out of ('yolo')
             path = os.path.join(DATA_ROOT, seq) if opts.data_format == 'origin' else os.path.join(getattr(opts, 'yolo_root', './'), opts.dataset, 'test.txt')
@@ -116,6 +119,13 @@ def main(opts, cfgs):
                                                       yolo_data_root=cfgs.get('YOLO_DATA_ROOT', DATASET_ROOT))
         data_loader = torch.utils.data.DataLoader(loader, batch_size=max(1, opts.batch))
         tracker = TRACKER_DICT[opts.tracker](opts, frame_rate=30, gamma=opts.gamma)
+        if opts.gmc == 'ecc':      # (extension) estimate the camera motion on the device; one estimator per sequence, like the reference's per-tracker GMC
+            from .gmc import GMC
+            estimator = GMC('ecc', faithful=bool(opts.gmc_faithful))
+            if opts.tracker == 'strongsort':
+                tracker.ECC = estimator
+            else:
+                tracker.gmc = estimator.apply_device
         results, frame_id, i = [], 0, -1
         for imgs, imgs0 in data_loader:
             # --batch N (extension, default 1 = the reference's frame-at-a-time loop): the detector + decode/NMS run once over N
@@ -213,6 +223,11 @@ def build_parser():
     parser.add_argument('--kalman_format', type=str, default='default', help='use what kind of Kalman, default, naive, strongsort or bot-sort like')
     parser.add_argument('--batch', type=int, default=1, help='(extension) frames per detector forward; the tracker still steps frame by frame')
     parser.add_argument('--device_preprocess', action='store_true', help='(extension) letterbox raw frames on the GPU instead of in the loader')
+    parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc'],
+                        help='(extension) camera-motion estimate for strongsort / botsort: ecc = findTransformECC on the device (tracker/gmc.py)')
+    parser.add_argument('--gmc_faithful', type=int, default=1, choices=[0, 1],
+                        help="(extension) 1 = the reference's applyEcc as written (every frame aligned to frame 0, half-resolution translation); "
+                             "0 = previous-frame template, full-resolution translation")
     parser.add_argument('--min_area', type=float, default=150, help='use to filter small bboxs')
     parser.add_argument('--save_images', action='store_true', help='save tracking results (image)')
     parser.add_argument('--save_videos', action='store_true', help='save tracking results (video)')

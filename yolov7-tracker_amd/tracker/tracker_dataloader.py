@@ -105,10 +105,13 @@ class SyntheticLoader(torch.utils.data.Dataset):
     """seeded synthetic sequence: frames rendered by synth.make_frames, plus the scene's detections (used as the
     tracker's input with --synthetic_dets, since random detector weights do not detect anything meaningful)."""
 
-    def __init__(self, n_frames, n_obj, size, seq_idx, device_preprocess=False):
+    def __init__(self, n_frames, n_obj, size, seq_idx, device_preprocess=False, moving_camera=False):
         from .. import synth
         self.device_preprocess = device_preprocess
-        self.frames = synth.make_frames(n_frames, n_obj, size, seq_idx)
+        if moving_camera:      # a textured scene under a moving camera (synth.make_camera_frames): what a camera-motion estimate needs to see
+            self.frames, self.warps = synth.make_camera_frames(n_frames, size, seq_idx)
+        else:
+            self.frames = synth.make_frames(n_frames, n_obj, size, seq_idx)
         self.dets = synth.make_detections(n_frames, n_obj, size, seq_idx)
 
     def __getitem__(self, i):
