@@ -1,6 +1,13 @@
-"""tests/_hostsim -- TEST INFRASTRUCTURE ONLY: CPU build (nt = 1) of the portable tracker
-workgroup programs, so their control flow can be tested without a GPU.  Never imported by the
-product package."""
+"""tests/_hostsim -- TEST INFRASTRUCTURE ONLY: CPU builds (g++, -ffp-contract=off) of device code, so that its control flow and pinned arithmetic can be
+tested without a GPU.  Never imported by the product package.
+
+  liby7t_hostsim*.so  (y7t_hostsim.cpp)      the portable tracker workgroup programs of csrc/y7t_track_*.h at nt = 1, every tracker kind: bound here (`lib()`);
+                                              HostSimTracker below, HostStrongSORT in strongsort.py, HostDeepMOT in deepmot.py
+  liby7t_hostsim_ecc.so (y7t_hostsim_ecc.cpp) the ECC kernel bodies of csrc/y7t_ecc.h (they share no code with the tracker programs): bound in ecc.py
+
+Y7T_HOSTSIM_DEFS="-DY7T_NEXT_TRACKER=1": a second tracker library with experimental macros of the headers switched on (the tests then run against it).
+Y7T_HOSTSIM_FAST_BYTES: the workgroup's fast scratch -- 131072 bytes by default, like the device's LDS budget (csrc/y7t_tracker.hip: kFastBytes), so the placement
+branches taken here are the ones the GPU takes; 0 runs everything out of the state blob (the other branches), any other value sizes it."""
 import ctypes
 import os
 import subprocess
@@ -8,20 +15,37 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# Y7T_HOSTSIM_DEFS="-DY7T_NEXT_TRACKER=1": a second library with experimental macros of the headers switched on (the tests then run against it)
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "yolov7-tracker_amd", "csrc")
 _DEFS = os.environ.get("Y7T_HOSTSIM_DEFS", "").split()
 _SO = os.path.join(_HERE, "liby7t_hostsim%s.so" % ("_" + "".join(c for c in "".join(_DEFS) if c.isalnum()) if _DEFS else ""))
-_SRC = os.path.join(_HERE, "y7t_hostsim.cpp")
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "yolov7-tracker_amd", "csrc")
+_SO_ECC = os.path.join(_HERE, "liby7t_hostsim_ecc.so")
+FAST_BYTES = 131072
+
+
+def _build(so, src, deps, defs=(), force=False):
+    """compile tests/_hostsim/<src> into <so> when it is older than the source or one of the csrc headers `deps`"""
+    src = os.path.join(_HERE, src)
+    deps = [src] + [os.path.join(_CSRC, h) for h in deps]
+    if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + list(defs) + ["-o", so, src])
+    return so
+
+
+def reset_fast_bytes():
+    """the fast scratch back to what the environment asks for (after a test that ran with another size)"""
+    ctypes.CDLL(_SO).hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", str(FAST_BYTES))))
+
+
+def build_ecc(force=False):
+    return _build(_SO_ECC, "y7t_hostsim_ecc.cpp", ["y7t_ecc.h"], force=force)
 
 
 def build(force=False):
-    deps = [_SRC, os.path.join(_CSRC, "y7t_track_core.h"), os.path.join(_CSRC, "y7t_track_step.h"), os.path.join(_CSRC, "y7t_track_deepsort.h")]
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + _DEFS + ["-o", _SO, _SRC])
-    # the workgroup's fast scratch: 131072 bytes like the device's LDS budget (csrc/y7t_tracker.hip: kFastBytes), so the placement branches taken here are
-    # the ones the GPU takes; Y7T_HOSTSIM_FAST_BYTES=0 runs everything out of the state blob (the other branches), any other value sizes it
-    ctypes.CDLL(_SO).hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", "131072")))
+    """both libraries -> the path of the tracker programs'"""
+    build_ecc(force)
+    _build(_SO, "y7t_hostsim.cpp", ["y7t_track_core.h", "y7t_track_step.h", "y7t_track_cbiou.h", "y7t_track_deepsort.h", "y7t_track_strongsort.h", "y7t_track_deepmot.h"],
+           _DEFS, force)
+    reset_fast_bytes()
     return _SO
 
 
@@ -32,30 +56,50 @@ def lib():
     global _lib
     if _lib is None:
         L = ctypes.CDLL(build())
-        L.hs_tracker_bytes.restype = ctypes.c_size_t
-        L.hs_tracker_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.hs_tracker_init.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_double] * 3 + [ctypes.c_void_p]
-        L.hs_tracker_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.hs_kf_gmc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.hs_tracker_status.argtypes = [ctypes.c_void_p]
-        L.hs_arena_begin.argtypes = [ctypes.c_void_p]
-        L.hs_arena_end.argtypes = [ctypes.c_void_p]
-        L.hs_lapjv.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        vp, ci, cd, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
+        L.hs_tracker_bytes.restype = sz
+        L.hs_tracker_bytes.argtypes = [ci, ci]
+        L.hs_tracker_init.argtypes = [vp] + [ci] * 6 + [cd] * 3 + [vp]
+        L.hs_tracker_step.argtypes = [vp, vp, ci, vp, ci, vp]
+        L.hs_kf_gmc.argtypes = [vp, vp, vp]
+        L.hs_tracker_status.argtypes = [vp]
+        L.hs_arena_begin.argtypes = [vp]
+        L.hs_arena_end.argtypes = [vp]
+        L.hs_lapjv.argtypes = [vp, ci, ci, cd, vp, vp]
         L.hs_lapsap.argtypes = L.hs_lapjv.argtypes
         L.hs_laplit.argtypes = L.hs_lapjv.argtypes
-        L.hs_iou_cost.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.hs_kf_initiate.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.hs_kf_predict.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.hs_kf_update.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]
-        L.hs_kf_project.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
-        L.hs_kf_gating.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        L.hs_kf_gating.restype = ctypes.c_double
-        L.hs_feat_bytes.restype = ctypes.c_size_t
-        L.hs_feat_bytes.argtypes = [ctypes.c_int] * 4
-        L.hs_feat_init.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4
-        L.hs_deepsort_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        L.hs_feat_status.argtypes = [ctypes.c_void_p]
-        L.hs_pyset_difference.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.hs_iou_cost.argtypes = [vp, ci, vp, ci, vp]
+        L.hs_kf_initiate.argtypes = [ci, vp, ci, vp, vp]
+        L.hs_kf_predict.argtypes = [ci, vp, vp]
+        L.hs_kf_update.argtypes = [ci, vp, vp, vp, cd]
+        L.hs_kf_project.argtypes = [ci, vp, vp, cd, vp, vp]
+        L.hs_kf_gating.argtypes = [ci, vp, vp, vp, ci]
+        L.hs_kf_gating.restype = cd
+        L.hs_pyset_difference.argtypes = [ci, vp, ci, vp]
+        # DeepSORT
+        L.hs_feat_bytes.restype = sz
+        L.hs_feat_bytes.argtypes = [ci] * 4
+        L.hs_feat_init.argtypes = [vp] + [ci] * 4
+        L.hs_deepsort_step.argtypes = [vp, vp, vp, ci, vp, vp, ci]
+        L.hs_feat_status.argtypes = [vp]
+        # StrongSORT
+        L.hs_ss_feat_bytes.restype = sz
+        L.hs_ss_feat_bytes.argtypes = [ci, ci, ci]
+        L.hs_ss_feat_init.argtypes = [vp, ci, ci, ci, cd]
+        L.hs_strongsort_step.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
+        L.hs_strongsort_predict.argtypes = [vp, vp, ci]
+        L.hs_ss_feat_status.argtypes = [vp]
+        L.hs_ss_vec_offset.restype = sz
+        L.hs_ss_vec_offset.argtypes = [ci, ci, ci]
+        L.hs_ss_cdist.argtypes = [vp, ci, vp, ci, ci, vp]
+        L.hs_ss_ema.argtypes = [vp, vp, ci]
+        L.hs_ss_fuse.restype = cd
+        L.hs_ss_fuse.argtypes = [cd, cd, cd]
+        # DeepMOT
+        L.hs_deepmot_front.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_longlong]
+        L.hs_deepmot_back.argtypes = [vp, vp, vp, ctypes.c_uint, vp, ci]
+        L.hs_dm_ecu_iou.restype = cd
+        L.hs_dm_ecu_iou.argtypes = [vp, vp, cd, ci, ci]
         _lib = L
     return _lib
 
@@ -86,7 +130,7 @@ def lapjv(cost, limit, sap=False, literal=False):
 
 
 class HostSimTracker:
-    TRACKERS = {"sort": 0, "bytetrack": 1, "botsort": 2, "deepsort": 3}
+    TRACKERS = {"sort": 0, "bytetrack": 1, "botsort": 2, "deepsort": 3, "c_biou": 4, "uavmot": 5, "strongsort": 6, "deepmot": 7}      # include/y7t.h: Y7T_TRACKER_<NAME>
     KINDS = {"default": 0, "naive": 1, "botsort": 2, "strongsort": 3}
 
     def __init__(self, kind="bytetrack", conf_thresh=0.2, track_buffer=30, kalman_format="default", iou_thresh=0.5,
@@ -94,7 +138,7 @@ class HostSimTracker:
         self.ids = ids if ids is not None else np.zeros(1, np.int32)
         n = lib().hs_tracker_bytes(cap_t, cap_d)
         self.blob = np.zeros(n, np.uint8)
-        self.cap_t = cap_t
+        self.cap_t, self.cap_d = cap_t, cap_d
         lib().hs_tracker_init(self.blob.ctypes.data, self.TRACKERS[kind], self.KINDS[kalman_format], cap_t, cap_d,
                               int(frame_rate / 30.0 * track_buffer), f32_quirk, conf_thresh, max(0.15, conf_thresh - 0.3),
                               iou_thresh, self.ids.ctypes.data)

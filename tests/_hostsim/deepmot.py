@@ -1,49 +1,23 @@
-"""tests/_hostsim_deepmot -- TEST INFRASTRUCTURE ONLY: tests/_hostsim's CPU build (nt = 1) of the tracker workgroup programs plus DeepMOT's two programs
-(csrc/y7t_track_deepmot.h), so that their control flow and pinned arithmetic can be tested without a GPU.  The Deep Hungarian Net between the two programs is a
-callable the test supplies (the package's fp32 torch module).  Never imported by the product package."""
-import ctypes
-import os
-import subprocess
-
+"""tests/_hostsim/deepmot.py -- TEST INFRASTRUCTURE ONLY: DeepMOT's two programs (csrc/y7t_track_deepmot.h) of the host build.  The Deep Hungarian Net between
+the two programs is a callable the test supplies (the package's fp32 torch module)."""
 import numpy as np
 
-from tests import _hostsim as hs
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "liby7t_hostsim_deepmot.so")
-_SRC = os.path.join(_HERE, "y7t_hostsim_deepmot.cpp")
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "yolov7-tracker_amd", "csrc")
-FAST_BYTES = 131072      # the device's LDS budget for the step's fast scratch (csrc/y7t_tracker.hip: kFastBytes)
+from tests._hostsim import HostSimTracker, lib
 
 
-def build(force=False):
-    deps = [_SRC, os.path.join(os.path.dirname(_HERE), "_hostsim", "y7t_hostsim.cpp")] + \
-           [os.path.join(_CSRC, h) for h in ("y7t_track_core.h", "y7t_track_step.h", "y7t_track_cbiou.h", "y7t_track_deepmot.h")]
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC])      # (tests/_hostsim's flags)
-    return _SO
+_NETS = {}
 
 
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-        L.hs_tracker_bytes.restype = ctypes.c_size_t
-        L.hs_tracker_bytes.argtypes = [ci, ci]
-        L.hs_tracker_init.argtypes = [vp] + [ci] * 6 + [cd] * 3 + [vp]
-        L.hs_tracker_step.argtypes = [vp, vp, ci, vp, ci, vp]
-        L.hs_tracker_status.argtypes = [vp]
-        L.hs_deepmot_front.argtypes = [vp, vp, ci, ci, ci, vp, ctypes.c_longlong]
-        L.hs_deepmot_back.argtypes = [vp, vp, vp, ctypes.c_uint, vp, ci]
-        L.hs_dm_ecu_iou.restype = cd
-        L.hs_dm_ecu_iou.argtypes = [vp, vp, cd, ci, ci]
-        L.hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", str(FAST_BYTES))))
-        _lib = L
-    return _lib
+def torch_net(seed, scale):
+    """the package's torch module with the seeded weights as a numpy -> numpy callable (built once per weight set, never modified)"""
+    import torch
+    from yolov7_tracker_amd import synth
+    from yolov7_tracker_amd.tracker.deepmot import TorchDHN
+    key = (int(seed), float(scale))
+    if key not in _NETS:
+        net = TorchDHN(synth.make_dhn_weights(*key))
+        _NETS[key] = lambda D, _n=net: _n(torch.from_numpy(np.ascontiguousarray(D, np.float32))).numpy()
+    return _NETS[key]
 
 
 def ecu_iou(t_tlwh, d_tlwh, iou_d, img_shape):
@@ -55,12 +29,12 @@ class HostDeepMOT:
     """the DeepMOT pool on the host.  net(D (h, w) float32 numpy) -> (h, w) float32 numpy: the Deep Hungarian Net seam"""
 
     def __init__(self, net, img_shape, conf_thresh=0.2, track_buffer=30, kalman_format="default", frame_rate=30, cap_t=256, cap_d=256, ids=None, f32_quirk=1,
-                 net_cap=None, kind=7):
+                 net_cap=None, kind="deepmot"):
         L = lib()
         self.ids = ids if ids is not None else np.zeros(1, np.int32)
         self.cap_t, self.cap_d, self.net, self.img_shape = cap_t, cap_d, net, img_shape
         self.blob = np.zeros(L.hs_tracker_bytes(cap_t, cap_d), np.uint8)
-        L.hs_tracker_init(self.blob.ctypes.data, kind, hs.HostSimTracker.KINDS[kalman_format], cap_t, cap_d, int(frame_rate / 30.0 * track_buffer), f32_quirk,
+        L.hs_tracker_init(self.blob.ctypes.data, HostSimTracker.TRACKERS[kind], HostSimTracker.KINDS[kalman_format], cap_t, cap_d, int(frame_rate / 30.0 * track_buffer), f32_quirk,
                           conf_thresh, max(0.15, conf_thresh - 0.3), 0.5, self.ids.ctypes.data)
         self.net_cap = cap_t * cap_d if net_cap is None else net_cap
         self.D = np.zeros(max(self.net_cap, 1), np.float32)

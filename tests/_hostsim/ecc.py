@@ -1,23 +1,11 @@
-"""tests/_hostsim_ecc -- TEST INFRASTRUCTURE ONLY: a CPU build (g++, -ffp-contract=off) of the ECC kernel bodies of csrc/y7t_ecc.h -- the per-pixel programs of
-the prepare and the iteration launch one "lane" at a time, the slab combine and the 3x3 solve, with the device's reduction order -- so that the camera-motion
-estimate can be tested without a GPU.  Never imported by the product package."""
+"""tests/_hostsim/ecc.py -- TEST INFRASTRUCTURE ONLY: the ECC kernel bodies of csrc/y7t_ecc.h of the host build -- the per-pixel programs of the prepare and the
+iteration launch one "lane" at a time, the slab combine and the 3x3 solve, with the device's reduction order -- so that the camera-motion estimate can be tested
+without a GPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "liby7t_hostsim_ecc.so")
-_SRC = os.path.join(_HERE, "y7t_hostsim_ecc.cpp")
-_HDR = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "yolov7-tracker_amd", "csrc", "y7t_ecc.h")
-
-
-def build(force=False):
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(_SRC), os.path.getmtime(_HDR)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC])      # (tests/_hostsim's flags)
-    return _SO
-
+from tests._hostsim import build_ecc
 
 _lib = None
 
@@ -25,7 +13,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        L = ctypes.CDLL(build())
+        L = ctypes.CDLL(build_ecc())
         vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.hs_ecc_ws_bytes.restype = ctypes.c_size_t
         L.hs_ecc_ws_bytes.argtypes = [ci, ci]

@@ -1,57 +1,8 @@
-"""tests/_hostsim_strongsort -- TEST INFRASTRUCTURE ONLY: tests/_hostsim's CPU build (nt = 1) of the tracker workgroup programs plus the StrongSORT
-program (csrc/y7t_track_strongsort.h), so that its control flow and its pinned arithmetic can be tested without a GPU.  Never imported by the product
-package."""
-import ctypes
-import os
-import subprocess
-
+"""tests/_hostsim/strongsort.py -- TEST INFRASTRUCTURE ONLY: the StrongSORT program (csrc/y7t_track_strongsort.h) of the host build: the plain forms of the frame's
+three launches at nt = 1, and its pinned arithmetic on its own."""
 import numpy as np
 
-from tests import _hostsim as hs
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "liby7t_hostsim_strongsort.so")
-_SRC = os.path.join(_HERE, "y7t_hostsim_strongsort.cpp")
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "yolov7-tracker_amd", "csrc")
-FAST_BYTES = 131072      # the device's LDS budget for the step's fast scratch (csrc/y7t_tracker.hip: kFastBytes)
-
-
-def build(force=False):
-    deps = [_SRC, os.path.join(os.path.dirname(_HERE), "_hostsim", "y7t_hostsim.cpp")] + \
-           [os.path.join(_CSRC, h) for h in ("y7t_track_core.h", "y7t_track_step.h", "y7t_track_cbiou.h", "y7t_track_deepsort.h", "y7t_track_strongsort.h")]
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC])      # (tests/_hostsim's flags)
-    return _SO
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-        L.hs_tracker_bytes.restype = ctypes.c_size_t
-        L.hs_tracker_bytes.argtypes = [ci, ci]
-        L.hs_tracker_init.argtypes = [vp] + [ci] * 6 + [cd] * 3 + [vp]
-        L.hs_tracker_step.argtypes = [vp, vp, ci, vp, ci, vp]
-        L.hs_tracker_status.argtypes = [vp]
-        L.hs_ss_feat_bytes.restype = ctypes.c_size_t
-        L.hs_ss_feat_bytes.argtypes = [ci, ci, ci]
-        L.hs_ss_feat_init.argtypes = [vp, ci, ci, ci, cd]
-        L.hs_strongsort_step.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp]
-        L.hs_strongsort_predict.argtypes = [vp, vp, ci]
-        L.hs_ss_feat_status.argtypes = [vp]
-        L.hs_ss_vec_offset.restype = ctypes.c_size_t
-        L.hs_ss_vec_offset.argtypes = [ci, ci, ci]
-        L.hs_ss_cdist.argtypes = [vp, ci, vp, ci, ci, vp]
-        L.hs_ss_ema.argtypes = [vp, vp, ci]
-        L.hs_ss_fuse.restype = cd
-        L.hs_ss_fuse.argtypes = [cd, cd, cd]
-        L.hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", str(FAST_BYTES))))
-        _lib = L
-    return _lib
+from tests._hostsim import HostSimTracker, lib
 
 
 def cdist(u, v):
@@ -78,7 +29,7 @@ class HostStrongSORT:
         self.ids = ids if ids is not None else np.zeros(1, np.int32)
         self.cap_t, self.cap_d, self.dim, self.feature_fn, self.conf = cap_t, cap_d, feat_dim, feature_fn, conf_thresh
         self.blob = np.zeros(L.hs_tracker_bytes(cap_t, cap_d), np.uint8)
-        L.hs_tracker_init(self.blob.ctypes.data, 6, hs.HostSimTracker.KINDS[kalman_format], cap_t, cap_d, int(frame_rate / 30.0 * track_buffer), f32_quirk,
+        L.hs_tracker_init(self.blob.ctypes.data, HostSimTracker.TRACKERS["strongsort"], HostSimTracker.KINDS[kalman_format], cap_t, cap_d, int(frame_rate / 30.0 * track_buffer), f32_quirk,
                           conf_thresh, max(0.15, conf_thresh - 0.3), 0.5, self.ids.ctypes.data)
         self.fcap_t, self.fcap_d = feat_cap_t or cap_t, feat_cap_d or cap_d
         self.fblob = np.zeros(L.hs_ss_feat_bytes(self.fcap_t, self.fcap_d, feat_dim), np.uint8)

@@ -9,8 +9,12 @@ static int g_tie_reason[8] = {0};
 #define Y7T_TIE_REASON(k) (++g_tie_reason[k])
 static int g_next_stat[4] = {0};
 #define Y7T_NEXT_STAT(k) (++g_next_stat[k])
+static int g_ss_stat[4] = {0};      // fused associations solved by the sparse component solver / densely after it declined / densely after a tie / densely (small problems)
+#define Y7T_SS_STAT(k) (++g_ss_stat[k])
 #include "../../yolov7-tracker_amd/csrc/y7t_track_step.h"
 #include "../../yolov7-tracker_amd/csrc/y7t_track_deepsort.h"
+#include "../../yolov7-tracker_amd/csrc/y7t_track_strongsort.h"
+#include "../../yolov7-tracker_amd/csrc/y7t_track_deepmot.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -138,4 +142,49 @@ int hs_pyset_difference(int n, const int* member, int n_other, int* out) {
     free(tab);
     return st ? -1 : c;
 }
+
+// ---- StrongSORT (y7t_track_strongsort.h): the plain forms of the frame's three launches (appearance distances, the step, the queued vector stores) ----
+size_t hs_ss_feat_bytes(int cap_t, int cap_d, int dim) { return y7t_ss_layout(cap_t, cap_d, dim).total; }
+void hs_ss_feat_init(void* fblob, int cap_t, int cap_d, int dim, double gamma) { y7t_ss_init(hs_ex(), fblob, cap_t, cap_d, dim, gamma); }
+int hs_strongsort_step(void* blob, void* fblob, const float* dets, int n, const float* feats, double* out_rows, int out_cap, const double* warp) {
+    int cnt = 0;
+    const Y7TExec ex = hs_ex();
+    Y7TTrkHdr* h = (Y7TTrkHdr*)blob;
+    const Y7TTrk s = y7t_trk_bind(blob, h->cfg.cap_t, h->cfg.cap_d);
+    const Y7TSs f = y7t_ss_bind(fblob);
+    y7t_ss_appearance_plain(ex, s, f, dets, feats, n);
+    y7t_tracker_step_strongsort(ex, blob, fblob, dets, n, feats, out_rows, out_cap, &cnt, warp);
+    y7t_ss_store_pending(ex, f, feats);
+    return cnt;
+}
+int hs_strongsort_predict(void* blob, double* out_rows, int out_cap) {      // update_without_detection: the program's predict-only form, no feature state
+    int cnt = 0;
+    y7t_tracker_step_strongsort(hs_ex(), blob, nullptr, nullptr, -1, nullptr, out_rows, out_cap, &cnt, nullptr);
+    return cnt;
+}
+int hs_ss_feat_status(void* fblob) { return ((Y7TSsHdr*)fblob)->status; }
+int hs_ss_stat(int k) { return g_ss_stat[k]; }
+// the slot's vector (STrack.features[-1]); the byte offset of the vectors for host-side views
+size_t hs_ss_vec_offset(int cap_t, int cap_d, int dim) { return y7t_ss_layout(cap_t, cap_d, dim).vec; }
+// the pieces on their own
+void hs_ss_cdist(const float* u, int nu, const float* v, int nv, int dim, double* out) {
+    for (int i = 0; i < nu; ++i) for (int j = 0; j < nv; ++j) out[(size_t)i * nv + j] = y7t_ss_dist(u + (size_t)i * dim, v + (size_t)j * dim, dim);
+}
+void hs_ss_ema(float* vec, const float* raw, int dim) { y7t_ss_ema(vec, raw, dim); }
+double hs_ss_fuse(double gamma, double iou_d, double app_d) { return y7t_ss_fuse(gamma, iou_d, app_d); }
+
+// ---- DeepMOT (y7t_track_deepmot.h): its two programs; the network between them is evaluated by the caller ----
+// -> rows << 16 | columns of the matrix the network is to run on (0: skipped); D holds it
+int hs_deepmot_front(void* blob, const float* dets, int n, int img_h, int img_w, float* D, long long d_cap) {
+    int hw[2] = {0, 0};
+    y7t_deepmot_front(hs_ex(), blob, dets, n, img_h, img_w, D, d_cap, hw);
+    return (hw[0] << 16) | hw[1];
+}
+int hs_deepmot_back(void* blob, const float* dets, const float* net_out, unsigned net_status, double* out_rows, int out_cap) {
+    int cnt = 0;
+    y7t_deepmot_back(hs_ex(), blob, dets, net_out, &net_status, out_rows, out_cap, &cnt);
+    return cnt;
+}
+// one element of matching.ecu_iou_distance
+double hs_dm_ecu_iou(const double* t_tlwh, const float* d_tlwh, double iou_d, int img_h, int img_w) { return y7t_dm_ecu_iou(t_tlwh, d_tlwh, iou_d, y7t_dm_norm_factor(img_h, img_w)); }
 }

@@ -1,4 +1,4 @@
-// tests/_hostsim_ecc/y7t_hostsim_ecc.cpp -- TEST INFRASTRUCTURE ONLY.
+// tests/_hostsim/y7t_hostsim_ecc.cpp -- TEST INFRASTRUCTURE ONLY.
 // The CPU build of the ECC kernel bodies of yolov7-tracker_amd/csrc/y7t_ecc.h: the per-pixel programs of the prepare and the iteration launch run one "lane" at a
 // time, and the reductions follow the device's order (per lane over its pixels; the shuffle tree of the 64 lanes of a wave; the waves of a workgroup in order;
 // the workgroups' slabs in the order of y7t_ecc_combine), so that the sums and the warp can be compared with the device's bit for bit.  The product package never loads this library.

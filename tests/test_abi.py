@@ -32,6 +32,14 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert s in syms, "%s bound in _lib.py but not declared in include/y7t.h" % s
 
 
+def test_hostsim_tracker_kinds_are_the_header_enumerators():
+    """the names by which the host build (tests/_hostsim) selects a tracker program are the Y7T_TRACKER_* enumerators of include/y7t.h, by value"""
+    from tests._hostsim import HostSimTracker
+    txt = open(os.path.join(ROOT, "include", "y7t.h")).read()
+    enum = {name.lower(): int(v) for name, v in re.findall(r"\bY7T_TRACKER_([A-Z_]+)\s*=\s*(\d+)", txt)}
+    assert len(enum) == 8 and HostSimTracker.TRACKERS == enum
+
+
 def test_version_and_error_string(lib):
     assert lib.y7t_version() >= 100
     assert isinstance(lib.y7t_last_error(), bytes)

@@ -1,97 +1,33 @@
 """C-BIoU without a GPU: the CPU build of the tracker workgroup programs (tests/_hostsim) with tracker kind 4 against the reference's golden vectors
 (tests/golden/tracker_c_biou_*.npz, tests/golden/make_golden_c_biou.py) and, where the reference sources exist, against the live reference on random
 scenes; the port's matching.buffered_iou_distance against the reference's."""
-import ctypes
-import os
+import functools
 
 import numpy as np
 import pytest
 
 from tests import _hostsim as hs
+from tests import tracker_case as tc
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = ["default", "bounce", "misses", "crowd", "empty", "conf04"]
-LIB = os.path.join(os.path.dirname(GOLDEN), "..", "yolov7-tracker_amd", "lib", "liby7t.so")
-
-
-class CBHost(hs.HostSimTracker):
-    TRACKERS = dict(hs.HostSimTracker.TRACKERS, c_biou=4)
+NAMES = tc.NAMES["c_biou"]
+load_golden = functools.partial(tc.load_golden, "c_biou")
 
 
-def load_golden(name):
-    g = np.load(os.path.join(GOLDEN, "tracker_c_biou_%s.npz" % name))
-    off = np.concatenate([[0], np.cumsum(g["det_counts"])])
-    dets = [g["dets"][off[i]:off[i + 1]] for i in range(len(g["det_counts"]))]
-
-    def split(counts, flat):
-        o = np.concatenate([[0], np.cumsum(counts)])
-        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
-    frames = []
-    for f in range(len(dets)):
-        sel = g["frame"] == f
-        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
-    return dict(dets=dets, frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]), lost=split(g["lost_counts"], g["lost_ids"]),
-                conf=float(g["conf_thresh"]))
-
-
-_LAYOUT = {}
-
-
-def layout(cap_t, cap_d):
-    """byte offsets of the pool blob's fields (the product library's y7t_tracker_layout: host code, no device needed)"""
-    if (cap_t, cap_d) not in _LAYOUT:
-        L = ctypes.CDLL(LIB)
-        L.y7t_tracker_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-        L.y7t_tracker_field_name.restype = ctypes.c_char_p
-        n = L.y7t_tracker_layout(cap_t, cap_d, None, 0)
-        offs = (ctypes.c_int64 * n)()
-        L.y7t_tracker_layout(cap_t, cap_d, offs, n)
-        _LAYOUT[(cap_t, cap_d)] = {L.y7t_tracker_field_name(i).decode(): int(offs[i]) for i in range(n)}
-    return _LAYOUT[(cap_t, cap_d)]
-
-
-def id_lists(trk):
-    """-> (ids of the tracked list, ids of the lost list) of a host pool, in list order"""
-    lo, b = layout(trk.cap_t, 1024), trk.blob
-    i32 = lambda off, n: b[off:off + 4 * n].view(np.int32)      # noqa: E731
-    tid = i32(lo["tid"], trk.cap_t)
-    nt, nl = int(i32(lo["hdr_n_tracked"], 1)[0]), int(i32(lo["hdr_n_lost"], 1)[0])
-    return tid[i32(lo["tracked"], nt)].tolist(), tid[i32(lo["lost"], nl)].tolist()
-
-
-def replay(dets, conf, arena_frames=0, want=None):
-    """run the host build over `dets`; with `want` (golden / reference frames) compare every frame"""
-    trk = CBHost("c_biou", conf_thresh=conf)
-    got = []
-    for f, d in enumerate(dets):
-        if arena_frames and f % arena_frames == 0:
-            assert hs.lib().hs_arena_begin(trk.blob.ctypes.data)
-        rows = trk.update(d)
-        group_end = not arena_frames or f % arena_frames == arena_frames - 1 or f == len(dets) - 1
-        if arena_frames and group_end:
-            hs.lib().hs_arena_end(trk.blob.ctypes.data)
-        got.append(rows)
-        if want is None:
-            continue
-        ids, tlwh, cls, score = want["frames"][f]
-        assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
-        assert np.array_equal(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh), "frame %d: tlwh" % f
-        assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score)
-        if group_end:      # (inside an arena group the lists live in the arena)
-            assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
-    return got
+def replay(want, arena_frames=0):
+    """the host build over the scene, every frame compared with `want` (a golden / the live reference's frames): tlwh exactly, C-BIoU has no Kalman filter"""
+    return tc.replay_host(hs.HostSimTracker("c_biou", conf_thresh=want["conf"]), want, arena_frames, exact=True)
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_hostsim_c_biou_matches_reference_golden(name):
     g = load_golden(name)
-    replay(g["dets"], g["conf"], want=g)
+    replay(g)
 
 
 @pytest.mark.parametrize("name,frames", [("default", 8), ("misses", 16), ("crowd", 5), ("empty", 3)])
 def test_hostsim_c_biou_with_list_arena_matches_reference_golden(name, frames):
     g = load_golden(name)
-    replay(g["dets"], g["conf"], arena_frames=frames, want=g)
+    replay(g, arena_frames=frames)
 
 
 def test_hostsim_c_biou_misses_golden_exercises_the_buffer():
@@ -103,22 +39,22 @@ def test_hostsim_c_biou_misses_golden_exercises_the_buffer():
 
 def test_hostsim_c_biou_update_without_detection():
     """an empty pool only advances the frame; a non-empty one is refused with Y7T_ERR_PREDICT (16), the state unchanged"""
-    trk = CBHost("c_biou")
+    trk = hs.HostSimTracker("c_biou")
     assert trk.update(None) == []
     assert trk.update(np.zeros((0, 6), np.float32)) == []
     d = np.array([[10, 10, 60, 90, 0.9, 0], [200, 40, 260, 160, 0.8, 1]], np.float32)
     assert len(trk.update(d)) == 0      # frame 3: new tracks, not activated
     assert len(trk.update(d)) == 2
-    lo = layout(trk.cap_t, 1024)
+    lo = tc.layout(trk.cap_t, trk.cap_d)
     frame = lambda: int(trk.blob[lo["hdr_frame_id"]:lo["hdr_frame_id"] + 4].view(np.int32)[0])      # noqa: E731
-    before, lists = frame(), id_lists(trk)
+    before, lists = frame(), tc.id_lists(trk)
     with pytest.raises(RuntimeError, match="status 16"):
         trk.update(None)
-    assert frame() == before == 4 and id_lists(trk) == lists
+    assert frame() == before == 4 and tc.id_lists(trk) == lists
 
 
 def test_hostsim_c_biou_pool_overflow_sets_status():
-    trk = CBHost("c_biou", cap_t=16)
+    trk = hs.HostSimTracker("c_biou", cap_t=16)
     from yolov7_tracker_amd import synth
     with pytest.raises(RuntimeError, match="capacity"):
         for d in synth.make_detections(5, 40, seq_idx=3):
@@ -131,19 +67,11 @@ from oracle import ref_harness  # noqa: E402
 needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference sources not present")
 
 
-def _ref_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_golden_c_biou", os.path.join(GOLDEN, "make_golden_c_biou.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    return mg
-
-
 @needs_ref
 @pytest.mark.parametrize("seed", range(20))
 def test_hostsim_c_biou_matches_live_reference(seed):
     from yolov7_tracker_amd import synth
-    mg = _ref_module()
+    mg = tc.maker("c_biou")
     rng = np.random.default_rng(1000 + seed)
     nf, nobj = int(rng.integers(20, 70)), int(rng.integers(5, 140))
     extra = {"bounce": bool(rng.integers(0, 2)), "miss": float(rng.uniform(0.0, 0.4))}
@@ -152,10 +80,7 @@ def test_hostsim_c_biou_matches_live_reference(seed):
         dets = [np.zeros((0, 6), np.float32) if rng.random() < 0.15 else d for d in dets]
     conf = [0.2, 0.3, 0.4, 0.25][seed % 4]
     ref = mg.run_reference(dets, conf)
-    want = dict(frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
-                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref],
-                tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref])
-    replay(dets, conf, arena_frames=(7 if seed % 2 else 0), want=want)
+    replay(tc.want_from_reference(ref, dets=dets, conf=conf), arena_frames=(7 if seed % 2 else 0))
 
 
 @needs_ref
@@ -166,7 +91,7 @@ def test_buffered_iou_distance_equals_reference(monkeypatch):
     from yolov7_tracker_amd import synth
     from yolov7_tracker_amd.tracker import matching as pm
     from yolov7_tracker_amd.tracker.c_biou_tracker import C_BIoUSTrack
-    mg = _ref_module()
+    mg = tc.maker("c_biou")
     mod = mg.load_c_biou()
     rm = ref_harness.load_tracker().matching
     monkeypatch.setattr(pm, "_cost", lambda a, b: 1 - cnative.bbox_overlaps(np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)))

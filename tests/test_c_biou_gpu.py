@@ -2,8 +2,8 @@
 y7t_tracker_step_batch -- against the reference's golden vectors (tests/golden/tracker_c_biou_*.npz) and the CPU build of the same program; the tracker
 CLI with --tracker c_biou."""
 import ctypes
+import functools
 import os
-import types
 
 import numpy as np
 import pytest
@@ -12,29 +12,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from tests.test_c_biou_cpu import CBHost, NAMES, load_golden  # noqa: E402
+from tests import _hostsim as hs  # noqa: E402
+from tests import tracker_case as tc  # noqa: E402
+from yolov7_tracker_amd.tracker.c_biou_tracker import C_BIoUTracker  # noqa: E402
 
-
-def opts(conf=0.2, threads=0, **kw):
-    o = types.SimpleNamespace(conf_thresh=conf, track_buffer=30, kalman_format="default", img_size=1280, iou_thresh=0.5, tracker_threads=threads)
-    o.__dict__.update(kw)
-    return o
-
-
-def new_tracker(conf=0.2, threads=0, **kw):
-    from yolov7_tracker_amd.tracker.basetrack import BaseTrack
-    from yolov7_tracker_amd.tracker.c_biou_tracker import C_BIoUTracker
-    BaseTrack._count = 0
-    return C_BIoUTracker(opts(conf, threads, **kw), frame_rate=30)
-
-
-def check_frame(g, f, cur, lists=None):
-    ids, tlwh, cls, score = g["frames"][f]
-    assert [t.track_id for t in cur] == ids.tolist(), "frame %d: ids" % f
-    assert np.array_equal(np.array([t.tlwh for t in cur], np.float64).reshape(-1, 4), tlwh), "frame %d: tlwh" % f
-    assert np.array_equal(np.array([t.cls for t in cur], np.float32), cls) and np.array_equal(np.array([t.score for t in cur], np.float32), score)
-    if lists is not None:
-        assert lists == (g["tracked"][f], g["lost"][f]), "frame %d: tracked / lost lists" % f
+NAMES = tc.NAMES["c_biou"]
+load_golden = functools.partial(tc.load_golden, "c_biou")
+new_tracker = functools.partial(tc.new_tracker, C_BIoUTracker)
 
 
 @pytest.mark.parametrize("threads", [64, 256, 1024])
@@ -45,7 +29,7 @@ def test_c_biou_tracker_matches_reference_golden(name, threads):
     for f, d in enumerate(g["dets"]):
         cur = t.update(d, None)
         check = f % 10 == 9 or f == len(g["dets"]) - 1
-        check_frame(g, f, cur, ([x.track_id for x in t.tracked_stracks], [x.track_id for x in t.lost_stracks]) if check else None)
+        tc.check_tracks(cur, g, f, True, ([x.track_id for x in t.tracked_stracks], [x.track_id for x in t.lost_stracks]) if check else None)
 
 
 def test_c_biou_track_views():
@@ -109,7 +93,7 @@ def test_c_biou_batch_with_shared_id_counter_equals_single_runs():
     def mk(ids):
         st = [torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for _ in range(nseq)]
         for s in range(nseq):
-            _lib.check(L.y7t_tracker_init(_lib.ptr(st[s]), nbytes, 4, 0, cap, cap, 0.2, 0.5, 30, 1, _lib.ptr(ids[s]), _lib.stream_ptr()))
+            _lib.check(L.y7t_tracker_init(_lib.ptr(st[s]), nbytes, hs.HostSimTracker.TRACKERS["c_biou"], 0, cap, cap, 0.2, 0.5, 30, 1, _lib.ptr(ids[s]), _lib.stream_ptr()))
         return st
     outs = torch.zeros((nseq, cap + 1, 8), dtype=torch.float64, device="cuda")
     st = mk([torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(nseq)])
@@ -150,7 +134,7 @@ def test_c_biou_batch_with_shared_id_counter_equals_single_runs():
 def test_c_biou_device_equals_host_build_on_crowds(seed):
     from yolov7_tracker_amd import synth
     dets = synth.make_detections(15, 500, seq_idx=90 + seed, miss=0.15, bounce=True)
-    host = CBHost("c_biou")
+    host = hs.HostSimTracker("c_biou")
     t = new_tracker(threads=512)
     for f, d in enumerate(dets):
         want = host.update(d)

@@ -1,73 +1,29 @@
-"""DeepMOT without a GPU: the CPU build of its two workgroup programs (tests/_hostsim_deepmot, nt = 1) with the Deep Hungarian Net between them evaluated by the
+"""DeepMOT without a GPU: the CPU build of its two workgroup programs (tests/_hostsim/deepmot.py, nt = 1) with the Deep Hungarian Net between them evaluated by the
 package's own fp32 torch module, against the reference's golden vectors (tests/golden/tracker_deepmot_*.npz, dhn_*.npz; tests/golden/make_golden_deepmot.py) and,
 where the reference sources exist, against the live reference; the seeded weights, the dhn_path loader, matching.ecu_iou_distance and the CLI surface."""
-import importlib.util
+import functools
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from tests import _hostsim_deepmot as hdm
-from tests import util
-from tests.test_uavmot_cpu import id_lists
+from tests import tracker_case as tc
+from tests._hostsim import deepmot as hdm
 from yolov7_tracker_amd import synth
 from yolov7_tracker_amd.tracker import deepmot as dm
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = ["default", "miss", "conf04", "empty", "gaps", "reject", "crowd"]
-DHN_NAMES = ["1x1", "1x7", "7x1", "3x5", "12x9", "33x20", "64x48"]
-COUNTS = ["first_matches", "first_rejected", "second_matches", "unconfirmed_removed", "reactivated", "quirk_frames"]
-
-
-def maker():
-    spec = importlib.util.spec_from_file_location("make_golden_deepmot", os.path.join(GOLDEN, "make_golden_deepmot.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    return mg
-
-
-_NETS = {}
-
-
-def torch_net(seed, scale):
-    """the package's torch module with the seeded weights as a numpy -> numpy callable (built once per weight set, never modified)"""
-    key = (int(seed), float(scale))
-    if key not in _NETS:
-        net = dm.TorchDHN(synth.make_dhn_weights(*key))
-        _NETS[key] = lambda D, _n=net: _n(torch.from_numpy(np.ascontiguousarray(D, np.float32))).numpy()
-    return _NETS[key]
-
-
-def load_golden(name):
-    g = np.load(os.path.join(GOLDEN, "tracker_deepmot_%s.npz" % name))
-
-    def split(counts, flat):
-        o = np.concatenate([[0], np.cumsum(counts)])
-        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
-    dets = maker().frames_from_golden(g)
-    frames = []
-    for f in range(len(dets)):
-        sel = g["frame"] == f
-        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
-    return dict(dets=dets, frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]), lost=split(g["lost_counts"], g["lost_ids"]), conf=float(g["conf_thresh"]),
-                kalman_format=str(g["kalman_format"]), img_shape=tuple(int(v) for v in g["img_shape"]), seed=int(g["weight_seed"]), scale=float(g["weight_scale"]),
-                counts={k: int(g["count_" + k]) for k in COUNTS}, E=float(g["E"]))
-
-
-def check_rows(rows, want, f):
-    ids, tlwh, cls, score = want["frames"][f]
-    assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
-    np.testing.assert_allclose(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL, err_msg="frame %d: tlwh" % f)
-    assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score), "frame %d" % f
+GOLDEN = tc.GOLDEN
+NAMES = tc.NAMES["deepmot"]
+DHN_NAMES = tc.DHN_NAMES
+COUNTS = tc.DEEPMOT_COUNTS
+load_golden = functools.partial(tc.load_golden, "deepmot")
+maker = functools.partial(tc.maker, "deepmot")
 
 
 def replay(want, **kw):
-    trk = hdm.HostDeepMOT(torch_net(want["seed"], want["scale"]), want["img_shape"], conf_thresh=want["conf"], kalman_format=want["kalman_format"], **kw)
-    for f, d in enumerate(want["dets"]):
-        check_rows(trk.update(d), want, f)
-        assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
+    trk = hdm.HostDeepMOT(hdm.torch_net(want["seed"], want["scale"]), want["img_shape"], conf_thresh=want["conf"], kalman_format=want["kalman_format"], **kw)
+    tc.replay_host(trk, want)
     return trk
 
 
@@ -153,8 +109,8 @@ def test_refusals_and_skipped_network():
     host-side registry), so here: the empty first frame and the frame without high detections skip the network; a network that gave up yields no rows (bit 64);
     a matrix larger than the network's workspace is refused (bit 32)"""
     want = load_golden("default")
-    net = torch_net(want["seed"], want["scale"])
-    other = hdm.HostDeepMOT(net, want["img_shape"], kind=1)
+    net = hdm.torch_net(want["seed"], want["scale"])
+    other = hdm.HostDeepMOT(net, want["img_shape"], kind="bytetrack")
     with pytest.raises(RuntimeError, match="status 8"):
         other.update(want["dets"][0])
     trk = hdm.HostDeepMOT(net, want["img_shape"])
@@ -211,7 +167,4 @@ def test_hostsim_deepmot_matches_live_reference(seed):
     nobj, conf, kform = [6, 14, 10, 8][seed], [0.2, 0.3, 0.4, 0.25][seed], ["default", "botsort", "strongsort", "default"][seed]
     dets = mg.make_scene(10, nobj, 700 + seed, {"miss": 0.15 * (seed % 3)}, 0, 6 if seed == 2 else 0)
     ref = mg.run_reference(dets, mod, conf, kform, 7, 3.0)
-    want = dict(dets=dets, conf=conf, kalman_format=kform, img_shape=mg.IMG_SHAPE, seed=7, scale=3.0, tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref],
-                frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
-                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref])
-    replay(want)
+    replay(tc.want_from_reference(ref, dets=dets, conf=conf, kalman_format=kform, img_shape=mg.IMG_SHAPE, seed=7, scale=3.0))

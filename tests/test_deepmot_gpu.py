@@ -6,6 +6,7 @@ the refusals, the overflows, a shared network object and the tracker CLI with --
 The give-up path of the recurrence's bounded waits is NOT exercised here: nothing may stall a card on purpose.  The CPU tests hand the back program a failed
 status word (tests/test_deepmot_cpu.py)."""
 import ctypes
+import functools
 import os
 import types
 
@@ -17,9 +18,13 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from tests import util  # noqa: E402
-from tests import _hostsim_deepmot as hdm  # noqa: E402
-from tests.test_deepmot_cpu import DHN_NAMES, GOLDEN, NAMES, load_golden, torch_net  # noqa: E402
-from tests.test_uavmot_cpu import id_lists as host_id_lists  # noqa: E402
+from tests import tracker_case as tc  # noqa: E402
+from tests._hostsim import deepmot as hdm  # noqa: E402
+from tests.tracker_case import DHN_NAMES, GOLDEN  # noqa: E402
+from yolov7_tracker_amd.tracker.deepmot import DeepMOT  # noqa: E402
+
+NAMES = tc.NAMES["deepmot"]
+load_golden = functools.partial(tc.load_golden, "deepmot")
 
 _DHN = {}
 
@@ -34,29 +39,8 @@ def device_dhn(seed, scale):
     return _DHN[key]
 
 
-def opts(conf=0.2, threads=0, kalman_format="default", **kw):
-    o = types.SimpleNamespace(conf_thresh=conf, track_buffer=30, kalman_format=kalman_format, img_size=1280, iou_thresh=0.5, tracker_threads=threads, max_tracks=256, max_dets=256)
-    o.__dict__.update(kw)
-    return o
-
-
-def new_tracker(g, threads=0, **kw):
-    from yolov7_tracker_amd.tracker.basetrack import BaseTrack
-    from yolov7_tracker_amd.tracker.deepmot import DeepMOT
-    BaseTrack._count = 0
-    return DeepMOT(opts(g["conf"], threads, g["kalman_format"], **kw), frame_rate=30, dhn=device_dhn(g["seed"], g["scale"]))
-
-
-def id_lists(t):
-    s = t._snapshot()
-    return s["tid"][s["tracked"][:s["hdr_n_tracked"]]].tolist(), s["tid"][s["lost"][:s["hdr_n_lost"]]].tolist()
-
-
-def check_frame(g, f, cur):
-    ids, tlwh, cls, score = g["frames"][f]
-    assert [t.track_id for t in cur] == ids.tolist(), "frame %d: ids" % f
-    np.testing.assert_allclose(np.array([t.tlwh for t in cur], np.float64).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL, err_msg="frame %d: tlwh" % f)
-    assert np.array_equal(np.array([t.cls for t in cur], np.float32), cls) and np.array_equal(np.array([t.score for t in cur], np.float32), score), "frame %d" % f
+def new_tracker(g, threads=0, max_tracks=256, max_dets=256, **kw):
+    return tc.new_tracker(DeepMOT, g["conf"], threads, g["kalman_format"], ctor=dict(dhn=device_dhn(g["seed"], g["scale"])), max_tracks=max_tracks, max_dets=max_dets, **kw)
 
 
 def step(t, g, f):
@@ -106,28 +90,26 @@ def test_deepmot_tracker_matches_reference_golden(name, threads):
     g = load_golden(name)
     t = new_tracker(g, threads)
     for f in range(len(g["dets"])):
-        check_frame(g, f, step(t, g, f))
-        assert id_lists(t) == (g["tracked"][f], g["lost"][f]), "frame %d: tracked / lost lists" % f
+        tc.check_tracks(step(t, g, f), g, f, False, tc.id_lists(t))
 
 
 def test_two_trackers_share_one_network_object():
     ga, gb = load_golden("default"), load_golden("miss")
-    from yolov7_tracker_amd.tracker.deepmot import DeepMOT
     ta = new_tracker(ga)
-    tb = DeepMOT(opts(gb["conf"], 0, gb["kalman_format"]), frame_rate=30, dhn=ta.DHN)
+    tb = DeepMOT(tc.opts(gb["conf"], 0, gb["kalman_format"], max_tracks=256, max_dets=256), frame_rate=30, dhn=ta.DHN)
     # the id counter is shared by the trackers of a process: compare the lists' sizes and the boxes, frame by frame, interleaved
     for f in range(12):
         ca, cb = step(ta, ga, f), step(tb, gb, f)
         for g, cur in ((ga, ca), (gb, cb)):
             np.testing.assert_allclose(np.array([t.tlwh for t in cur], np.float64).reshape(-1, 4), g["frames"][f][1], rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL)
-        assert [len(x) for x in id_lists(ta)] == [len(ga["tracked"][f]), len(ga["lost"][f])] and [len(x) for x in id_lists(tb)] == [len(gb["tracked"][f]), len(gb["lost"][f])]
+        assert [len(x) for x in tc.id_lists(ta)] == [len(ga["tracked"][f]), len(ga["lost"][f])] and [len(x) for x in tc.id_lists(tb)] == [len(gb["tracked"][f]), len(gb["lost"][f])]
 
 
 def test_frames_that_skip_the_network_equal_the_host_build():
     """the first frame (empty pool), a frame without detections at all and one with low detections only run no network; the device and the CPU build agree"""
     g = load_golden("default")
     t = new_tracker(g)
-    host = hdm.HostDeepMOT(torch_net(g["seed"], g["scale"]), g["img_shape"], conf_thresh=g["conf"], kalman_format=g["kalman_format"])
+    host = hdm.HostDeepMOT(hdm.torch_net(g["seed"], g["scale"]), g["img_shape"], conf_thresh=g["conf"], kalman_format=g["kalman_format"])
     low = g["dets"][3].copy()
     low[:, 4] = 0.17
     img = types.SimpleNamespace(shape=g["img_shape"] + (3,))
@@ -136,27 +118,8 @@ def test_frames_that_skip_the_network_equal_the_host_build():
         assert [c.track_id for c in cur] == [r[0] for r in rows], k
         np.testing.assert_allclose(np.array([c.tlwh for c in cur], np.float64).reshape(-1, 4), np.array([r[1] for r in rows]).reshape(-1, 4), rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL)
         sn = t._snapshot()
-        assert (int(sn["hdr_n_tracked"]), int(sn["hdr_n_lost"])) == tuple(len(x) for x in host_id_lists(host)), k
+        assert (int(sn["hdr_n_tracked"]), int(sn["hdr_n_lost"])) == tuple(len(x) for x in tc.id_lists(host)), k
     assert len(host.net_shapes) == 3      # frames 1, 4 and 5 of the six
-
-
-def _raw_pool(kind, cap=256, kalman=0):
-    from yolov7_tracker_amd import _lib
-    L = _lib.load()
-    nbytes = int(L.y7t_tracker_state_bytes(cap, cap))
-    st = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    ids = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _lib.check(L.y7t_tracker_init(_lib.ptr(st), nbytes, kind, kalman, cap, cap, 0.2, 0.5, 30, 1, _lib.ptr(ids), _lib.stream_ptr()))
-    out = torch.zeros((cap + 1, 8), dtype=torch.float64, device="cuda")
-    return L, st, ids, out
-
-
-def _status(L, st, cap=256):
-    n = L.y7t_tracker_layout(cap, cap, None, 0)
-    offs = (ctypes.c_int64 * n)()
-    L.y7t_tracker_layout(cap, cap, offs, n)
-    off = {L.y7t_tracker_field_name(i).decode(): int(offs[i]) for i in range(n)}["hdr_status"]
-    return int(st[off:off + 4].view(torch.int32).item())
 
 
 def test_entry_points_refuse_the_wrong_pool():
@@ -166,23 +129,23 @@ def test_entry_points_refuse_the_wrong_pool():
     from yolov7_tracker_amd import _lib
     cap = 256
     dhn = device_dhn(7, 3.0)
-    L, st, ids, out = _raw_pool(7)
+    L, st, ids, out = tc.raw_pool("deepmot")
     d = torch.tensor([[10, 10, 60, 90, 0.9, 0]], dtype=torch.float32, device="cuda")
     cnt = ctypes.c_void_p(out.data_ptr() + cap * 64)
     assert L.y7t_tracker_step(_lib.ptr(st), None, -1, _lib.ptr(out), cap, cnt, 0, None, _lib.stream_ptr()) == 0
     torch.cuda.synchronize()
-    assert _status(L, st) == 0
+    assert tc.pool_status(L, st) == 0
     r = L.y7t_tracker_step(_lib.ptr(st), _lib.ptr(d), 1, _lib.ptr(out), cap, cnt, 0, None, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st) & 8 and b"DeepMOT" in L.y7t_last_error()
-    _, st2, _, out2 = _raw_pool(7)
+    assert r == -4 and tc.pool_status(L, st) & 8 and b"DeepMOT" in L.y7t_last_error()
+    _, st2, _, out2 = tc.raw_pool("deepmot")
     tab = torch.tensor([d.data_ptr(), out2.data_ptr(), out2.data_ptr() + cap * 64], dtype=torch.int64, device="cuda")
     n1 = torch.ones(1, dtype=torch.int32, device="cuda")
     r = L.y7t_tracker_step_frames(_lib.ptr(st2), _lib.ptr(tab[0:1]), _lib.ptr(n1), _lib.ptr(tab[1:2]), _lib.ptr(tab[2:3]), cap, 1, 0, None, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st2) & 8
-    _, st3, _, out3 = _raw_pool(7)
-    _, st4, _, out4 = _raw_pool(1)
+    assert r == -4 and tc.pool_status(L, st2) & 8
+    _, st3, _, out3 = tc.raw_pool("deepmot")
+    _, st4, _, out4 = tc.raw_pool("bytetrack")
     states = torch.tensor([st3.data_ptr(), st4.data_ptr()], dtype=torch.int64, device="cuda")
     dets = torch.tensor([d.data_ptr(), d.data_ptr()], dtype=torch.int64, device="cuda")
     outs = torch.tensor([out3.data_ptr(), out4.data_ptr()], dtype=torch.int64, device="cuda")
@@ -191,9 +154,9 @@ def test_entry_points_refuse_the_wrong_pool():
         _lib.check(L.y7t_tracker_step_batch(_lib.ptr(states), _lib.ptr(dets), _lib.ptr(torch.ones(2, dtype=torch.int32, device="cuda")), _lib.ptr(outs),
                                             _lib.ptr(counts), cap, 2, threads, None, _lib.stream_ptr()))
         torch.cuda.synchronize()
-        assert _status(L, st3) & 8 and _status(L, st4) == 0 and counts.tolist()[0] == 0
+        assert tc.pool_status(L, st3) & 8 and tc.pool_status(L, st4) == 0 and counts.tolist()[0] == 0
     # the appearance trackers' steps on a DeepMOT pool
-    _, st5, _, out5 = _raw_pool(7)
+    _, st5, _, out5 = tc.raw_pool("deepmot")
     cnt5 = ctypes.c_void_p(out5.data_ptr() + cap * 64)
     f = torch.zeros((1, 128), dtype=torch.float32, device="cuda")
     fb = int(L.y7t_deepsort_feature_bytes(cap, cap, 128, 8))
@@ -201,21 +164,21 @@ def test_entry_points_refuse_the_wrong_pool():
     _lib.check(L.y7t_deepsort_init(_lib.ptr(feat), fb, cap, cap, 128, 8, _lib.stream_ptr()))
     r = L.y7t_tracker_step_deepsort(_lib.ptr(st5), _lib.ptr(feat), cap, _lib.ptr(d), 1, _lib.ptr(f), _lib.ptr(out5), cap, cnt5, 0, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st5) & 8
-    _, st6, _, out6 = _raw_pool(7)
+    assert r == -4 and tc.pool_status(L, st5) & 8
+    _, st6, _, out6 = tc.raw_pool("deepmot")
     sb = int(L.y7t_strongsort_feature_bytes(cap, cap, 128))
     sfeat = torch.zeros(sb, dtype=torch.uint8, device="cuda")
     _lib.check(L.y7t_strongsort_init(_lib.ptr(sfeat), sb, cap, cap, 128, 0.1, _lib.stream_ptr()))
     r = L.y7t_tracker_step_strongsort(_lib.ptr(st6), _lib.ptr(sfeat), _lib.ptr(d), 1, _lib.ptr(f), _lib.ptr(out6), cap, ctypes.c_void_p(out6.data_ptr() + cap * 64), 0, None, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st6) & 8
+    assert r == -4 and tc.pool_status(L, st6) & 8
     # the DeepMOT step on pools of other kinds
     held = [st, st2, st3, st4, st5, st6]
-    for kind in (1, 5, 6):
-        _, st7, _, out7 = _raw_pool(kind)
+    for kind in ("bytetrack", "uavmot", "strongsort"):
+        _, st7, _, out7 = tc.raw_pool(kind)
         r = L.y7t_tracker_step_deepmot(_lib.ptr(st7), dhn.ptr, _lib.ptr(d), 1, 720, 1280, _lib.ptr(out7), cap, ctypes.c_void_p(out7.data_ptr() + cap * 64), 0, _lib.stream_ptr())
         torch.cuda.synchronize()
-        assert r == -4 and _status(L, st7) & 8, kind
+        assert r == -4 and tc.pool_status(L, st7) & 8, kind
         held.append(st7)
     for s_ in held:
         L.y7t_tracker_release(_lib.ptr(s_))
@@ -230,21 +193,20 @@ def test_overflows_set_the_status():
     g = load_golden("default")
     dhn = device_dhn(g["seed"], g["scale"])
     cap = 256
-    L, st, ids, out = _raw_pool(7)
+    L, st, ids, out = tc.raw_pool("deepmot")
     cnt = ctypes.c_void_p(out.data_ptr() + cap * 64)
     for f in range(3):
         d = torch.from_numpy(g["dets"][f]).cuda()
         _lib.check(L.y7t_tracker_step_deepmot(_lib.ptr(st), dhn.ptr, _lib.ptr(d), d.shape[0], 720, 1280, _lib.ptr(out), cap if f < 2 else 2, cnt, 0, _lib.stream_ptr()))
         torch.cuda.synchronize()
-        assert bool(_status(L, st) & 4) == (f == 2)
+        assert bool(tc.pool_status(L, st) & 4) == (f == 2)
     assert int(out[cap].view(torch.int32)[0]) == len(g["frames"][2][0]) > 2      # (the count is the frame's; the rows stop at out_cap)
     L.y7t_tracker_release(_lib.ptr(st))
     t = new_tracker(g, max_tracks=8)
     with pytest.raises(_lib.Y7TError, match="overflow"):
         for f in range(4):
             step(t, g, f)
-    from yolov7_tracker_amd.tracker.deepmot import DeepMOT
-    small = DeepMOT(opts(g["conf"]), frame_rate=30, dhn=DeviceDHN(synth.make_dhn_weights(7, 3.0), 2, 2))
+    small = DeepMOT(tc.opts(g["conf"], max_tracks=256, max_dets=256), frame_rate=30, dhn=DeviceDHN(synth.make_dhn_weights(7, 3.0), 2, 2))
     step(small, g, 0)
     with pytest.raises(_lib.Y7TError, match="status 32"):
         step(small, g, 1)

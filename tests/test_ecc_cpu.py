@@ -1,5 +1,5 @@
 """CPU: the camera-motion estimate (ECC, tracker/gmc.py) without a GPU -- the NumPy float64 restatement (tests/ecc_np.py) against closed forms and planted warps,
-and the host build of the kernel bodies (tests/_hostsim_ecc: csrc/y7t_ecc.h compiled with g++) against the restatement.  The tolerances are the float32 noise
+and the host build of the kernel bodies (tests/_hostsim/ecc.py: csrc/y7t_ecc.h compiled with g++) against the restatement.  The tolerances are the float32 noise
 measured on the restatement itself (tests/ecc_scenes.py)."""
 import numpy as np
 import pytest
@@ -11,9 +11,9 @@ NAMES = list(sc.FIXTURES)
 
 @pytest.fixture(scope="module")
 def hs():
-    from tests import _hostsim_ecc
-    _hostsim_ecc.lib()
-    return _hostsim_ecc
+    from tests._hostsim import ecc
+    ecc.lib()
+    return ecc
 
 
 @pytest.fixture(scope="module")

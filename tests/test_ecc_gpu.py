@@ -1,5 +1,5 @@
 """GPU: the camera-motion estimate through the C ABI (y7t_ecc_prepare_u8, y7t_ecc_align, y7t_ecc_iteration_sums_f64) against the NumPy float64 restatement
-(tests/ecc_np.py, the tolerances of tests/ecc_scenes.py) and, bit for bit, against the host build of the same kernel bodies (tests/_hostsim_ecc), which mirrors
+(tests/ecc_np.py, the tolerances of tests/ecc_scenes.py) and, bit for bit, against the host build of the same kernel bodies (tests/_hostsim/ecc.py), which mirrors
 the device's reduction order; then the GMC class inside StrongSORT, BoT-SORT and the tracker CLI."""
 import ctypes
 import os
@@ -59,9 +59,9 @@ def dev():
 
 @pytest.fixture(scope="module")
 def hs():
-    from tests import _hostsim_ecc
-    _hostsim_ecc.lib()
-    return _hostsim_ecc
+    from tests._hostsim import ecc
+    ecc.lib()
+    return ecc
 
 
 @pytest.fixture(scope="module")

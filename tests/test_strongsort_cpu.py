@@ -1,72 +1,29 @@
-"""StrongSORT without a GPU: the CPU build of its workgroup program (tests/_hostsim_strongsort: the plain forms of the frame's three launches at nt = 1)
+"""StrongSORT without a GPU: the CPU build of its workgroup program (tests/_hostsim/strongsort.py: the plain forms of the frame's three launches at nt = 1)
 against the reference's golden vectors (tests/golden/tracker_strongsort_*.npz, tests/golden/make_golden_strongsort.py) and, where the reference sources
 exist, against the live reference on random scenes; the pinned arithmetic -- the float64 Euclidean chain, the float32 moving average, the fuse -- against
 scipy / numpy; the port's matching.embedding_distance against the reference's."""
-import importlib.util
+import functools
 import os
 
 import numpy as np
 import pytest
 
-from tests import _hostsim_strongsort as hss
+from tests import _hostsim as hs
+from tests import tracker_case as tc
 from tests import util
-from tests.test_uavmot_cpu import id_lists, layout
+from tests._hostsim import strongsort as hss
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = ["identity128", "identity512", "dim100", "boxfeat", "crowd300", "crowd500", "gamma05", "conf04", "empty", "gaps"]
+GOLDEN = tc.GOLDEN
+NAMES = tc.NAMES["strongsort"]
 SPARSE_NAMES = ["identity512", "crowd300", "crowd500"]      # identity features and frames of 64 x 64 pairs or more: the sparse component solver
-
-
-def maker():
-    """tests/golden/make_golden_strongsort.py as a module: the scenes' generators (and, where the reference exists, its runner)"""
-    spec = importlib.util.spec_from_file_location("make_golden_strongsort", os.path.join(GOLDEN, "make_golden_strongsort.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    return mg
-
-
-def load_golden(name):
-    g = np.load(os.path.join(GOLDEN, "tracker_strongsort_%s.npz" % name))
-    dets, fn, warps = maker().scene_from_golden(g)
-
-    def split(counts, flat):
-        o = np.concatenate([[0], np.cumsum(counts)])
-        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
-    frames = []
-    for f in range(len(dets)):
-        sel = g["frame"] == f
-        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
-    return dict(dets=dets, feature_fn=fn, warps=warps, dim=int(g["feat_dim"]), frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]),
-                lost=split(g["lost_counts"], g["lost_ids"]), conf=float(g["conf_thresh"]), gamma=float(g["gamma"]), final_ids=g["final_slots_ids"].tolist(),
-                final_features=g["final_features"], stale=g["stale_counts"], both=g["both_counts"], ref_ms=float(g["ref_ms_per_frame"]),
-                kalman_format=str(g["kalman_format"]))
-
-
-def slot_of(trk, track_id):
-    lo = layout(trk.cap_t, trk.cap_d)
-    tid = trk.blob[lo["tid"]:lo["tid"] + 4 * trk.cap_t].view(np.int32)
-    nt = int(trk.blob[lo["hdr_n_tracked"]:lo["hdr_n_tracked"] + 4].view(np.int32)[0])
-    tracked = trk.blob[lo["tracked"]:lo["tracked"] + 4 * nt].view(np.int32)
-    hit = [int(s) for s in tracked if tid[s] == track_id]
-    assert len(hit) == 1, track_id
-    return hit[0]
-
-
-def check_rows(rows, want, f):
-    ids, tlwh, cls, score = want["frames"][f]
-    assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
-    # (the Kalman arithmetic matches the reference to util's tolerance, as for ByteTrack: tests/test_hostsim.py; ids, classes, scores and lists exactly)
-    np.testing.assert_allclose(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL, err_msg="frame %d: tlwh" % f)
-    assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score), "frame %d" % f
+load_golden = functools.partial(tc.load_golden, "strongsort")
+maker = functools.partial(tc.maker, "strongsort")
 
 
 def replay(want, n_frames=None, **kw):
     """run the host build over the scene and compare every frame with `want` (a golden / the live reference's frames) -> the tracker"""
     trk = hss.HostStrongSORT(want["feature_fn"], want["dim"], conf_thresh=want["conf"], gamma=want["gamma"], kalman_format=want["kalman_format"], **kw)
-    for f, d in enumerate(want["dets"][:n_frames]):
-        rows = trk.update(d, None if want["warps"] is None else want["warps"][f])
-        check_rows(rows, want, f)
-        assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
+    tc.replay_host(trk, want, n_frames=n_frames)
     return trk
 
 
@@ -78,7 +35,7 @@ def test_hostsim_strongsort_matches_reference_golden(name):
     trk = replay(g)
     assert len(g["final_ids"]) > 0 and g["final_ids"] == g["tracked"][-1][:len(g["final_ids"])]
     for tid, want in zip(g["final_ids"], g["final_features"]):
-        got = trk.vector(slot_of(trk, tid))
+        got = trk.vector(tc.slot_of(trk, tid))
         assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), "track %d: smoothed vector" % tid
 
 
@@ -105,7 +62,7 @@ def test_goldens_state_their_environment_and_size():
 
 
 def _stats():
-    return [hss.lib().hs_ss_stat(k) for k in range(4)]
+    return [hs.lib().hs_ss_stat(k) for k in range(4)]
 
 
 def test_boxfeat_takes_the_dense_path():
@@ -136,13 +93,13 @@ def test_identity_goldens_take_the_sparse_path_with_and_without_fast_scratch(nam
     before = _stats()
     replay(g)
     assert _stats()[0] > before[0], "no fused association solved by the sparse component solver"
-    hss.lib().hs_set_fast_bytes(0)      # every work array in the state blob (the placement branches a workgroup without enough LDS takes)
+    hs.lib().hs_set_fast_bytes(0)      # every work array in the state blob (the placement branches a workgroup without enough LDS takes)
     try:
         before = _stats()
         replay(g, n_frames=8 if name == "crowd500" else None)
         assert _stats()[0] > before[0]
     finally:
-        hss.lib().hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", str(hss.FAST_BYTES))))
+        hs.reset_fast_bytes()
 
 
 # ---- the pinned arithmetic ----
@@ -188,7 +145,7 @@ def test_fuse_equals_python_expression(gamma):
     a, b = rng.uniform(0, 1, 5000), rng.uniform(0, 2, 5000)
     a[:100] = 1.0
     want = gamma * a + (1. - gamma) * b
-    got = np.array([hss.lib().hs_ss_fuse(gamma, x, y) for x, y in zip(a, b)])
+    got = np.array([hs.lib().hs_ss_fuse(gamma, x, y) for x, y in zip(a, b)])
     assert np.array_equal(got, want)
 
 
@@ -196,11 +153,11 @@ def test_feature_vectors_follow_the_slot_not_its_previous_track():
     """a slot that is freed and reused starts with its new track's raw vector; re_activate and frames without a match leave a vector alone"""
     g = load_golden("identity128")
     trk = hss.HostStrongSORT(g["feature_fn"], g["dim"], conf_thresh=g["conf"], gamma=g["gamma"], kalman_format=g["kalman_format"], cap_t=96)      # a small pool: slots are reused
-    lo = layout(96, 1024)
+    lo = tc.layout(trk.cap_t, trk.cap_d)
     born = {}
     for f, d in enumerate(g["dets"]):
         rows = trk.update(d, g["warps"][f])
-        check_rows(rows, g, f)
+        tc.check_rows(rows, g, f, exact=False)
         tid = trk.blob[lo["tid"]:lo["tid"] + 4 * 96].view(np.int32)
         start = trk.blob[lo["start"]:lo["start"] + 4 * 96].view(np.int32)
         box = trk.blob[lo["box"]:lo["box"] + 16 * 96].view(np.float32).reshape(96, 4)
@@ -226,7 +183,7 @@ def test_pool_and_feature_state_overflow_raise():
 
 
 def test_vectors_follow_the_header():
-    assert hss.lib().hs_ss_vec_offset(1024, 1024, 128) == 64      # (tracker/strongsort.py reads the vectors from there)
+    assert hs.lib().hs_ss_vec_offset(1024, 1024, 128) == 64      # (tracker/strongsort.py reads the vectors from there)
 
 
 # ---- against the live reference ----
@@ -237,9 +194,7 @@ needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference so
 
 def _want_from_reference(mg, dets, fn, dim, warps, conf, gamma, kalman_format="strongsort"):
     ref, _ = mg.run_reference(dets, fn, warps, conf, gamma, kalman_format)
-    return dict(dets=dets, feature_fn=fn, warps=warps, dim=dim, conf=conf, gamma=gamma, kalman_format=kalman_format, tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref],
-                frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
-                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref])
+    return tc.want_from_reference(ref, dets=dets, feature_fn=fn, warps=warps, dim=dim, conf=conf, gamma=gamma, kalman_format=kalman_format)
 
 
 @needs_ref

@@ -2,8 +2,8 @@
 Python class, against the reference's golden vectors (tests/golden/tracker_strongsort_*.npz) and the CPU build of the same program; the appearance kernel
 alone against numpy's sequential float64 chain; the refusals, the overflows, the ReID seam and the tracker CLI with --tracker strongsort."""
 import ctypes
+import functools
 import os
-import types
 
 import numpy as np
 import pytest
@@ -12,38 +12,16 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from tests import util  # noqa: E402
-from tests import _hostsim_strongsort as hss  # noqa: E402
-from tests.test_strongsort_cpu import NAMES, load_golden  # noqa: E402
+from tests import tracker_case as tc  # noqa: E402
+from tests._hostsim import strongsort as hss  # noqa: E402
+from yolov7_tracker_amd.tracker.strongsort import StrongSORT  # noqa: E402
+
+NAMES = tc.NAMES["strongsort"]
+load_golden = functools.partial(tc.load_golden, "strongsort")
 
 
-def opts(conf=0.2, threads=0, **kw):
-    o = types.SimpleNamespace(conf_thresh=conf, track_buffer=30, kalman_format="strongsort", img_size=1280, iou_thresh=0.5, tracker_threads=threads)
-    o.__dict__.update(kw)
-    return o
-
-
-def new_tracker(feature_fn=None, conf=0.2, threads=0, gamma=0.1, **kw):
-    from yolov7_tracker_amd.tracker.basetrack import BaseTrack
-    from yolov7_tracker_amd.tracker.strongsort import StrongSORT
-    BaseTrack._count = 0
-    t = StrongSORT(opts(conf, threads, **kw), frame_rate=30, gamma=gamma)
-    if feature_fn is not None:
-        t.get_feature = lambda tlbrs, ori_img, _fn=feature_fn: _fn(tlbrs)
-    return t
-
-
-def id_lists(t):
-    s = t._snapshot()
-    return s["tid"][s["tracked"][:s["hdr_n_tracked"]]].tolist(), s["tid"][s["lost"][:s["hdr_n_lost"]]].tolist()
-
-
-def check_frame(g, f, cur):
-    ids, tlwh, cls, score = g["frames"][f]
-    assert [t.track_id for t in cur] == ids.tolist(), "frame %d: ids" % f
-    np.testing.assert_allclose(np.array([t.tlwh for t in cur], np.float64).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL,
-                               err_msg="frame %d: tlwh" % f)
-    assert np.array_equal(np.array([t.cls for t in cur], np.float32), cls) and np.array_equal(np.array([t.score for t in cur], np.float32), score), "frame %d" % f
+def new_tracker(feature_fn=None, conf=0.2, threads=0, gamma=0.1, kalman_format="strongsort", **kw):
+    return tc.new_tracker(StrongSORT, conf, threads, kalman_format, feature_fn, dict(gamma=gamma), **kw)
 
 
 def run_golden(g, t):
@@ -52,8 +30,7 @@ def run_golden(g, t):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)      # (scenes without warps: "use_ECC is set but no camera-motion matrix was supplied")
             cur = t.update_without_detection(None, None) if d is None else t.update(d, None, warp=None if g["warps"] is None else g["warps"][f])
-        check_frame(g, f, cur)
-        assert id_lists(t) == (g["tracked"][f], g["lost"][f]), "frame %d: tracked / lost lists" % f
+        tc.check_tracks(cur, g, f, False, tc.id_lists(t))
 
 
 @pytest.mark.parametrize("threads", [256, 512, 1024])
@@ -113,48 +90,29 @@ def test_appearance_kernel_equals_sequential_chain(n, dim):
     assert got[5, 3] == 0.0
 
 
-def _raw_pool(kind, cap=256, kalman=0):
-    from yolov7_tracker_amd import _lib
-    L = _lib.load()
-    nbytes = int(L.y7t_tracker_state_bytes(cap, cap))
-    st = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    ids = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _lib.check(L.y7t_tracker_init(_lib.ptr(st), nbytes, kind, kalman, cap, cap, 0.2, 0.5, 30, 1, _lib.ptr(ids), _lib.stream_ptr()))
-    out = torch.zeros((cap + 1, 8), dtype=torch.float64, device="cuda")
-    return L, st, ids, out
-
-
-def _status(L, st, cap=256):
-    n = L.y7t_tracker_layout(cap, cap, None, 0)
-    offs = (ctypes.c_int64 * n)()
-    L.y7t_tracker_layout(cap, cap, offs, n)
-    off = {L.y7t_tracker_field_name(i).decode(): int(offs[i]) for i in range(n)}["hdr_status"]
-    return int(st[off:off + 4].view(torch.int32).item())
-
-
 def test_plain_entry_points_refuse_a_strongsort_pool():
     """y7t_tracker_step with detections and y7t_tracker_step_frames return Y7T_E_STATE and set status bit 8; y7t_tracker_step_batch sets bit 8 on the
     StrongSORT pool of a batch, returns no rows for it and steps the ByteTrack pool beside it; the predict-only step is accepted"""
     from yolov7_tracker_amd import _lib
     cap = 256
-    L, st, ids, out = _raw_pool(6)
+    L, st, ids, out = tc.raw_pool("strongsort")
     d = torch.tensor([[10, 10, 60, 90, 0.9, 0]], dtype=torch.float32, device="cuda")
     cnt = ctypes.c_void_p(out.data_ptr() + cap * 64)
     assert L.y7t_tracker_step(_lib.ptr(st), None, -1, _lib.ptr(out), cap, cnt, 0, None, _lib.stream_ptr()) == 0
     torch.cuda.synchronize()
-    assert _status(L, st) == 0
+    assert tc.pool_status(L, st) == 0
     r = L.y7t_tracker_step(_lib.ptr(st), _lib.ptr(d), 1, _lib.ptr(out), cap, cnt, 0, None, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st) & 8 and b"StrongSORT" in L.y7t_last_error()
-    L2, st2, _, out2 = _raw_pool(6)
+    assert r == -4 and tc.pool_status(L, st) & 8 and b"StrongSORT" in L.y7t_last_error()
+    L2, st2, _, out2 = tc.raw_pool("strongsort")
     tab = torch.tensor([d.data_ptr(), out2.data_ptr(), out2.data_ptr() + cap * 64], dtype=torch.int64, device="cuda")
     n1 = torch.ones(1, dtype=torch.int32, device="cuda")
     r = L.y7t_tracker_step_frames(_lib.ptr(st2), _lib.ptr(tab[0:1]), _lib.ptr(n1), _lib.ptr(tab[1:2]), _lib.ptr(tab[2:3]), cap, 1, 0, None, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st2) & 8
+    assert r == -4 and tc.pool_status(L, st2) & 8
     # a batch of a StrongSORT and a ByteTrack pool
-    _, st3, _, out3 = _raw_pool(6)
-    _, st4, _, out4 = _raw_pool(1)
+    _, st3, _, out3 = tc.raw_pool("strongsort")
+    _, st4, _, out4 = tc.raw_pool("bytetrack")
     states = torch.tensor([st3.data_ptr(), st4.data_ptr()], dtype=torch.int64, device="cuda")
     dets = torch.tensor([d.data_ptr(), d.data_ptr()], dtype=torch.int64, device="cuda")
     outs = torch.tensor([out3.data_ptr(), out4.data_ptr()], dtype=torch.int64, device="cuda")
@@ -163,7 +121,7 @@ def test_plain_entry_points_refuse_a_strongsort_pool():
         _lib.check(L.y7t_tracker_step_batch(_lib.ptr(states), _lib.ptr(dets), _lib.ptr(torch.ones(2, dtype=torch.int32, device="cuda")), _lib.ptr(outs),
                                             _lib.ptr(counts), cap, 2, threads, None, _lib.stream_ptr()))
         torch.cuda.synchronize()
-        assert _status(L, st3) & 8 and _status(L, st4) == 0 and counts.tolist()[0] == 0
+        assert tc.pool_status(L, st3) & 8 and tc.pool_status(L, st4) == 0 and counts.tolist()[0] == 0
     for s_ in (st, st2, st3, st4):
         L.y7t_tracker_release(_lib.ptr(s_))
 
@@ -171,7 +129,7 @@ def test_plain_entry_points_refuse_a_strongsort_pool():
 def test_deepsort_step_refuses_a_strongsort_pool_and_strongsort_step_another_kind():
     from yolov7_tracker_amd import _lib
     cap = 256
-    L, st, _, out = _raw_pool(6)
+    L, st, _, out = tc.raw_pool("strongsort")
     cnt = ctypes.c_void_p(out.data_ptr() + cap * 64)
     fb = int(L.y7t_deepsort_feature_bytes(cap, cap, 128, 8))
     feat = torch.zeros(fb, dtype=torch.uint8, device="cuda")
@@ -180,16 +138,16 @@ def test_deepsort_step_refuses_a_strongsort_pool_and_strongsort_step_another_kin
     f = torch.zeros((1, 128), dtype=torch.float32, device="cuda")
     r = L.y7t_tracker_step_deepsort(_lib.ptr(st), _lib.ptr(feat), cap, _lib.ptr(d), 1, _lib.ptr(f), _lib.ptr(out), cap, cnt, 0, _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert r == -4 and _status(L, st) & 8
-    for kind in (1, 3, 5):      # ByteTrack, DeepSORT, UAVMOT pools
-        L, st2, _, out2 = _raw_pool(kind)
+    assert r == -4 and tc.pool_status(L, st) & 8
+    for kind in ("bytetrack", "deepsort", "uavmot"):
+        L, st2, _, out2 = tc.raw_pool(kind)
         sb = int(L.y7t_strongsort_feature_bytes(cap, cap, 128))
         sfeat = torch.zeros(sb, dtype=torch.uint8, device="cuda")
         _lib.check(L.y7t_strongsort_init(_lib.ptr(sfeat), sb, cap, cap, 128, 0.1, _lib.stream_ptr()))
         r = L.y7t_tracker_step_strongsort(_lib.ptr(st2), _lib.ptr(sfeat), _lib.ptr(d), 1, _lib.ptr(f), _lib.ptr(out2), cap,
                                           ctypes.c_void_p(out2.data_ptr() + cap * 64), 0, None, _lib.stream_ptr())
         torch.cuda.synchronize()
-        assert r == -4 and _status(L, st2) & 8, kind
+        assert r == -4 and tc.pool_status(L, st2) & 8, kind
         L.y7t_tracker_release(_lib.ptr(st2))
     L.y7t_tracker_release(_lib.ptr(st))
 
@@ -202,7 +160,7 @@ def test_strongsort_refuses_the_botsort_kalman_filter():
     nbytes = int(L.y7t_tracker_state_bytes(64, 64))
     st = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
     ids = torch.zeros(1, dtype=torch.int32, device="cuda")
-    assert L.y7t_tracker_init(_lib.ptr(st), nbytes, 6, 2, 64, 64, 0.2, 0.5, 30, 1, _lib.ptr(ids), _lib.stream_ptr()) == -1
+    assert L.y7t_tracker_init(_lib.ptr(st), nbytes, StrongSORT._KIND, 2, 64, 64, 0.2, 0.5, 30, 1, _lib.ptr(ids), _lib.stream_ptr()) == -1
 
 
 def test_pool_and_feature_state_overflow_raise():
@@ -235,7 +193,7 @@ def test_pool_starts_clean_after_release_and_reinit():
     L.y7t_tracker_release(_lib.ptr(t._state))
     from yolov7_tracker_amd.tracker.basetrack import BaseTrack, _IdCounter
     BaseTrack._count = 0
-    _lib.check(L.y7t_tracker_init(_lib.ptr(t._state), t._state.numel(), 6, 3, t.cap_t, t.cap_d, g["conf"], 0.5, 30, t._flags, _lib.ptr(_IdCounter.tensor()),
+    _lib.check(L.y7t_tracker_init(_lib.ptr(t._state), t._state.numel(), t._KIND, 3, t.cap_t, t.cap_d, g["conf"], 0.5, 30, t._flags, _lib.ptr(_IdCounter.tensor()),
                                   _lib.stream_ptr()))
     _lib.check(L.y7t_strongsort_init(_lib.ptr(t._feat), t._feat.numel(), t.cap_t, t.cap_d, t._feat_dim, g["gamma"], _lib.stream_ptr()))
     t.frame_id = 0
@@ -249,8 +207,7 @@ def test_update_and_launch_agree_row_for_row():
     same rows, lists and vectors"""
     g = load_golden("identity512")
     a = new_tracker(g["feature_fn"], g["conf"], 0, g["gamma"], kalman_format=g["kalman_format"])
-    from yolov7_tracker_amd.tracker.strongsort import StrongSORT
-    b = StrongSORT(opts(g["conf"], kalman_format=g["kalman_format"]), frame_rate=30, gamma=g["gamma"])
+    b = StrongSORT(tc.opts(g["conf"], kalman_format=g["kalman_format"]), frame_rate=30, gamma=g["gamma"])
     out = torch.zeros((b.cap_t + 1, 8), dtype=torch.float64, device="cuda")
     from yolov7_tracker_amd.tracker.basetrack import BaseTrack
     for f, d in enumerate(g["dets"]):
@@ -271,7 +228,7 @@ def test_update_and_launch_agree_row_for_row():
         assert rows[:, 0].astype(np.int64).tolist() == [x.track_id for x in cur], "frame %d" % f
         assert np.array_equal(rows[:, 1:5], np.array([x.tlwh for x in cur], np.float64).reshape(-1, 4)), "frame %d" % f
         assert rows[:, 7].astype(np.int64).tolist() == [x._slot for x in cur]
-    assert b._status() == 0 and b._feature_status() == 0 and id_lists(a) == id_lists(b)
+    assert b._status() == 0 and b._feature_status() == 0 and tc.id_lists(a) == tc.id_lists(b)
     assert np.array_equal(a._vectors(), b._vectors())
 
 
@@ -296,13 +253,13 @@ def test_update_with_the_device_reid_extractor():
     and the tracks carry finite feat_dim-wide vectors"""
     from yolov7_tracker_amd import synth
     from yolov7_tracker_amd.tracker.reid import ReIDExtractor
-    from yolov7_tracker_amd.tracker.strongsort import StrongSORT, REID_SIZE
+    from yolov7_tracker_amd.tracker.strongsort import REID_SIZE
     from yolov7_tracker_amd.tracker.basetrack import BaseTrack
     assert REID_SIZE == (256, 128)
     BaseTrack._count = 0
     ext = ReIDExtractor(None, size=(256, 128), max_crops=64)
     assert not ext.fused and (ext.in_w, ext.in_h) == (256, 128)
-    t = StrongSORT(opts(0.2), frame_rate=30, gamma=0.1, reid_model=ext)
+    t = StrongSORT(tc.opts(0.2, kalman_format="strongsort"), frame_rate=30, gamma=0.1, reid_model=ext)
     frames = synth.make_frames(4, 30, 640, seq_idx=2)
     dets = synth.make_detections(4, 30, 640, seq_idx=2, miss=0.0, fp=0.0)
     n_tracks = 0
@@ -315,7 +272,6 @@ def test_update_with_the_device_reid_extractor():
 
 
 def test_use_ecc_without_a_warp_warns_once_and_the_ecc_object_is_called():
-    from yolov7_tracker_amd.tracker.strongsort import StrongSORT
     g = load_golden("identity128")
     StrongSORT._warned = False
     t = new_tracker(g["feature_fn"], g["conf"], 0, g["gamma"])
@@ -330,7 +286,7 @@ def test_use_ecc_without_a_warp_warns_once_and_the_ecc_object_is_called():
             return g["warps"][len(calls) - 1]
     t2.ECC = ECC()
     for f in range(15):
-        check_frame(g, f, t2.update(g["dets"][f], None))
+        tc.check_tracks(t2.update(g["dets"][f], None), g, f, False)
     assert len(calls) == 15
 
 

@@ -2,110 +2,45 @@
 (tests/golden/tracker_uavmot_*.npz, tests/golden/make_golden_uavmot.py) and, where the reference sources exist, against the live reference on random
 scenes; the port's matching.structure_* functions against the reference's, and the float64 pins of the AMF arithmetic against numpy / scipy."""
 import ctypes
+import functools
 import math
-import os
 
 import numpy as np
 import pytest
 
 from tests import _hostsim as hs
-from tests import util
+from tests import tracker_case as tc
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = ["default", "misses", "sparse1", "sparse3", "crowd", "empty", "conf04", "botsort"]
-LIB = os.path.join(os.path.dirname(GOLDEN), "..", "yolov7-tracker_amd", "lib", "liby7t.so")
-
-
-class UAVHost(hs.HostSimTracker):
-    TRACKERS = dict(hs.HostSimTracker.TRACKERS, uavmot=5)
+NAMES = tc.NAMES["uavmot"]
+load_golden = functools.partial(tc.load_golden, "uavmot")
 
 
-def load_golden(name):
-    g = np.load(os.path.join(GOLDEN, "tracker_uavmot_%s.npz" % name))
-    off = np.concatenate([[0], np.cumsum(g["det_counts"])])
-    dets = [g["dets"][off[i]:off[i + 1]] for i in range(len(g["det_counts"]))]
-
-    def split(counts, flat):
-        o = np.concatenate([[0], np.cumsum(counts)])
-        return [flat[o[i]:o[i + 1]].tolist() for i in range(len(counts))]
-    frames = []
-    for f in range(len(dets)):
-        sel = g["frame"] == f
-        frames.append((g["track_id"][sel], g["tlwh"][sel], g["cls"][sel], g["score"][sel]))
-    return dict(dets=dets, frames=frames, tracked=split(g["tracked_counts"], g["tracked_ids"]), lost=split(g["lost_counts"], g["lost_ids"]),
-                conf=float(g["conf_thresh"]), kalman_format=str(g["kalman_format"]))
-
-
-_LAYOUT = {}
-
-
-def layout(cap_t, cap_d):
-    """byte offsets of the pool blob's fields (the product library's y7t_tracker_layout: host code, no device needed)"""
-    if (cap_t, cap_d) not in _LAYOUT:
-        L = ctypes.CDLL(LIB)
-        L.y7t_tracker_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-        L.y7t_tracker_field_name.restype = ctypes.c_char_p
-        n = L.y7t_tracker_layout(cap_t, cap_d, None, 0)
-        offs = (ctypes.c_int64 * n)()
-        L.y7t_tracker_layout(cap_t, cap_d, offs, n)
-        _LAYOUT[(cap_t, cap_d)] = {L.y7t_tracker_field_name(i).decode(): int(offs[i]) for i in range(n)}
-    return _LAYOUT[(cap_t, cap_d)]
-
-
-def id_lists(trk):
-    """-> (ids of the tracked list, ids of the lost list) of a host pool, in list order"""
-    lo, b = layout(trk.cap_t, 1024), trk.blob
-    i32 = lambda off, n: b[off:off + 4 * n].view(np.int32)      # noqa: E731
-    tid = i32(lo["tid"], trk.cap_t)
-    nt, nl = int(i32(lo["hdr_n_tracked"], 1)[0]), int(i32(lo["hdr_n_lost"], 1)[0])
-    return tid[i32(lo["tracked"], nt)].tolist(), tid[i32(lo["lost"], nl)].tolist()
-
-
-def replay(dets, conf, kalman_format="default", arena_frames=0, want=None):
-    """run the host build over `dets`; with `want` (golden / reference frames) compare every frame"""
-    trk = UAVHost("uavmot", conf_thresh=conf, kalman_format=kalman_format)
-    got = []
-    for f, d in enumerate(dets):
-        if arena_frames and f % arena_frames == 0:
-            assert hs.lib().hs_arena_begin(trk.blob.ctypes.data)
-        rows = trk.update(d)
-        group_end = not arena_frames or f % arena_frames == arena_frames - 1 or f == len(dets) - 1
-        if arena_frames and group_end:
-            hs.lib().hs_arena_end(trk.blob.ctypes.data)
-        got.append(rows)
-        if want is None:
-            continue
-        ids, tlwh, cls, score = want["frames"][f]
-        assert [r[0] for r in rows] == ids.tolist(), "frame %d: ids" % f
-        # (the Kalman arithmetic matches the reference to util's tolerance, as for ByteTrack: tests/test_hostsim.py; ids and lists exactly)
-        np.testing.assert_allclose(np.array([r[1] for r in rows]).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL, err_msg="frame %d: tlwh" % f)
-        assert np.array_equal(np.array([r[2] for r in rows], np.float32), cls) and np.array_equal(np.array([r[3] for r in rows], np.float32), score)
-        if group_end:      # (inside an arena group the lists live in the arena)
-            assert id_lists(trk) == (want["tracked"][f], want["lost"][f]), "frame %d: tracked / lost lists" % f
-    return got
+def replay(want, arena_frames=0, n_frames=None):
+    """the host build over the scene, every frame compared with `want` (a golden / the live reference's frames)"""
+    trk = hs.HostSimTracker("uavmot", conf_thresh=want["conf"], kalman_format=want.get("kalman_format", "default"))
+    return tc.replay_host(trk, want, arena_frames, n_frames)
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_hostsim_uavmot_matches_reference_golden(name):
     g = load_golden(name)
-    replay(g["dets"], g["conf"], g["kalman_format"], want=g)
+    replay(g)
 
 
 @pytest.mark.parametrize("name,frames", [("default", 8), ("misses", 16), ("crowd", 5), ("sparse3", 7)])
 def test_hostsim_uavmot_with_list_arena_matches_reference_golden(name, frames):
     g = load_golden(name)
-    replay(g["dets"], g["conf"], g["kalman_format"], arena_frames=frames, want=g)
+    replay(g, arena_frames=frames)
 
 
 def test_hostsim_uavmot_without_fast_scratch_matches_reference_golden(monkeypatch):
     """every work array in the state blob (the placement branches a workgroup without enough LDS takes): the centres of the AMF pass behind its vectors"""
-    import ctypes as ct
     g = load_golden("crowd")
-    ct.CDLL(hs.build()).hs_set_fast_bytes(0)
+    hs.lib().hs_set_fast_bytes(0)
     try:
-        replay(g["dets"][:6], g["conf"], want=dict(g, frames=g["frames"][:6], tracked=g["tracked"][:6], lost=g["lost"][:6]))
+        replay(g, n_frames=6)
     finally:
-        ct.CDLL(hs.build()).hs_set_fast_bytes(int(os.environ.get("Y7T_HOSTSIM_FAST_BYTES", "131072")))
+        hs.reset_fast_bytes()
 
 
 def test_uavmot_goldens_cover_the_scenes():
@@ -120,13 +55,14 @@ def test_uavmot_goldens_cover_the_scenes():
 def test_hostsim_uavmot_differs_from_bytetrack():
     """kind 5 is not ByteTrack: on the CLI's sequence the two disagree (the 0.7 / AMF first association, the index quirk)"""
     g = load_golden("default")
-    u = replay(g["dets"][:40], g["conf"])
+    uav = hs.HostSimTracker("uavmot", conf_thresh=g["conf"])
+    u = [uav.update(d) for d in g["dets"][:40]]
     b = hs.run("bytetrack", g["dets"][:40])
     assert any([r[0] for r in x] != [r[0] for r in y] or not np.array_equal(np.array([r[1] for r in x]), np.array([r[1] for r in y])) for x, y in zip(u, b))
 
 
 def test_hostsim_uavmot_pool_overflow_sets_status():
-    trk = UAVHost("uavmot", cap_t=16)
+    trk = hs.HostSimTracker("uavmot", cap_t=16)
     from yolov7_tracker_amd import synth
     with pytest.raises(RuntimeError, match="capacity"):
         for d in synth.make_detections(5, 40, seq_idx=3):
@@ -201,14 +137,6 @@ from oracle import ref_harness  # noqa: E402
 needs_ref = pytest.mark.skipif(not ref_harness.available(), reason="reference sources not present")
 
 
-def _ref_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_golden_uavmot", os.path.join(GOLDEN, "make_golden_uavmot.py"))
-    mg = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mg)
-    return mg
-
-
 class _T:
     """a track as structure_representation sees it: mean[0:2]"""
     def __init__(self, xy):
@@ -238,7 +166,7 @@ def test_structure_functions_equal_reference():
     bit against the reference's, on random, lattice and boundary centres"""
     from yolov7_tracker_amd.tracker import matching as pm
     from yolov7_tracker_amd.tracker.uavmot import AMF_STrack
-    mg = _ref_module()
+    mg = tc.maker("uavmot")
     mod = mg.load_uavmot()
     rm = ref_harness.load_tracker().matching
     rng = np.random.default_rng(11)
@@ -264,7 +192,7 @@ def test_structure_functions_equal_reference():
 @pytest.mark.parametrize("seed", range(12))
 def test_hostsim_uavmot_matches_live_reference(seed):
     from yolov7_tracker_amd import synth
-    mg = _ref_module()
+    mg = tc.maker("uavmot")
     rng = np.random.default_rng(3000 + seed)
     nf, nobj = int(rng.integers(20, 50)), int(rng.integers(1, 120))
     extra = {"bounce": bool(rng.integers(0, 2)), "miss": float(rng.uniform(0.0, 0.4))}
@@ -274,23 +202,18 @@ def test_hostsim_uavmot_matches_live_reference(seed):
     conf = [0.2, 0.3, 0.4, 0.25][seed % 4]
     kform = "botsort" if seed % 5 == 4 else "default"
     ref = mg.run_reference(dets, conf, kform)
-    want = dict(frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
-                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref],
-                tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref])
-    replay(dets, conf, kform, arena_frames=(7 if seed % 2 else 0), want=want)
+    replay(tc.want_from_reference(ref, dets=dets, conf=conf, kalman_format=kform), arena_frames=(7 if seed % 2 else 0))
 
 
 @needs_ref
 def test_hostsim_uavmot_update_without_detection_matches_live_reference():
     """frames without detections (update_without_detection, basetrack.py:489-537 -- ByteTrack's) between ordinary ones"""
     from yolov7_tracker_amd import synth
-    mg = _ref_module()
+    mg = tc.maker("uavmot")
     dets = list(synth.make_detections(30, 40, seq_idx=320, miss=0.2))
     dets[8:8] = [None, None]
     dets[20:20] = [None]
     ref = mg.run_reference(dets, 0.2)
-    want = dict(frames=[(np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64).reshape(-1, 4),
-                         np.array([r[2] for r in rows], np.float32), np.array([r[3] for r in rows], np.float32)) for rows, _, _ in ref],
-                tracked=[t for _, t, _ in ref], lost=[lo for _, _, lo in ref])
+    want = tc.want_from_reference(ref, dets=dets, conf=0.2)
     assert len(want["frames"][8][0]) > 0
-    replay(dets, 0.2, want=want)
+    replay(want)

@@ -3,9 +3,9 @@ UAVMOT frame by frame, y7t_tracker_step_frames, y7t_tracker_step_batch -- agains
 the CPU build of the same program; y7t_structure_distance_f64 (the device's atan2 among it) against a numpy restatement; the tracker CLI with
 --tracker uavmot."""
 import ctypes
+import functools
 import math
 import os
-import types
 
 import numpy as np
 import pytest
@@ -14,31 +14,14 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from tests import _hostsim as hs  # noqa: E402
+from tests import tracker_case as tc  # noqa: E402
 from tests import util  # noqa: E402
-from tests.test_uavmot_cpu import UAVHost, NAMES, load_golden  # noqa: E402
+from yolov7_tracker_amd.tracker.uavmot import UAVMOT  # noqa: E402
 
-
-def opts(conf=0.2, threads=0, **kw):
-    o = types.SimpleNamespace(conf_thresh=conf, track_buffer=30, kalman_format="default", img_size=1280, iou_thresh=0.5, tracker_threads=threads)
-    o.__dict__.update(kw)
-    return o
-
-
-def new_tracker(conf=0.2, threads=0, **kw):
-    from yolov7_tracker_amd.tracker.basetrack import BaseTrack
-    from yolov7_tracker_amd.tracker.uavmot import UAVMOT
-    BaseTrack._count = 0
-    return UAVMOT(opts(conf, threads, **kw), frame_rate=30)
-
-
-def check_frame(g, f, cur, lists=None):
-    ids, tlwh, cls, score = g["frames"][f]
-    assert [t.track_id for t in cur] == ids.tolist(), "frame %d: ids" % f
-    np.testing.assert_allclose(np.array([t.tlwh for t in cur], np.float64).reshape(-1, 4), tlwh, rtol=util.TLWH_RTOL, atol=util.TLWH_ATOL,
-                               err_msg="frame %d: tlwh" % f)
-    assert np.array_equal(np.array([t.cls for t in cur], np.float32), cls) and np.array_equal(np.array([t.score for t in cur], np.float32), score)
-    if lists is not None:
-        assert lists == (g["tracked"][f], g["lost"][f]), "frame %d: tracked / lost lists" % f
+NAMES = tc.NAMES["uavmot"]
+load_golden = functools.partial(tc.load_golden, "uavmot")
+new_tracker = functools.partial(tc.new_tracker, UAVMOT)
 
 
 @pytest.mark.parametrize("threads", [64, 256, 1024])
@@ -49,7 +32,7 @@ def test_uavmot_tracker_matches_reference_golden(name, threads):
     for f, d in enumerate(g["dets"]):
         cur = t.update(d, None)
         check = f % 10 == 9 or f == len(g["dets"]) - 1
-        check_frame(g, f, cur, ([x.track_id for x in t.tracked_stracks], [x.track_id for x in t.lost_stracks]) if check else None)
+        tc.check_tracks(cur, g, f, False, ([x.track_id for x in t.tracked_stracks], [x.track_id for x in t.lost_stracks]) if check else None)
 
 
 def test_uavmot_track_views_have_get_xy():
@@ -65,7 +48,7 @@ def test_uavmot_track_views_have_get_xy():
 def test_uavmot_update_without_detection():
     """update_without_detection is ByteTrack's (basetrack.py:489-537): the device step against the host build"""
     g = load_golden("misses")
-    t, host = new_tracker(), UAVHost("uavmot")
+    t, host = new_tracker(), hs.HostSimTracker("uavmot")
     seq = list(g["dets"][:30])
     seq[10:10] = [None, None]
     seq[20:20] = [None]
@@ -102,7 +85,7 @@ def test_uavmot_batch_mixed_with_shared_id_counter_equals_single_runs(threads):
     scores, slots), each of its ids stands for one id of the single run, and no id is handed out twice"""
     from yolov7_tracker_amd import _lib, synth
     L = _lib.load()
-    kinds = [5, 1, 5, 4, 5]
+    kinds = [hs.HostSimTracker.TRACKERS[k] for k in ("uavmot", "bytetrack", "uavmot", "c_biou", "uavmot")]
     nseq, nfr, cap = len(kinds), 25, 512
     seqs = [synth.make_detections(nfr, 20 + 25 * s, seq_idx=70 + s, miss=0.2) for s in range(nseq)]
     nbytes = int(L.y7t_tracker_state_bytes(cap, cap))
@@ -151,7 +134,7 @@ def test_uavmot_batch_mixed_with_shared_id_counter_equals_single_runs(threads):
 def test_uavmot_device_equals_host_build_on_crowds(seed):
     from yolov7_tracker_amd import synth
     dets = synth.make_detections(12, 500, seq_idx=95 + seed, miss=0.15, bounce=True)
-    host = UAVHost("uavmot")
+    host = hs.HostSimTracker("uavmot")
     t = new_tracker(threads=512 if seed != 1 else 256)
     for f, d in enumerate(dets):
         want = host.update(d)
@@ -273,7 +256,7 @@ def test_local_relation_fuse_motion_through_the_device():
 
 def _host_result_lines(dets, min_area=150):
     """the MOT result lines tracker/track.py writes, from the host build's rows"""
-    host = UAVHost("uavmot")
+    host = hs.HostSimTracker("uavmot")
     lines = []
     for f, d in enumerate(dets):
         for tid, b, _, _ in host.update(d):

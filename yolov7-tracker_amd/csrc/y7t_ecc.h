@@ -1,5 +1,5 @@
 // y7t_ecc.h -- camera-motion estimation by ECC maximisation (cv2.findTransformECC, MOTION_EUCLIDEAN, as GMC.applyEcc of the reference calls it:
-// tracker/botsort.py:78-109), stated once for the device kernels (y7t_ecc.hip) and for the CPU build of the same bodies (tests/_hostsim_ecc).
+// tracker/botsort.py:78-109), stated once for the device kernels (y7t_ecc.hip) and for the CPU build of the same bodies (tests/_hostsim/ecc.py).
 // DESIGN.md section 4 "GMC / ECC" is the specification; in short
 //   prepare : BGR uint8 -> gray (round half up) -> 3x3 Gaussian sigma 1.5, reflect-101 (round half up) -> bilinear resize to (W / ds, H / ds), pixel-centre
 //             convention (round half up) -> float32 I; gx, gy with the taps [-0.5, 0, 0.5], reflect-101.  float64 arithmetic in one fixed order, so I is the

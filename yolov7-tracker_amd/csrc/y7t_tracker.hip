@@ -790,23 +790,27 @@ extern "C" int y7t_kf_multi_gmc_f64(double* mean, double* cov, const double* war
     return 0;
 }
 
-// frames with detections of a StrongSORT pool belong to y7t_tracker_step_strongsort (the smoothed appearance vectors): the plain entry points refuse them like a
-// DeepSORT pool's, and say so in the pool's status word too
-// (DeepMOT's frames with detections belong to y7t_tracker_step_deepmot -- the Deep Hungarian Net sits between its two programs: refused the same way)
-static int refuse_deepmot(const char* who, void* state, int* out_count, y7t_stream stream) {
-    hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
-    Y7T_LAUNCH_CHECK();
-    y7t_set_error("%s: this pool was initialised as DeepMOT -- frames with detections go through y7t_tracker_step_deepmot (the Deep Hungarian Net); only the "
-                  "predict-only step (n < 0) is shared", who);
+// a pool of the wrong kind for an entry point: nothing is stepped, the pool's status word says Y7T_ERR_KIND and the frame has 0 rows (k_tracker_refuse), the error text
+// is "<who>: <message>".  state null: no launch (a blob that was never initialised is not touched).  The plain entry points refuse the frames with detections of
+// a StrongSORT pool (they belong to y7t_tracker_step_strongsort: the smoothed appearance vectors) and of a DeepMOT pool (y7t_tracker_step_deepmot: the Deep Hungarian
+// Net sits between its two programs) through this; a DeepSORT pool's they refuse without touching the pool
+static int refuse_pool(const char* who, void* state, int* out_count, y7t_stream stream, const char* fmt, ...) {
+    if (state) {
+        hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
+        Y7T_LAUNCH_CHECK();
+    }
+    char msg[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof(msg), fmt, ap);
+    va_end(ap);
+    y7t_set_error("%s: %s", who, msg);
     return Y7T_E_STATE;
 }
-static int refuse_strongsort(const char* who, void* state, int* out_count, y7t_stream stream) {
-    hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
-    Y7T_LAUNCH_CHECK();
-    y7t_set_error("%s: this pool was initialised as StrongSORT -- frames with detections go through y7t_tracker_step_strongsort (appearance vectors); only the "
-                  "predict-only step (n < 0) is shared", who);
-    return Y7T_E_STATE;
-}
+static const char kRefuseStrongsort[] = "this pool was initialised as StrongSORT -- frames with detections go through y7t_tracker_step_strongsort (appearance vectors); only the "
+                                        "predict-only step (n < 0) is shared";
+static const char kRefuseDeepmot[] = "this pool was initialised as DeepMOT -- frames with detections go through y7t_tracker_step_deepmot (the Deep Hungarian Net); only the "
+                                     "predict-only step (n < 0) is shared";
 
 extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* dets, const int* n_dets, double* const* out_rows,
                                       int* out_count, int out_cap, int batch, int threads, const double* const* gmc_warps,
@@ -840,8 +844,8 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
                       "(appearance rings); only the predict-only step (n < 0) is shared");
         return Y7T_E_STATE;
     }
-    if (n >= 0 && kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step", state, out_count, stream);
-    if (n >= 0 && kind == Y7T_DEEPMOT) return refuse_deepmot("y7t_tracker_step", state, out_count, stream);      // (its predict-only step is the plain program's: default below)
+    if (n >= 0 && kind == Y7T_STRONGSORT) return refuse_pool("y7t_tracker_step", state, out_count, stream, kRefuseStrongsort);
+    if (n >= 0 && kind == Y7T_DEEPMOT) return refuse_pool("y7t_tracker_step", state, out_count, stream, kRefuseDeepmot);      // (its predict-only step is the plain program's: default below)
     const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
     switch (kind) {
     // (predict-only: StrongSORT's own program without a feature state -- its lists may share a track, which its pool holds once, as joint_stracks does)
@@ -864,8 +868,8 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
         y7t_set_error("y7t_tracker_step_frames: a DeepSORT pool steps through y7t_tracker_step_deepsort (appearance rings)");
         return Y7T_E_STATE;
     }
-    if (pool.kind == Y7T_DEEPMOT) return refuse_deepmot("y7t_tracker_step_frames", state, nullptr, stream);
-    if (pool.kind == Y7T_STRONGSORT) return refuse_strongsort("y7t_tracker_step_frames", state, nullptr, stream);      // (the frames' counts are device arrays: none is written)
+    if (pool.kind == Y7T_DEEPMOT) return refuse_pool("y7t_tracker_step_frames", state, nullptr, stream, kRefuseDeepmot);
+    if (pool.kind == Y7T_STRONGSORT) return refuse_pool("y7t_tracker_step_frames", state, nullptr, stream, kRefuseStrongsort);      // (the frames' counts are device arrays: none is written)
     // LDS of the launch: header | fast scratch (cost matrix, assignment work arrays) | the pool's index lists for the length of the launch (y7t_arena_*), when the
     // CU's 160 KiB hold them beside at least 64 KiB of fast scratch (the default capacities, 1024 tracks x 1024 detections: 68 KiB of lists, 91 KiB of scratch)
     static const unsigned kLdsMax = 160 * 1024;
@@ -902,12 +906,9 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const int kind = pool_info(state).kind;
-    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT) {      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
-        hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
-        Y7T_LAUNCH_CHECK();
-        y7t_set_error("y7t_tracker_step_deepsort: this pool was initialised as %s -- it steps through y7t_tracker_step", kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : "StrongSORT (y7t_tracker_step_strongsort)");
-        return Y7T_E_STATE;
-    }
+    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT)      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+        return refuse_pool("y7t_tracker_step_deepsort", state, out_count, stream, "this pool was initialised as %s -- it steps through y7t_tracker_step",
+                           kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : "StrongSORT (y7t_tracker_step_strongsort)");
     if (n > 0) {
         hipLaunchKernelGGL(k_ds_normalize, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats, n);      // a wave per detection
         Y7T_LAUNCH_CHECK();
@@ -943,14 +944,8 @@ extern "C" int y7t_tracker_step_strongsort(void* state, void* feat_state, const 
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const PoolInfo pool = pool_info(state);
-    if (pool.kind != Y7T_STRONGSORT) {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
-        if (pool.kind >= 0) {
-            hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
-            Y7T_LAUNCH_CHECK();
-        }
-        y7t_set_error("y7t_tracker_step_strongsort: this pool was not initialised as StrongSORT (tracker kind %d)", pool.kind);
-        return Y7T_E_STATE;
-    }
+    if (pool.kind != Y7T_STRONGSORT)      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+        return refuse_pool("y7t_tracker_step_strongsort", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as StrongSORT (tracker kind %d)", pool.kind);
     if (n > 0) {
         const int groups = (pool.cap_t + 31) / 32;
         const int vec_ok = (((uintptr_t)feat_state | (uintptr_t)det_feats) & 15) == 0;
@@ -976,14 +971,8 @@ extern "C" int y7t_tracker_step_deepmot(void* state, void* dhn, const float* det
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const PoolInfo pool = pool_info(state);
-    if (pool.kind != Y7T_DEEPMOT) {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
-        if (pool.kind >= 0) {
-            hipLaunchKernelGGL(k_tracker_refuse, dim3(1), dim3(64), 0, S(stream), state, out_count);
-            Y7T_LAUNCH_CHECK();
-        }
-        y7t_set_error("y7t_tracker_step_deepmot: this pool was not initialised as DeepMOT (tracker kind %d)", pool.kind);
-        return Y7T_E_STATE;
-    }
+    if (pool.kind != Y7T_DEEPMOT)      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+        return refuse_pool("y7t_tracker_step_deepmot", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as DeepMOT (tracker kind %d)", pool.kind);
     Y7TDhnView v;
     if (int e = y7t_dhn_view(dhn, &v)) return e;
     const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;

@@ -359,6 +359,13 @@ class BaseTracker(object):
         except Exception:
             pass
 
+    def _out_ptrs(self, out):
+        """-> (rows, count) pointers of a step's result: the tracker's own buffer (out None), or an (cap_t + 1, 8) float64 device tensor whose row cap_t
+        receives the count"""
+        if out is None:
+            return _lib.ptr(self._out), self._count_ptr
+        return _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + self.cap_t * 8 * 8)
+
     def _launch(self, det_results, out=None, n_dev=None, warp=None, staged=False):
         """enqueue one frame step (asynchronous).  out: optional (cap_t + 1, 8) float64 device tensor that receives the
         returned rows (row cap_t holds the count) instead of the tracker's own buffer -- lets a pipeline keep every
@@ -392,10 +399,7 @@ class BaseTracker(object):
             n, dptr = d.shape[0], _lib.ptr(d)
             if n > self.cap_d:
                 raise _lib.Y7TError("%d detections exceed the pool capacity max_dets=%d" % (n, self.cap_d))
-        if out is None:
-            optr, cptr = _lib.ptr(self._out), self._count_ptr
-        else:
-            optr, cptr = _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + self.cap_t * 8 * 8)
+        optr, cptr = self._out_ptrs(out)
         _lib.check(self._L.y7t_tracker_step(_lib.ptr(self._state), dptr, n, optr, self.cap_t, cptr, self.threads, _lib.ptr(warp),
                                             _lib.stream_ptr()))
         self.frame_id += 1

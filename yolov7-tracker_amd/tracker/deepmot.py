@@ -143,11 +143,7 @@ class DeepMOT(BaseTracker):
         if n > self.cap_d:
             raise _lib.Y7TError("%d detections exceed the pool capacity max_dets=%d" % (n, self.cap_d))
         self._det_keep = d
-        if out is None:
-            optr, cptr = _lib.ptr(self._out), self._count_ptr
-        else:
-            import ctypes
-            optr, cptr = _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + self.cap_t * 8 * 8)
+        optr, cptr = self._out_ptrs(out)
         self.frame_id += 1
         self._snap_cache = None
         _lib.check(self._L.y7t_tracker_step_deepmot(_lib.ptr(self._state), self.DHN.ptr, _lib.ptr(d), n, int(img_shape[0]), int(img_shape[1]), optr, self.cap_t, cptr,
