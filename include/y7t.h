@@ -32,6 +32,7 @@ enum { Y7T_KALMAN_DEFAULT = 0, Y7T_KALMAN_NAIVE = 1, Y7T_KALMAN_BOTSORT = 2, Y7T
 /* tracker kinds == TRACKER_DICT keys implemented on the device, tracker/track.py:56-65 */
 enum { Y7T_TRACKER_SORT = 0, Y7T_TRACKER_BYTETRACK = 1, Y7T_TRACKER_BOTSORT = 2, Y7T_TRACKER_DEEPSORT = 3, Y7T_TRACKER_C_BIOU = 4,
        Y7T_TRACKER_UAVMOT = 5, Y7T_TRACKER_STRONGSORT = 6, Y7T_TRACKER_DEEPMOT = 7 };
+#define Y7T_TRACKER_BOTSORT_REID 8      /* BoT-SORT with its appearance branch: a kind of y7t_tracker_init beside the reference's eight tracker names (see below) */
 
 const char* y7t_last_error(void);
 int y7t_version(void);
@@ -222,6 +223,37 @@ size_t y7t_strongsort_feature_bytes(int cap_tracks, int cap_dets, int feat_dim);
 int y7t_strongsort_init(void* feat_state, size_t bytes, int cap_tracks, int cap_dets, int feat_dim, double gamma, y7t_stream stream);
 int y7t_tracker_step_strongsort(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
                                 int* out_count, int threads, const double* gmc_warp, y7t_stream stream);
+
+/* BoT-SORT with its appearance branch (tracker/botsort.py:313-493 with use_apperance_model = True, tracker kind Y7T_TRACKER_BOTSORT_REID; Kalman kind botsort
+ * only; the pool blob has the layout and size of a BoT-SORT pool): the first (0.9) and the unconfirmed (0.7) association solve equations 12-13 of the BoT-SORT
+ * paper, cost = min(IoU distance, App) with App = 0.5 * (1 - cosine of the track's smoothed vector and the detection's vector), App = 1 where the IoU distance
+ * exceeds theta_iou and App = 1 where App exceeds theta_emb (matching.embedding_distance(..., 'cosine'), tracker/matching.py:84-103,165-178: float64 casts of the
+ * float32 vectors, each divided by its np.linalg.norm, then the dot product -- here ONE sequential FMA chain per pair); between them the IoU association at 0.5 of
+ * every unmatched pool track with the low detections.  High detections are score >= conf_thresh; only they carry a vector.  The cost differs from the IoU distance
+ * only on pairs at or under theta_iou, so a cosine is taken for those pairs alone: the step walks its box pairs, files them in a table and evaluates a lane per pair.
+ * Next to the pool the tracker owns a FEATURE STATE (y7t_botsort_reid_feature_bytes, y7t_botsort_reid_init; INTEGRATION.md gives the layout): a 64-byte header that
+ * begins like StrongSORT's (status word at byte 20; the frame's count of cosines evaluated at byte 28, theta_iou / theta_emb at bytes 32 / 40, the count of evaluated
+ * pairs that theta_emb sent to 1 at byte 48), per slot ONE float32 vector (StrongSORT's store: the raw vector of the track's first detection, then the float32
+ * moving average of the normalised vectors; re_activate and a match with a low detection keep it), the pending-store list (two entries per detection), the
+ * frame's normalised float64 rows of the listed tracks and of the high detections, and the pair table of the association in flight.  There is no
+ * cap_tracks x cap_dets matrix.  Status bits: 2 the feature state is smaller than the pool it is stepped with; 4 a vector with zero or non-finite norm among the
+ * frame's rows (the reference hands NaN costs to lapjv there): the frame is NOT stepped, the pool and the vectors stay as they were; 16 more queued vectors than the
+ * list holds; 32 more pairs at or under theta_iou than the table holds (8 per track or detection of the capacities, three quarters used).
+ * y7t_tracker_step_botsort_reid = BoTSORT.update for one frame, n >= 0 known on the host:
+ *   det_feats   n x feat_dim float32, row j = what BoTSORT.get_feature (botsort.py:291-311 -> Extractor: the DeepSORT Net on 128 x 64 crops) returns for detection
+ *               row j, NOT normalised (rows with conf < conf_thresh are never read)
+ *   gmc_warp    the frame's 2x3 camera-motion matrix (6 doubles in DEVICE memory) or NULL; multi_gmc is applied to strack_pool and to the unconfirmed tracks AFTER
+ *               the Kalman prediction (botsort.py:376-382)
+ *   launches (three, on `stream`, nothing is read back): a wave per row for the normalised rows; ONE workgroup for multi_predict, multi_gmc, the three
+ *   associations with their pair passes and cosines, and the list bookkeeping; a wave per queued vector for the moving averages and the raw copies.
+ * update_without_detection: y7t_tracker_step(state, NULL, -1, ...) as for every tracker (the plain program: this pool's lists are disjoint).
+ * Misuse is refused with Y7T_E_STATE and status bit 8 in the pool: y7t_tracker_step with detections and y7t_tracker_step_frames on such a pool
+ * (y7t_tracker_step_batch: status bit 8 and no rows for that pool of the batch, the call returns 0), y7t_tracker_step_deepsort / y7t_tracker_step_strongsort on such
+ * a pool, y7t_tracker_step_botsort_reid on a pool of another kind.  Frames depend on each other through the smoothed vectors: there is no multi-frame or batch form. */
+size_t y7t_botsort_reid_feature_bytes(int cap_tracks, int cap_dets, int feat_dim);
+int y7t_botsort_reid_init(void* feat_state, size_t bytes, int cap_tracks, int cap_dets, int feat_dim, double theta_iou, double theta_emb, y7t_stream stream);
+int y7t_tracker_step_botsort_reid(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
+                                  int* out_count, int threads, const double* gmc_warp, y7t_stream stream);
 
 /* DeepMOT (tracker/deepmot.py:143-324, tracker kind Y7T_TRACKER_DEEPMOT; the pool blob and the Kalman kinds of ByteTrack): ByteTrack whose first association
  * solves 1 - DHN(D) at 0.9, D = matching.ecu_iou_distance(strack_pool, D_high, image shape) cast to float32 and DHN the Deep Hungarian Net (class Munkrs,

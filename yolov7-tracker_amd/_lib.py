@@ -60,6 +60,9 @@ SIGNATURES = {
     "y7t_strongsort_feature_bytes": (c_size_t, [c_int, c_int, c_int]),
     "y7t_strongsort_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_void_p]),
     "y7t_tracker_step_strongsort": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "y7t_botsort_reid_feature_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "y7t_botsort_reid_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_double, c_void_p]),
+    "y7t_tracker_step_botsort_reid": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "y7t_dhn_num_weights": (c_size_t, []),
     "y7t_dhn_weight_bytes": (c_size_t, []),
     "y7t_dhn_workspace_bytes": (c_size_t, [c_int, c_int]),

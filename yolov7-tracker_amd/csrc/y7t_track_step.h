@@ -1461,7 +1461,7 @@ Y7T_FN void y7t_step_one(const Y7TExec& ex, void* blob, const float* dets, int n
             if (ex.tid == 0) { ((Y7TTrkHdr*)blob)->status |= Y7T_ERR_KIND; if (out_count) *out_count = 0; }
         } else y7t_step_one<Y7T_PROG_ANY_SS, false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
     } else if constexpr (PROG == Y7T_PROG_ANY_SS) {
-        if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_STRONGSORT) {      // (its predict-only step too: y7t_tracker_step runs StrongSORT's own program for it)
+        if (((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_STRONGSORT || ((const Y7TTrkHdr*)blob)->cfg.tracker == Y7T_BOTSORT_REID) {      // (StrongSORT's predict-only step too: y7t_tracker_step runs StrongSORT's own program for it; BoT-SORT with ReID: y7t_tracker_step_botsort_reid)
             if (ex.tid == 0) { ((Y7TTrkHdr*)blob)->status |= Y7T_ERR_KIND; if (out_count) *out_count = 0; }
         } else y7t_step_one<Y7T_PROG_ANY, false>(ex, blob, dets, n, out_rows, out_cap, out_count, gmc_warp);
     } else if constexpr (PROG == Y7T_PROG_ANY) {

@@ -159,9 +159,16 @@ Y7T_FN float y7t_ss_wave_sdot_fold(float a5, int lane) {
 
 // write the queued vectors (ex may span a whole grid: on the device a wave per vector); resets nothing -- the next step zeroes the queue.  A detection row is
 // stored at most once per frame and a slot receives at most one vector, so the entries are independent.
+// PPD: the queue holds PPD entries per detection of the capacity (y7t_track_botsort_reid.h: two)
+template <int PPD>
+Y7T_FN int y7t_ss_pend_cap(const Y7TSs& f) {
+    if constexpr (PPD == 1) return f.h->cap_d;
+    else return PPD * f.h->cap_d;
+}
+template <int PPD = 1>
 Y7T_FN void y7t_ss_store_pending(const Y7TExec& ex, const Y7TSs& f, const float* det_feats) {
     const int dim = f.h->dim;
-    const int count = f.h->n_pend < f.h->cap_d ? f.h->n_pend : f.h->cap_d;
+    const int count = f.h->n_pend < y7t_ss_pend_cap<PPD>(f) ? f.h->n_pend : y7t_ss_pend_cap<PPD>(f);
 #if Y7T_DEVICE
     if (y7t_dim_wave_ok(dim) && (ex.nt & 63) == 0) {      // 128 / 256 / 512 / 1024: a lane owns elements lane, lane + 64, ... (at most 16) in registers
         const int lane = ex.tid & 63, nc = dim >> 6;
@@ -201,20 +208,21 @@ Y7T_FN void y7t_ss_store_pending(const Y7TExec& ex, const Y7TSs& f, const float*
 }
 
 // queue the vectors a step decides to store (nothing in the step reads the vectors: this frame's distances were taken before it)
-template <class PairFn>
+template <int PPD = 1, class PairFn>
 Y7T_FN void y7t_ss_queue(const Y7TExec& ex, const Y7TSs& f, int count, int update, PairFn pair /* (i, slot&, detection row&) -> bool */) {
     for (int i = ex.tid; i < count; i += ex.nt) {
         int sl, row;
         if (!pair(i, sl, row)) continue;
         const int k = Y7T_FETCH_ADD(&f.h->n_pend, 1);
-        if (k < f.h->cap_d) { f.pend[3 * k] = sl; f.pend[3 * k + 1] = row; f.pend[3 * k + 2] = update; }
+        if (k < y7t_ss_pend_cap<PPD>(f)) { f.pend[3 * k] = sl; f.pend[3 * k + 1] = row; f.pend[3 * k + 2] = update; }
         else f.h->status |= Y7T_SS_ERR_PEND;
     }
     y7t_sync(ex);
 }
 // ... for the rows of `tracks` that apply_matches UPDATED (tmpa[i] == 1; re_activate keeps the vector)
+template <int PPD = 1>
 Y7T_FN void y7t_ss_queue_updates(const Y7TExec& ex, const Y7TTrk& s, const Y7TSs& f, const int* tracks, int na, const int* dets) {
-    y7t_ss_queue(ex, f, na, 1, [&](int i, int& sl, int& row) {
+    y7t_ss_queue<PPD>(ex, f, na, 1, [&](int i, int& sl, int& row) {
         if (s.xrow[i] < 0 || s.tmpa[i] != 1) return false;
         sl = tracks[i];
         row = dets[s.xrow[i]];

@@ -9,6 +9,7 @@
 #include "y7t_track_step.h"
 #include "y7t_track_deepsort.h"
 #include "y7t_track_strongsort.h"
+#include "y7t_track_botsort_reid.h"
 #include "y7t_track_deepmot.h"
 #include "y7t_dhn.h"
 #include <string.h>
@@ -466,6 +467,37 @@ __global__ void __launch_bounds__(MAXT) k_tracker_step_strongsort(void* state, v
     y7t_tracker_step_strongsort(ex, state, fblob, dets, n, det_feats, out_rows, out_cap, out_count, warp);
 }
 
+// ---- BoT-SORT with its appearance branch (y7t_track_botsort_reid.h): three launches per frame -- k_br_prepare, k_tracker_step_botsort_reid, k_br_store ----
+__global__ void k_br_init(void* fblob, int cap_t, int cap_d, int dim, double theta_iou, double theta_emb) {
+    const Y7TExec ex = make_exec_flat(threadIdx.x, blockDim.x);
+    y7t_br_init(ex, fblob, cap_t, cap_d, dim, theta_iou, theta_emb);
+}
+
+// the frame's normalised float64 rows -- the vectors of the slots of the tracked / lost lists and the detection rows at or above det_thresh -- a wave per row, across
+// the grid (numpy's pairwise sum of squares by the wave's first eight lanes, the divisions a lane per element).  A row that cannot be normalised sets status bit 4
+__global__ void __launch_bounds__(256) k_br_prepare(void* blob, void* fblob, const float* __restrict__ dets, const float* __restrict__ det_feats, int n) {
+    const Y7TTrkHdr* h = (const Y7TTrkHdr*)blob;
+    const Y7TTrk s = y7t_trk_bind(blob, h->cfg.cap_t, h->cfg.cap_d);
+    const Y7TBr f = y7t_br_bind(fblob);
+    if (h->cfg.tracker != Y7T_BOTSORT_REID || f.h->ss.cap_t < h->cfg.cap_t || f.h->ss.cap_d < h->cfg.cap_d) return;      // (the step reports it; nothing is read or written past either state)
+    const Y7TExec ex = make_exec_flat(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    y7t_br_prepare(ex, s, f, dets, det_feats, n);
+}
+
+// the appearance vectors the step queued -> the slots' vectors: StrongSORT's store (y7t_ss_store_pending) on this feature state's queue of two entries per detection
+__global__ void __launch_bounds__(256) k_br_store(void* fblob, const float* __restrict__ det_feats) {
+    const Y7TBr f = y7t_br_bind(fblob);
+    const Y7TExec ex = make_exec_flat(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    y7t_ss_store_pending<Y7T_BR_PPD>(ex, f.ss, det_feats);
+}
+
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT) k_tracker_step_botsort_reid(void* state, void* fblob, const float* dets, int n, const float* det_feats, double* out_rows,
+                                                                     int out_cap, int* out_count, unsigned fast_bytes, const double* warp) {
+    const Y7TExec ex = make_exec(fast_bytes);
+    y7t_tracker_step_botsort_reid(ex, state, fblob, dets, n, det_feats, out_rows, out_cap, out_count, warp);
+}
+
 // ---- DeepMOT (y7t_track_deepmot.h): the two programs of a frame, on either side of the Deep Hungarian Net's launches (y7t_dhn.hip) ----
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_deepmot_front(void* state, const float* dets, int n, int img_h, int img_w, float* D, long long d_cap, int* hw, unsigned fast_bytes) {
@@ -550,6 +582,7 @@ template <int PROG> struct StepFrames { static const int kMinT = 256; template <
 template <int PROG> struct StepBatch { static const int kMinT = 512; template <int MAXT> static constexpr auto k = &k_tracker_step_batch<PROG, MAXT>; };      // (launches of <= 256 threads take the 512 instance)
 struct StepDeepsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_deepsort<MAXT>; };
 struct StepStrongsort { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_strongsort<MAXT>; };
+struct StepBotsortReid { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_tracker_step_botsort_reid<MAXT>; };
 struct StepDeepmotFront { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_deepmot_front<MAXT>; };
 struct StepDeepmotBack { static const int kMinT = 256; template <int MAXT> static constexpr auto k = &k_deepmot_back<MAXT>; };
 
@@ -701,12 +734,13 @@ extern "C" int y7t_lapjv_f64_host(const double* cost_host, int n, int m, double 
 struct PoolInfo { int kind; size_t arena_bytes; int cap_t; };
 static std::mutex g_pool_mu;
 static std::unordered_map<const void*, PoolInfo> g_pools;
-static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0}, g_n_strongsort{0}, g_n_deepmot{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
+static std::atomic<int> g_n_cbiou{0}, g_n_uavmot{0}, g_n_strongsort{0}, g_n_deepmot{0}, g_n_botsort_reid{0};      // noted pools of the kinds a batch launch must branch for (written under g_pool_mu)
 static void count_kind(int kind, int d) {
     if (kind == Y7T_C_BIOU) g_n_cbiou += d;
     else if (kind == Y7T_UAVMOT) g_n_uavmot += d;
     else if (kind == Y7T_STRONGSORT) g_n_strongsort += d;
     else if (kind == Y7T_DEEPMOT) g_n_deepmot += d;
+    else if (kind == Y7T_BOTSORT_REID) g_n_botsort_reid += d;
 }
 static void forget_pool(const void* state) {      // (g_pool_mu held; an address that was never noted changes nothing)
     auto it = g_pools.find(state);
@@ -744,7 +778,7 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
                                 y7t_stream stream) {
     Y7T_ARG_CHECK(state && id_counter && cap_t > 0 && cap_d > 0);
     Y7T_ARG_CHECK(tracker_kind == Y7T_SORT || tracker_kind == Y7T_BYTETRACK || tracker_kind == Y7T_BOTSORT || tracker_kind == Y7T_DEEPSORT ||
-                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT || tracker_kind == Y7T_STRONGSORT || tracker_kind == Y7T_DEEPMOT);
+                  tracker_kind == Y7T_C_BIOU || tracker_kind == Y7T_UAVMOT || tracker_kind == Y7T_STRONGSORT || tracker_kind == Y7T_DEEPMOT || tracker_kind == Y7T_BOTSORT_REID);
     if (tracker_kind == Y7T_C_BIOU) kalman_kind = Y7T_KF_XYAH;      // (C-BIoU has no Kalman filter: the kind is ignored)
     if (tracker_kind == Y7T_DEEPSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("DeepSORT gates on xyah measurements (deepsort.py:59): kalman_format default / strongsort only");
@@ -752,6 +786,10 @@ extern "C" int y7t_tracker_init(void* state, size_t state_bytes, int tracker_kin
     }
     if (tracker_kind == Y7T_STRONGSORT && kalman_kind == Y7T_KF_XYWH) {
         y7t_set_error("StrongSORT fuses the IoU of xyah means (strongsort.py:150, track.py:70-71): kalman_format default / strongsort only");
+        return Y7T_E_ARG;
+    }
+    if (tracker_kind == Y7T_BOTSORT_REID && kalman_kind != Y7T_KF_XYWH) {
+        y7t_set_error("BoT-SORT runs the xywh filter (track.py:68-69): kalman_format botsort only");
         return Y7T_E_ARG;
     }
     if (!kind_ok(kalman_kind)) { y7t_set_error("kalman kind %d is not implemented on the device", kalman_kind); return Y7T_E_ARG; }
@@ -809,6 +847,8 @@ static int refuse_pool(const char* who, void* state, int* out_count, y7t_stream 
 }
 static const char kRefuseStrongsort[] = "this pool was initialised as StrongSORT -- frames with detections go through y7t_tracker_step_strongsort (appearance vectors); only the "
                                         "predict-only step (n < 0) is shared";
+static const char kRefuseBotsortReid[] = "this pool was initialised as BoT-SORT with its appearance branch -- frames with detections go through y7t_tracker_step_botsort_reid "
+                                         "(appearance vectors); only the predict-only step (n < 0) is shared";
 static const char kRefuseDeepmot[] = "this pool was initialised as DeepMOT -- frames with detections go through y7t_tracker_step_deepmot (the Deep Hungarian Net); only the "
                                      "predict-only step (n < 0) is shared";
 
@@ -824,10 +864,10 @@ extern "C" int y7t_tracker_step_batch(void* const* states, const float* const* d
     // needs it (the called copy of the plain program serves C-BIoU)
     const bool uav = g_n_uavmot.load() > 0, any = nt <= 512 ? (uav || g_n_cbiou.load() > 0) : uav;
     const unsigned lds = kFastBytes + Y7T_LDS_HDR;
-    // ... and while a StrongSORT pool exists, the kernel that refuses such a pool (status bit 8; it steps through y7t_tracker_step_strongsort / y7t_tracker_step)
+    // ... and while a StrongSORT pool or one of BoT-SORT with its appearance branch exists, the kernel that refuses such a pool (status bit 8; it steps through y7t_tracker_step_strongsort / y7t_tracker_step)
     // ... and while a DeepMOT pool exists, the one that refuses its frames with detections as well (they step through y7t_tracker_step_deepmot)
     if (g_n_deepmot.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_DM>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
-    if (g_n_strongsort.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_SS>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
+    if (g_n_strongsort.load() > 0 || g_n_botsort_reid.load() > 0) return launch_step<StepBatch<Y7T_PROG_ANY_SS>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     if (any) return launch_step<StepBatch<Y7T_PROG_ANY>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
     return launch_step<StepBatch<Y7T_PROG_PLAIN>>(batch, nt, lds, lds, stream, states, dets, n_dets, out_rows, out_count, out_cap, kFastBytes, gmc_warps);
 }
@@ -845,6 +885,7 @@ extern "C" int y7t_tracker_step(void* state, const float* dets, int n, double* o
         return Y7T_E_STATE;
     }
     if (n >= 0 && kind == Y7T_STRONGSORT) return refuse_pool("y7t_tracker_step", state, out_count, stream, kRefuseStrongsort);
+    if (n >= 0 && kind == Y7T_BOTSORT_REID) return refuse_pool("y7t_tracker_step", state, out_count, stream, kRefuseBotsortReid);      // (its predict-only step is the plain program's: disjoint lists)
     if (n >= 0 && kind == Y7T_DEEPMOT) return refuse_pool("y7t_tracker_step", state, out_count, stream, kRefuseDeepmot);      // (its predict-only step is the plain program's: default below)
     const unsigned fb = step_fast_bytes(n), lds_max = kFastBytes + Y7T_LDS_HDR;
     switch (kind) {
@@ -869,6 +910,7 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
         return Y7T_E_STATE;
     }
     if (pool.kind == Y7T_DEEPMOT) return refuse_pool("y7t_tracker_step_frames", state, nullptr, stream, kRefuseDeepmot);
+    if (pool.kind == Y7T_BOTSORT_REID) return refuse_pool("y7t_tracker_step_frames", state, nullptr, stream, kRefuseBotsortReid);
     if (pool.kind == Y7T_STRONGSORT) return refuse_pool("y7t_tracker_step_frames", state, nullptr, stream, kRefuseStrongsort);      // (the frames' counts are device arrays: none is written)
     // LDS of the launch: header | fast scratch (cost matrix, assignment work arrays) | the pool's index lists for the length of the launch (y7t_arena_*), when the
     // CU's 160 KiB hold them beside at least 64 KiB of fast scratch (the default capacities, 1024 tracks x 1024 detections: 68 KiB of lists, 91 KiB of scratch)
@@ -906,9 +948,9 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     const int nt = step_threads(threads, n);
     Y7T_ARG_CHECK(nt > 0);
     const int kind = pool_info(state).kind;
-    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT)      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT || kind == Y7T_BOTSORT_REID)      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
         return refuse_pool("y7t_tracker_step_deepsort", state, out_count, stream, "this pool was initialised as %s -- it steps through y7t_tracker_step",
-                           kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : "StrongSORT (y7t_tracker_step_strongsort)");
+                           kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : kind == Y7T_BOTSORT_REID ? "BoT-SORT with ReID (y7t_tracker_step_botsort_reid)" : "StrongSORT (y7t_tracker_step_strongsort)");
     if (n > 0) {
         hipLaunchKernelGGL(k_ds_normalize, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats, n);      // a wave per detection
         Y7T_LAUNCH_CHECK();
@@ -956,6 +998,44 @@ extern "C" int y7t_tracker_step_strongsort(void* state, void* feat_state, const 
     if (int e = launch_step<StepStrongsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, gmc_warp)) return e;
     if (n > 0) {
         hipLaunchKernelGGL(k_ss_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most one per detection)
+        Y7T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" size_t y7t_botsort_reid_feature_bytes(int cap_t, int cap_d, int feat_dim) {
+    if (cap_t <= 0 || cap_d <= 0 || feat_dim <= 0 || feat_dim > 65536) return 0;
+    return y7t_br_layout(cap_t, cap_d, feat_dim).total;
+}
+
+extern "C" int y7t_botsort_reid_init(void* feat_state, size_t bytes, int cap_t, int cap_d, int feat_dim, double theta_iou, double theta_emb, y7t_stream stream) {
+    Y7T_ARG_CHECK(feat_state && cap_t > 0 && cap_d > 0 && feat_dim > 0 && feat_dim <= 65536);
+    Y7T_ARG_CHECK((long long)cap_t * cap_d < (1ll << 31));      // (a pair's table key is row * columns + column)
+    Y7T_ARG_CHECK(theta_iou < 1.0);                             // (a pair of boxes apart costs exactly 1 and takes no cosine: what the pair pass is built on)
+    Y7T_ARG_CHECK(bytes >= y7t_br_layout(cap_t, cap_d, feat_dim).total);
+    hipLaunchKernelGGL(k_br_init, dim3(1), dim3(64), 0, S(stream), feat_state, cap_t, cap_d, feat_dim, theta_iou, theta_emb);
+    Y7T_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int y7t_tracker_step_botsort_reid(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap,
+                                             int* out_count, int threads, const double* gmc_warp, y7t_stream stream) {
+    Y7T_ARG_CHECK(state && feat_state && out_rows && out_count && out_cap >= 0 && n >= 0);
+    Y7T_ARG_CHECK(n == 0 || (dets && det_feats));
+    const int nt = step_threads(threads, n);
+    Y7T_ARG_CHECK(nt > 0);
+    const PoolInfo pool = pool_info(state);
+    if (pool.kind != Y7T_BOTSORT_REID)      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+        return refuse_pool("y7t_tracker_step_botsort_reid", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as BoT-SORT with its appearance branch (tracker kind %d)", pool.kind);
+    if (n > 0) {   // a wave per row: the live slots (at most cap_tracks) and the frame's detections; a frame without detections takes no cosine
+        const int rows = pool.cap_t + n, blocks = (rows + 3) / 4;
+        hipLaunchKernelGGL(k_br_prepare, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n);
+        Y7T_LAUNCH_CHECK();
+    }
+    const unsigned fb = step_fast_bytes(n);
+    if (int e = launch_step<StepBotsortReid>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, gmc_warp)) return e;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_br_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most two per detection)
         Y7T_LAUNCH_CHECK();
     }
     return 0;

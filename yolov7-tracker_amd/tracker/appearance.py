@@ -13,11 +13,40 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .basetrack import BaseTracker
+from .basetrack import BaseTracker, _PoolTrack
+
+
+class _VectorPoolTrack(_PoolTrack):
+    """View of one slot of a device pool whose feature state keeps ONE float32 vector per slot (StrongSORT, BoT-SORT with its appearance branch): `features` is
+    the list with the track's smoothed vector, read from the feature state."""
+
+    @property
+    def features(self):
+        v = self._pool._vector(self._slot, self.track_id)
+        return [] if v is None else [v]
+
+    @features.setter
+    def features(self, value):      # (the views are built with an empty list)
+        pass
+
+    @property
+    def smooth_feat(self):
+        f = self.features
+        return f[0] if f else None
+
+    @property
+    def has_feature(self):
+        return bool(self.features)
+
+    @has_feature.setter
+    def has_feature(self, value):
+        pass
 
 
 class AppearanceTracker(BaseTracker):
-    _KALMAN_NOTE = ""       # why the tracker needs an xyah filter (kalman_format default / strongsort)
+    _KALMAN_FORMATS = ("default", "strongsort")      # the kalman_format values the tracker's device program accepts
+    _KALMAN_NOTE = ""       # why the tracker needs these filters
+    _FEATURE_AT_THRESHOLD = False      # a detection gets a feature when its score is > det_thresh (deepsort.py:98, strongsort.py:110); True: >= (botsort.py:339)
     _REID_ARCHS = {}        # "random:<arch>" -> ReIDExtractor keyword arguments; the first is what a bare "random" means
     _REID_ARCH_NOTE = ""    # the accepted forms of a "random" reid_model_path, for the error message
     _REID_CKPT = {}         # ReIDExtractor.from_checkpoint keyword arguments
@@ -26,8 +55,8 @@ class AppearanceTracker(BaseTracker):
 
     def __init__(self, opts, frame_rate=30, reid_model=None):
         name = type(self).__name__
-        if getattr(opts, "kalman_format", "default") not in ("default", "strongsort"):
-            raise NotImplementedError("%s %s: kalman_format default / strongsort" % (name, self._KALMAN_NOTE))
+        if getattr(opts, "kalman_format", "default") not in self._KALMAN_FORMATS:
+            raise NotImplementedError("%s %s: kalman_format %s" % (name, self._KALMAN_NOTE, " / ".join(self._KALMAN_FORMATS)))
         super().__init__(opts, frame_rate=frame_rate)
         self.reid_model = reid_model if reid_model is not None else getattr(opts, "reid_model", None)
         path = getattr(opts, "reid_model_path", None)
@@ -130,7 +159,8 @@ class AppearanceTracker(BaseTracker):
         n = det_host.shape[0]
         if n > self.cap_d:
             raise _lib.Y7TError("%d detections exceed the pool capacity max_dets=%d" % (n, self.cap_d))
-        keep = det_host[:, 4] > np.float32(self.det_thresh)            # deepsort.py:98, strongsort.py:110: only these get features
+        thr = np.float32(self.det_thresh)                              # deepsort.py:98, strongsort.py:110, botsort.py:339: only these get features
+        keep = det_host[:, 4] >= thr if self._FEATURE_AT_THRESHOLD else det_host[:, 4] > thr
         feats = None
         if keep.any():
             feats = self.get_feature(det_host[keep, :4], ori_img)
@@ -152,3 +182,25 @@ class AppearanceTracker(BaseTracker):
         if st:
             raise _lib.Y7TError("%s feature state overflow (status %d)%s" % (type(self).__name__, st, self._OVERFLOW_NOTE))
         return rows
+
+
+class OneVectorViews:
+    """host views of a feature state that keeps ONE float32 vector per slot behind a 64-byte header (y7t_ss_layout, y7t_br_layout): mixed into the tracker class,
+    which sets `_vec_cache = None` in its constructor and after every step"""
+    _VIEW = _VectorPoolTrack
+
+    def _vectors(self):
+        """(cap_t, D) float32 host copy of the slots' vectors (cached until the next step)"""
+        if self._vec_cache is None and self._feat is not None:
+            off = 64                                                     # the vectors follow the 64-byte header
+            raw = self._feat[off:off + 4 * self.cap_t * self._feat_dim].cpu().numpy()
+            self._vec_cache = raw.view(np.float32).reshape(self.cap_t, self._feat_dim)
+        return self._vec_cache
+
+    def _vector(self, slot, track_id):
+        if self._feat is None or not self._feat_used or self._snapshot()["tid"][slot] != track_id:
+            return None
+        return self._vectors()[slot].copy()
+
+    def _views(self, list_name, n_name):
+        return [_VectorPoolTrack(t._pool, t._slot, t.track_id, t._tlwh_now, t.cls, t.score) for t in super()._views(list_name, n_name)]

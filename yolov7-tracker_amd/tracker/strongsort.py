@@ -15,44 +15,17 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .appearance import AppearanceTracker
+from .appearance import AppearanceTracker, OneVectorViews, _VectorPoolTrack as _SSPoolTrack  # noqa: F401
 from .botsort import _device_warp
 from .basetrack import STrack, TrackState, _PoolTrack, joint_stracks, sub_stracks, remove_duplicate_stracks  # noqa: F401
 
 REID_SIZE = (256, 128)      # (W, H): cv2.resize(..., dsize=(256, 128)), strongsort.py:56
 
 
-class _SSPoolTrack(_PoolTrack):
-    """View of one slot of a StrongSORT device pool: `features` is the list with the track's one smoothed float32 vector, read from the feature state."""
-
-    @property
-    def features(self):
-        v = self._pool._vector(self._slot, self.track_id)
-        return [] if v is None else [v]
-
-    @features.setter
-    def features(self, value):      # (the views are built with an empty list)
-        pass
-
-    @property
-    def smooth_feat(self):
-        f = self.features
-        return f[0] if f else None
-
-    @property
-    def has_feature(self):
-        return bool(self.features)
-
-    @has_feature.setter
-    def has_feature(self, value):
-        pass
-
-
-class StrongSORT(AppearanceTracker):
+class StrongSORT(OneVectorViews, AppearanceTracker):
     """strongsort.py:20-250.  opts: conf_thresh, track_buffer, kalman_format (default / strongsort; tracker/track.py sets strongsort), img_size,
     reid_model_path (+ the optional capacities of BaseTracker)."""
     _KIND = 6  # Y7T_TRACKER_STRONGSORT
-    _VIEW = _SSPoolTrack
     _KALMAN_NOTE = "fuses the IoU of xyah means (strongsort.py:150)"
     _REID_ARCHS = {"osnet": dict(size=REID_SIZE, max_crops=128)}
     _REID_ARCH_NOTE = "random or random:osnet (strongsort.py:26: osnet_x0_25)"
@@ -102,20 +75,3 @@ class StrongSORT(AppearanceTracker):
                           "running WITHOUT compensation, results on moving-camera footage will differ from the reference", RuntimeWarning)
             StrongSORT._warned = True
         return _device_warp(warp, self._warp) if warp is not None and self.use_ECC else None
-
-    # -- host views of the feature state ---------------------------------------------------------
-    def _vectors(self):
-        """(cap_t, D) float32 host copy of the slots' vectors (cached until the next step)"""
-        if self._vec_cache is None and self._feat is not None:
-            off = 64                                                     # the vectors follow the 64-byte header (y7t_ss_layout)
-            raw = self._feat[off:off + 4 * self.cap_t * self._feat_dim].cpu().numpy()
-            self._vec_cache = raw.view(np.float32).reshape(self.cap_t, self._feat_dim)
-        return self._vec_cache
-
-    def _vector(self, slot, track_id):
-        if self._feat is None or not self._feat_used or self._snapshot()["tid"][slot] != track_id:
-            return None
-        return self._vectors()[slot].copy()
-
-    def _views(self, list_name, n_name):
-        return [_SSPoolTrack(t._pool, t._slot, t.track_id, t._tlwh_now, t.cls, t.score) for t in super()._views(list_name, n_name)]

@@ -8,6 +8,7 @@ device-resident SORT / ByteTrack trackers.
 Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / arch name for state-dict checkpoints),
 --nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch,
 --gmc {none,ecc} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
+--botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
 """
 import argparse
 import os
@@ -90,6 +91,9 @@ def main(opts, cfgs):
         opts.kalman_format = 'botsort'      # track.py:68-69
     elif opts.tracker == 'strongsort':
         opts.kalman_format = 'strongsort'   # track.py:70-71
+    botsort_reid = bool(getattr(opts, 'botsort_reid', False))
+    if botsort_reid and opts.tracker != 'botsort':
+        raise ValueError("--botsort_reid: the appearance branch belongs to --tracker botsort (tracker %r has none to switch)" % (opts.tracker,))
     if opts.gmc != 'none' and opts.tracker not in ('strongsort', 'botsort'):
         raise ValueError("--gmc %s: only strongsort and botsort compensate camera motion (tracker %r does not)" % (opts.gmc, opts.tracker))
     img_size = opts.img_size[0] if isinstance(opts.img_size, (list, tuple)) else opts.img_size
@@ -118,7 +122,8 @@ def main(opts, cfgs):
                                                       device_preprocess=opts.device_preprocess,
                                                       yolo_data_root=cfgs.get('YOLO_DATA_ROOT', DATASET_ROOT))
         data_loader = torch.utils.data.DataLoader(loader, batch_size=max(1, opts.batch))
-        tracker = TRACKER_DICT[opts.tracker](opts, frame_rate=30, gamma=opts.gamma)
+        # (extension) --botsort_reid: BoTSORT's use_apperance_model, which the reference hard-codes to False (botsort.py:276)
+        tracker = TRACKER_DICT[opts.tracker](opts, frame_rate=30, gamma=opts.gamma, **({'use_apperance_model': True} if botsort_reid else {}))
         if opts.gmc == 'ecc':      # (extension) estimate the camera motion on the device; one estimator per sequence, like the reference's per-tracker GMC
             from .gmc import GMC
             estimator = GMC('ecc', faithful=bool(opts.gmc_faithful))
@@ -225,6 +230,9 @@ def build_parser():
     parser.add_argument('--device_preprocess', action='store_true', help='(extension) letterbox raw frames on the GPU instead of in the loader')
     parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc'],
                         help='(extension) camera-motion estimate for strongsort / botsort: ecc = findTransformECC on the device (tracker/gmc.py)')
+    parser.add_argument('--botsort_reid', action='store_true',
+                        help="(extension) --tracker botsort with its appearance branch (use_apperance_model, off in the reference): IoU-gated cosine fusion with "
+                             "--reid_model_path features")
     parser.add_argument('--gmc_faithful', type=int, default=1, choices=[0, 1],
                         help="(extension) 1 = the reference's applyEcc as written (every frame aligned to frame 0, half-resolution translation); "
                              "0 = previous-frame template, full-resolution translation")
