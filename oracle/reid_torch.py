@@ -59,10 +59,11 @@ def _osblock(x, sd, name):
 
 
 @torch.no_grad()
-def osnet_forward(sd, x, layers=(2, 2, 2)):
-    """x: (N, 3, H, W) float32 -> (N, feature_dim) (OSNet.forward, eval mode)"""
-    sd = {k: v.float() for k, v in sd.items()}
-    x = _conv_layer(x.float(), sd, "conv1", 2, 3)
+def osnet_forward(sd, x, layers=(2, 2, 2), dtype=torch.float32):
+    """x: (N, 3, H, W) float32 -> (N, feature_dim) (OSNet.forward, eval mode); dtype=torch.float64 evaluates the same float32 parameters in double precision
+    (how far the float32 oracle itself is from the exact network: tests/test_op_refs_cpu.py)"""
+    sd = {k: v.to(dtype) for k, v in sd.items()}
+    x = _conv_layer(x.to(dtype), sd, "conv1", 2, 3)
     x = F.max_pool2d(x, 3, 2, 1)
     for si, nblk in enumerate(layers):
         stage = "conv%d" % (si + 2)

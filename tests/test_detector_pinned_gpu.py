@@ -133,10 +133,8 @@ def test_launch_list_is_the_benchmarked_one(bench_det):
 
 
 def test_every_op_matches_the_oracle_teacher_forced(bench_det):
-    from oracle import detector_torch as dt
     det, frames_host, _ = bench_det
     p = det.plan
-    sd = det._sd
     torch.set_num_threads(min(32, torch.get_num_threads() if torch.get_num_threads() > 1 else 32))
     fr = CHECK_FRAMES
     # op 0's input: the layout kernel (BGR -> RGB, /255, ReOrg, fp16) against the oracle's ReOrg of the float image
@@ -146,69 +144,14 @@ def test_every_op_matches_the_oracle_teacher_forced(bench_det):
     if not p.stem_fused:                                            # (fused stem: the layout tensor is never written -- the stem's OUTPUT is checked below)
         got0 = _slice(det, 0, p.in_ld, 0, p.in_ld, 640, 640, fr).float().cpu()
         assert torch.equal(got0[..., :12], re16.permute(0, 2, 3, 1)) and float(got0[..., 12:].abs().max()) == 0.0
-    ci = 0
     names = det.launch_list(B_BENCH)
     det(torch.from_numpy(frames_host).cuda())
     torch.cuda.synchronize()
-    worst = collections.defaultdict(float)
-    n_conv = n_other = n_up = 0
-    for oi, op in enumerate(p.ops):
-        H, W, Cin = int(op["H"]), int(op["W"]), int(op["Cin"])
-        if oi == 0 and int(op["in_buf"]) == 0:
-            x = re16.clone()                                        # op 0 reads the frame: BGR -> RGB, /255, ReOrg, fp16 (whether or not that tensor exists in HBM)
-        else:
-            x = _slice(det, int(op["in_buf"]), int(op["in_ld"]), int(op["in_coff"]), Cin, H, W, fr).float().cpu().permute(0, 3, 1, 2).contiguous()
-        if int(op["up_C"]) > 0:      # upsample-on-read: these channels of the concat exist only at half resolution (nn.Upsample(None, 2, 'nearest'))
-            c0, cu = int(op["up_c0"]), int(op["up_C"])
-            lo = _slice(det, int(op["up_buf"]), int(op["up_ld"]), int(op["up_coff"]), cu, H // 2, W // 2, fr).float().cpu().permute(0, 3, 1, 2)
-            x[:, c0:c0 + cu] = F.interpolate(lo, scale_factor=2, mode="nearest")
-            n_up += 1
-        if int(op["type"]) == 0:
-            wl = p.wlayout[ci]
-            ci += 1
-            x = x[:, :wl["cin"]]                                   # the stem's 12 real channels of the 16-channel layout
-            k, s_, pd = int(op["KH"]), int(op["stride"]), int(op["pad"])
-            extra_tol = 0.0
-            if wl["kind"] == "conv" and wl.get("fused_next"):      # korder 11: the stride-2 layer + the twin 1x1 behind it in one launch; the tensor between them is never written
-                w2 = p.wlayout[ci]
-                ci += 1
-                assert int(op["korder"]) == 11 and w2.get("fused_prev") and isinstance(w2["wkey"], tuple)
-                mid = dt._conv_bn_act(x, sd, wl["wkey"], k, s_, pd, wl["act"], fp16=True, round_out=True)        # (fp16 in LDS, as it would be in memory)
-                ref = torch.cat([dt._conv_bn_act(mid, sd, key, 1, 1, 0, w2["act"], fp16=True, round_out=False) for key in w2["wkey"]], 1)
-                absum = torch.cat([dt.conv_abs_sum(mid, sd, key, 1, 0) for key in w2["wkey"]], 1)
-                extra_tol = 2.0 ** -11      # a 1-ulp difference of a middle value (other summation order) times its weight: bounded by 2^-11 sum |w x|
-                got = _slice(det, int(op["out_buf"]), int(op["out_ld"]), int(op["out_coff"]), int(op["Cout"]), int(op["Ho"]), int(op["Wo"]), fr)
-                got = got.float().cpu()
-            elif wl["kind"] == "conv":
-                keys = wl["wkey"] if isinstance(wl["wkey"], tuple) else (wl["wkey"],)
-                ref = torch.cat([dt._conv_bn_act(x, sd, key, k, s_, pd, wl["act"], fp16=True, round_out=False) for key in keys], 1)
-                absum = torch.cat([dt.conv_abs_sum(x, sd, key, s_, pd) for key in keys], 1)      # sum_k |w_k x_k| (+ |b|) per output
-                got = _slice(det, int(op["out_buf"]), int(op["out_ld"]), int(op["out_coff"]), int(op["Cout"]), int(op["Ho"]), int(op["Wo"]), fr)
-                got = got.float().cpu()
-            else:                                                   # Detect 1x1 (models/yolo.py:46): fp16 weights, fp32 bias, fp32 output
-                ref = F.conv2d(x, sd[wl["wkey"] + ".weight"].half().float(), sd[wl["wkey"] + ".bias"].float())
-                absum = F.conv2d(x.abs(), sd[wl["wkey"] + ".weight"].half().float().abs(), sd[wl["wkey"] + ".bias"].float().abs())
-                got = det.head_tensor(wl["level"], B_BENCH)[fr].cpu()
-            ref, absum = ref.permute(0, 2, 3, 1), absum.permute(0, 2, 3, 1)
-            err = (got - ref).abs()
-            tol = 3e-4 + 6e-4 * ref.abs() + (2 * float(Cin * k * k) ** 0.5 * 2.0 ** -24 + extra_tol) * absum      # |SiLU'| <= 1.1: the pre-activation bound carries over
-            bad = err > tol
-            if bool(bad.any()):
-                w_ = int(torch.argmax((err / tol).flatten()))
-                detail = "got %.6g ref %.6g sum|wx| %.4g tol %.3g" % (float(got.flatten()[w_]), float(ref.flatten()[w_]), float(absum.flatten()[w_]), float(tol.flatten()[w_]))
-            assert not bool(bad.any()), "op %d %s (%s, %dx%d %d->%d k%d s%d): %d values off, worst err/tol %.2f [%s]" % (
-                oi, names[oi], wl["wkey"], H, W, Cin, int(op["Cout"]), k, s_, int(bad.sum()), float((err / tol).max()), detail)
-            worst[names[oi]] = max(worst[names[oi]], float((err / tol).max()))
-            n_conv += 1
-        else:
-            if int(op["type"]) == 1:
-                ref = F.interpolate(x, scale_factor=2, mode="nearest")                     # nn.Upsample(None, 2, 'nearest')
-            else:
-                ref = F.max_pool2d(x, int(op["KH"]), int(op["stride"]), int(op["pad"]))  # SPPCSPC pools (cascaded), concat copies (k = 1)
-            got = _slice(det, int(op["out_buf"]), int(op["out_ld"]), int(op["out_coff"]), Cin, ref.shape[2], ref.shape[3], fr).float().cpu()
-            assert torch.equal(got, ref.permute(0, 2, 3, 1)), "op %d %s" % (oi, names[oi])
-            n_other += 1
-    assert ci == len(p.wlayout) and n_conv >= 95 and n_other + n_up >= 6 and n_up == 3      # w6: all three upsamples are read through
+    from tests import teacher_forced
+    r = teacher_forced.check_every_op(det, B_BENCH, fr, re16, names)      # the per-op loop (shared with tests/test_tiny_pinned_gpu.py): it asserts every op, and that every weight entry was consumed
+    n_conv, n_other, n_up, worst = r["n_conv"], r["n_other"], r["n_up"], r["worst"]
+    assert r["visited"] == list(range(len(p.ops)))
+    assert n_conv >= 95 and n_other + n_up >= 6 and n_up == 3      # w6: all three upsamples are read through
     print("per-op worst err / tol by kernel:", {k: "%.2e" % v for k, v in sorted(worst.items())})
 
 
