@@ -361,7 +361,9 @@ int y7t_input_layout(const void* img, int is_u8, int B, int H, int W, int reorg,
  * y7t_det_stem_fusable): raw (B, H0, W0, 3) uint8 BGR frames -> TrackerLoader._letterbox (resize INTER_LINEAR to new_w x new_h at (top, left)
  * of the H x W network input, pad 114; new == source: no resampling) -> BGR->RGB, /255 -> ReOrg -> stem Conv + bias + activation, i.e. what
  * y7t_letterbox_layout_u8 / y7t_input_layout followed by op 0 compute, without the fp16 layout tensor in between.  Continue with
- * y7t_det_forward_ops / y7t_det_forward_fused from op 1. */
+ * y7t_det_forward_ops / y7t_det_forward_fused from op 1.
+ * Refusals, nothing written: Y7T_E_STATE if op 0 is not such a stem; Y7T_E_ARG if the plan's image (2 x op 0's map) is no multiple of 32 in H or W (the kernel
+ * walks whole 16 x 16 tiles; y7t_det_stem_fusable answers 0 for such a plan), if top + new_h or left + new_w leaves that image, or if B exceeds max_batch. */
 int y7t_det_stem_fusable(const y7t_det* det);
 int y7t_det_forward_stem_u8(y7t_det* det, const void* frames_u8, int B, int H0, int W0, int new_h, int new_w, int top, int left, y7t_stream stream);
 

@@ -4,9 +4,17 @@ numpy restatement of the reference's frame pre-processing, /root/reference/track
 `_letterbox` (scale ratio, `auto=True` padding to the stride multiple, cv2.resize INTER_LINEAR, cv2.copyMakeBorder 114) and the
 BGR->RGB / CHW / float32 / 255 tail of `__getitem__`.
 
-PARITY UNPINNED for the resize itself: cv2 is not installed here and the reference has no fixture for it.  This restates
-cv2.INTER_LINEAR's geometry (half-pixel centres, edge-clamped taps) in float arithmetic with rounding to uint8; OpenCV's
-own 8-bit path uses 11-bit fixed-point weights, which can differ from this by one grey level on rounding ties.
+What is pinned for the resize (tests/preproc_ref.py, tests/test_preprocess_cpu.py, tests/test_preprocess_gpu.py):
+  * `resize_bilinear` == the device samplers k_letterbox_layout and k_stem_u8, bit for bit: the same sequence of IEEE float32 operations (the device files are
+    compiled without FMA contraction), checked on up- and downscaled, odd-sized, one-row and one-column frames, on noise and on smooth images.  The host
+    loader's `_resize_linear` (yolov7_tracker_amd/tracker/tracker_dataloader.py) is this expression written out a second time, so its equality with this one is a
+    guard against the two copies drifting apart, not evidence for either;
+  * all of them == rint of the same formula evaluated in float64 wherever that value is further from a rounding tie than an a-priori bound on the float32
+    error (the "decided" pixels, 95-100 % of them), and within one grey level elsewhere; at scale 2, 1/2 and 3/2 the float32 arithmetic is exact and every
+    value is equal, ties rounded half to even.
+PARITY STILL UNPINNED: OpenCV itself.  cv2 is not installed here and the reference has no fixture for it.  This restates cv2.INTER_LINEAR's geometry (half-pixel
+centres, edge-clamped taps) in float arithmetic with rounding to uint8; OpenCV's own 8-bit path uses 11-bit fixed-point weights and rounds half up, so it can
+differ from this by one grey level near rounding ties -- on the exact x2 shrink at every tie whose floor is even.
 """
 import numpy as np
 
@@ -29,7 +37,9 @@ def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scale
     top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
     left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
     out = np.empty((img.shape[0] + top + bottom, img.shape[1] + left + right, 3), np.uint8)
-    out[...] = np.asarray(color, np.uint8)
+    row = np.empty((out.shape[1], 3), np.uint8)
+    row[...] = np.asarray(color, np.uint8)
+    out[...] = row                      # whole rows of the pad colour: 20 times faster at 1280 x 1280 than broadcasting the three bytes over every pixel
     out[top:top + img.shape[0], left:left + img.shape[1]] = img
     return out
 

@@ -11,6 +11,12 @@ import torch
 import torch.nn.functional as F
 
 
+def conv_tolerance(ref, absum, K, extra_tol=0.0):
+    """the convolution bar of the module docstring for a result `ref` of K-term sums with sum_k |w_k x_k| = absum (|act'| <= 1.1 (SiLU; LeakyReLU 1): the pre-activation
+    bound carries over)"""
+    return 3e-4 + 6e-4 * ref.abs() + (2 * float(K) ** 0.5 * 2.0 ** -24 + extra_tol) * absum
+
+
 def arena_slice(det, B, buf, ld, coff, c, H, W, frames):
     v = det.buffer_view(buf, B, ld).view(B, H, W, ld)
     return v[frames][..., coff:coff + c]
@@ -65,7 +71,7 @@ def check_every_op(det, B, frames, x0, names):
                 got = det.head_tensor(wl["level"], B)[fr].cpu()
             ref, absum = ref.permute(0, 2, 3, 1), absum.permute(0, 2, 3, 1)
             err = (got - ref).abs()
-            tol = 3e-4 + 6e-4 * ref.abs() + (2 * float(Cin * k * k) ** 0.5 * 2.0 ** -24 + extra_tol) * absum      # |act'| <= 1.1 (SiLU; LeakyReLU 1): the pre-activation bound carries over
+            tol = conv_tolerance(ref, absum, Cin * k * k, extra_tol)
             bad = err > tol
             if bool(bad.any()):
                 w_ = int(torch.argmax((err / tol).flatten()))

