@@ -292,7 +292,7 @@ const char* y7t_tracker_field_name(int i);
  * (models/yolo.py:321-351 forward_once over the yaml layer list, models/yolo.py:443-520 parse_model) into a
  * static launch list over a pre-planned NHWC fp16 activation arena: concat is eliminated (producers write
  * channel slices), BN is folded (utils/torch_utils.py:181-201), weights are packed [Cout_pad][K_pad] fp16. */
-enum { Y7T_OP_CONV = 0, Y7T_OP_UPSAMPLE2X = 1, Y7T_OP_MAXPOOL = 2 };
+enum { Y7T_OP_CONV = 0, Y7T_OP_UPSAMPLE2X = 1, Y7T_OP_MAXPOOL = 2, Y7T_OP_ADD = 3 };
 typedef struct y7t_op {
     int32_t type;
     int32_t in_buf, in_ld, in_coff;     /* arena buffer id, channels of that buffer, first channel of the slice */
@@ -315,7 +315,10 @@ typedef struct y7t_op {
     int64_t bias_off;                   /* element offset into the fp32 bias blob */
     /* upsample-on-read (1x1 / stride 1 convs; cfg/deploy/yolov7-w6.yaml:75,89,103: nn.Upsample feeds only a Concat whose consumers are
      * 1x1 convs): channels [up_c0, up_c0 + up_C) of the input slice are not stored at this resolution -- pixel (y, x) reads
-     * buffer up_buf (H/2 x W/2, up_ld channels, slice starting at up_coff) at (y >> 1, x >> 1).  up_C == 0: off. */
+     * buffer up_buf (H/2 x W/2, up_ld channels, slice starting at up_coff) at (y >> 1, x >> 1).  up_C == 0: off.
+     * Y7T_OP_ADD (Shortcut, models/common.py:80-86: out = a + b, half(float(a) + float(b))) reuses the three fields for its SECOND operand: b is the slice
+     * [up_coff, up_coff + Cin) of buffer up_buf with up_ld channels, at the same H x W as the first operand (in_*) and the output; up_c0 / up_C stay 0.  Cin, every
+     * ld and every coff must be multiples of 8 and the output slice must not overlap an operand's slice in the same buffer (Y7T_E_ARG, nothing written). */
     int32_t up_buf, up_ld, up_coff, up_c0, up_C, pad0;
 } y7t_op;                               /* sizeof == 136 */
 

@@ -36,7 +36,8 @@ extern "C" int y7t_det_create(const y7t_op* ops, int n_ops, const int64_t* bufs,
     Y7T_ARG_CHECK(ops && n_ops > 0 && bufs && n_bufs > 0 && arena && w && bias && out && max_batch > 0);
     for (int i = 0; i < n_ops; ++i) {
         Y7T_ARG_CHECK(ops[i].in_buf >= 0 && ops[i].in_buf < n_bufs && ops[i].out_buf >= 0 && ops[i].out_buf < n_bufs);
-        Y7T_ARG_CHECK(ops[i].type >= Y7T_OP_CONV && ops[i].type <= Y7T_OP_MAXPOOL);
+        Y7T_ARG_CHECK(ops[i].type >= Y7T_OP_CONV && ops[i].type <= Y7T_OP_ADD);
+        if (ops[i].type == Y7T_OP_ADD) Y7T_ARG_CHECK(ops[i].up_buf >= 0 && ops[i].up_buf < n_bufs);      // the second operand
     }
     for (int i = 0; i < n_bufs; ++i) Y7T_ARG_CHECK(bufs[i] >= 0 && (size_t)bufs[i] < arena_bytes && bufs[i] % 256 == 0);
     y7t_det* d = new y7t_det();
@@ -153,6 +154,10 @@ static int forward_impl(y7t_det* d, int B, int first, int last, const Y7TFused* 
             }
         } else if (op.type == Y7T_OP_UPSAMPLE2X) {
             rc = y7t_upsample_launch(in, op.in_ld, op.in_coff, B, op.H, op.W, op.Cin, (_Float16*)outp, op.out_ld, op.out_coff, s);
+        } else if (op.type == Y7T_OP_ADD) {
+            // Shortcut (models/common.py:80-86): the second operand travels in up_buf / up_ld / up_coff; H, W, Cin describe both operands and the output
+            rc = y7t_add_launch(in, op.in_ld, op.in_coff, (const _Float16*)(d->arena + d->bufs[op.up_buf]), op.up_ld, op.up_coff, B, op.H, op.W, op.Cin, (_Float16*)outp,
+                                op.out_ld, op.out_coff, s);
         } else {
             // SPPCSPC (models/common.py:262-280): three 5 x 5 / 1 pools in cascade, each reading its predecessor's slice and writing the next slice of the same concat
             // buffer -> one launch that keeps the slab in LDS (when the whole chain is inside the requested op range)

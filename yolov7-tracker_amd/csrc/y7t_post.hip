@@ -2,6 +2,7 @@
 //   * input layout kernels: (B,3,H,W) fp32 RGB in [0,1]  or  (B,H,W,3) uint8 BGR  ->  NHWC fp16, optionally fused with
 //     ReOrg (space-to-depth; /root/reference/models/common.py:48-53) -- tracker_dataloader.py:83-88 semantics (/255, BGR->RGB)
 //   * nearest x2 upsample (nn.Upsample(None, 2, 'nearest'), cfg/deploy/yolov7-w6.yaml:75,89,103) into a concat slice
+//   * Shortcut: the sum of two channel slices (models/common.py:80-86; yolov7-e6e)
 //   * max-pool k x k (SPPCSPC's 5/9/13 as a 5-cascade, models/common.py:271-278; MP 2x2/s2, SP, common.py:30-45)
 //   * Detect decode (models/yolo.py:39-57) fused with the candidate filter of non_max_suppression
 //     (utils/general.py:607-665), rank sort by confidence, class-offset bitmask NMS with torchvision's greedy
@@ -254,6 +255,42 @@ int y7t_spp3_try(const half_t* in, int ldin, int cin_off, int B, int H, int W, i
     hipLaunchKernelGGL(k_spp3_lds, dim3(B * (C / 16)), dim3(256), (size_t)H * W * 64, s, in, ldin, cin_off, H, W, C, out, ldout, cout_off);
     Y7T_LAUNCH_CHECK();
     y7t_note_kernel("spp3<5,5,5> lds");
+    return 0;
+}
+
+// Shortcut (models/common.py:80-86: x[0] + x[1]) of two NHWC fp16 channel slices into a third: 8 channels (16 B) per lane and access, half(float(a) + float(b)) -- the
+// sum of two fp16 values is exact in fp32, so the result is rounded once.  Memory-bound: at most 2048 workgroups of 256 lanes, grid-striding the rest.
+__global__ void __launch_bounds__(256) k_add(const half_t* __restrict__ a, int lda, int a_off, const half_t* __restrict__ b, int ldb, int b_off, long long npix, int C8,
+                                             half_t* __restrict__ out, int ldout, int cout_off) {
+    const long long tot = npix * C8;
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < tot; t += (long long)gridDim.x * blockDim.x) {
+        const int c8 = (int)(t % C8);
+        const size_t p = (size_t)(t / C8);
+        const half8 va = *(const half8*)(a + p * lda + a_off + c8 * 8);
+        const half8 vb = *(const half8*)(b + p * ldb + b_off + c8 * 8);
+        half8 r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = (half_t)((float)va[e] + (float)vb[e]);
+        *(half8*)(out + p * ldout + cout_off + c8 * 8) = r;
+    }
+}
+
+// `a`, `b`, `out`: the BASES of the three buffers (slices of one buffer share a base: that is how an overlap is recognised)
+int y7t_add_launch(const half_t* a, int lda, int a_off, const half_t* b, int ldb, int b_off, int B, int H, int W, int C, half_t* out, int ldout, int cout_off,
+                   hipStream_t s) {
+    if (C <= 0 || C % 8 || lda % 8 || a_off % 8 || ldb % 8 || b_off % 8 || ldout % 8 || cout_off % 8 || a_off < 0 || b_off < 0 || cout_off < 0) {
+        y7t_set_error("add: channel alignment");
+        return Y7T_E_ARG;
+    }
+    if (a_off + C > lda || b_off + C > ldb || cout_off + C > ldout) { y7t_set_error("add: a slice leaves its buffer's channels"); return Y7T_E_ARG; }
+    const bool hit_a = out == a && (ldout != lda || (cout_off < a_off + C && a_off < cout_off + C));
+    const bool hit_b = out == b && (ldout != ldb || (cout_off < b_off + C && b_off < cout_off + C));
+    if (hit_a || hit_b) { y7t_set_error("add: the output slice overlaps an operand"); return Y7T_E_ARG; }
+    const long long npix = (long long)B * H * W, tot = npix * (C / 8);
+    int blocks = (int)((tot + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_add, dim3(blocks), dim3(256), 0, s, a, lda, a_off, b, ldb, b_off, npix, C / 8, out, ldout, cout_off);
+    Y7T_LAUNCH_CHECK();
+    y7t_note_kernel("add");
     return 0;
 }
 

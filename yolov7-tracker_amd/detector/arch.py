@@ -3,10 +3,12 @@
 
 `yolov7_w6(nc)` / `yolov7_tiny(nc)` generate the lists programmatically (they are checked against the reference's
 cfg/deploy/yolov7-w6.yaml and cfg/deploy/yolov7-tiny.yaml by tests/test_detector_graph.py where the reference is
-present); `load_yaml(path)` reads any cfg file of the same format (the CLI's --model_cfg)."""
+present), and so do `yolov7` / `yolov7x` (P5, three Detect levels) and `yolov7_e6` / `yolov7_d6` / `yolov7_e6e` (P6, four levels;
+tests/test_family_cpu.py); `load_yaml(path)` reads any cfg file of the same format (the CLI's --model_cfg)."""
 import yaml
 
 W6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542], [436, 615, 739, 380, 925, 792]]
+P5_ANCHORS = [[12, 16, 19, 36, 40, 28], [36, 75, 76, 55, 72, 146], [142, 110, 192, 243, 459, 401]]
 TINY_ANCHORS = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
 
 
@@ -65,6 +67,94 @@ def yolov7_tiny(nc=80):
     return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "anchors": TINY_ANCHORS, "layers": L, "n_backbone": 29}
 
 
+def _elan(c, h, out, n, dense, again=False):
+    """ELAN block: two 1x1 convs (c) of one tensor, n chained 3x3 convs (h), a Concat, a 1x1 (out).  dense: the Concat takes every conv of the block (the head blocks of
+    yolov7 / e6 / d6 / e6e), else every second 3x3 and the two 1x1 (backbones; yolov7x throughout).  again: the block reads the tensor the block before it read (the
+    second half of an e6e double block)"""
+    f = -(n + 5) if again else -1
+    cat = list(range(-1, -(n + 3), -1)) if dense else list(range(-1, -(n + 1), -2)) + [-(n + 1), -(n + 2)]
+    return [_conv(f, c), _conv(f - 1, c)] + [_conv(-1, h, 3, 1) for _ in range(n)] + [[cat, 1, "Concat", [1]], _conv(-1, out)]
+
+
+def _block(c, h, out, n, dense, double):
+    """one ELAN block, or e6e's pair of them over the same input joined by a Shortcut (cfg/deploy/yolov7-e6e.yaml:20-40)"""
+    L = _elan(c, h, out, n, dense)
+    if double:
+        L += _elan(c, h, out, n, dense, again=True) + [[[-1, -(n + 5)], 1, "Shortcut", [1]]]
+    return L
+
+
+def _p5(nc, stem, stages, spp, td, bu, head, n, dense_head, rep):
+    """the P5 graphs (yolov7, yolov7x): stem convs, four backbone stages (the last three behind an MP / 3x3-stride-2 down-sampling pair), SPPCSPC, two top-down and two
+    bottom-up head blocks, one 3x3 (yolov7: RepConv) per Detect level"""
+    L = [_conv(-1, stem[0], 3, 1), _conv(-1, stem[1], 3, 2), _conv(-1, stem[1], 3, 1), _conv(-1, stem[2], 3, 2)]
+    routes = []
+    for i, (m, h, out) in enumerate(stages):
+        if i:
+            L += [[-1, 1, "MP", []], _conv(-1, m), _conv(-3, m), _conv(-1, m, 3, 2), [[-1, -3], 1, "Concat", [1]]]
+        L += _elan(h, h, out, n, False)
+        routes.append(len(L) - 1)
+    nb = len(L)
+    L.append([-1, 1, "SPPCSPC", [spp]])
+    lat, outs = [len(L) - 1], []
+    for (c, blk), route in zip(td, (routes[2], routes[1])):      # top-down
+        L += [_conv(-1, c), [-1, 1, "nn.Upsample", [None, 2, "nearest"]], _conv(route, c), [[-1, -2], 1, "Concat", [1]]] + _elan(*blk, n, dense_head)
+        lat.append(len(L) - 1)
+    outs.append(lat.pop())
+    for c, blk in bu:                                             # bottom-up
+        L += [[-1, 1, "MP", []], _conv(-1, c), _conv(-3, c), _conv(-1, c, 3, 2), [[-1, -3, lat.pop()], 1, "Concat", [1]]] + _elan(*blk, n, dense_head)
+        outs.append(len(L) - 1)
+    L += [[o, 1, "RepConv", [c, 3, 1]] if rep else _conv(o, c, 3, 1) for o, c in zip(outs, head)]
+    L.append([list(range(len(L) - 3, len(L))), 1, "Detect", ["nc", "anchors"]])
+    return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "anchors": P5_ANCHORS, "layers": L, "n_backbone": nb}
+
+
+def yolov7(nc=80):
+    return _p5(nc, (32, 64, 128), ((0, 64, 256), (128, 128, 512), (256, 256, 1024), (512, 256, 1024)), 512,
+               ((256, (256, 128, 256)), (128, (128, 64, 128))), ((128, (256, 128, 256)), (256, (512, 256, 512))), (256, 512, 1024), 4, True, True)
+
+
+def yolov7x(nc=80):
+    return _p5(nc, (40, 80, 160), ((0, 64, 320), (160, 128, 640), (320, 256, 1280), (640, 256, 1280)), 640,
+               ((320, (256, 256, 320)), (160, (128, 128, 160))), ((160, (256, 256, 320)), (320, (512, 512, 640))), (320, 640, 1280), 6, False, False)
+
+
+def _p6(nc, stem, widths, n, double):
+    """the P6 graphs behind a DownC down-sampling (yolov7-e6, -d6, -e6e): ReOrg + stem conv, five DownC + ELAN stages, SPPCSPC, three top-down and three bottom-up head
+    blocks of half-width 3x3 convs, one 3x3 per Detect level.  widths: the five stage widths; n: 3x3 convs per ELAN; double: e6e's Shortcut pairs"""
+    L = [[-1, 1, "ReOrg", []], _conv(-1, stem, 3, 1)]
+    routes = []
+    for c, h in zip(widths, (64, 128, 256, 384, 512)):
+        L += [[-1, 1, "DownC", [c]]] + _block(h, h, c, n, False, double)
+        routes.append(len(L) - 1)
+    nb = len(L)
+    L.append([-1, 1, "SPPCSPC", [widths[4] // 2]])
+    hb = lambda c, h: _block(h, h // 2, c, n, True, double)
+    lat, outs = [len(L) - 1], []
+    for c, h, route in ((widths[3] // 2, 384, routes[3]), (widths[2] // 2, 256, routes[2]), (widths[1] // 2, 128, routes[1])):      # top-down
+        L += [_conv(-1, c), [-1, 1, "nn.Upsample", [None, 2, "nearest"]], _conv(route, c), [[-1, -2], 1, "Concat", [1]]] + hb(c, h)
+        lat.append(len(L) - 1)
+    outs.append(lat.pop())
+    for c, h in ((widths[2] // 2, 256), (widths[3] // 2, 384), (widths[4] // 2, 512)):                                            # bottom-up
+        L += [[-1, 1, "DownC", [c]], [[-1, lat.pop()], 1, "Concat", [1]]] + hb(c, h)
+        outs.append(len(L) - 1)
+    L += [_conv(o, c, 3, 1) for o, c in zip(outs, widths[1:])]
+    L.append([list(range(len(L) - 4, len(L))), 1, "Detect", ["nc", "anchors"]])
+    return {"nc": nc, "depth_multiple": 1.0, "width_multiple": 1.0, "anchors": W6_ANCHORS, "layers": L, "n_backbone": nb}
+
+
+def yolov7_e6(nc=80):
+    return _p6(nc, 80, (160, 320, 640, 960, 1280), 6, False)
+
+
+def yolov7_d6(nc=80):
+    return _p6(nc, 96, (192, 384, 768, 1152, 1536), 8, False)
+
+
+def yolov7_e6e(nc=80):
+    return _p6(nc, 80, (160, 320, 640, 960, 1280), 6, True)
+
+
 def load_yaml(path, nc=None):
     with open(path) as f:
         d = yaml.safe_load(f)
@@ -73,4 +163,5 @@ def load_yaml(path, nc=None):
     return spec
 
 
-ARCHS = {"yolov7-w6": yolov7_w6, "yolov7-tiny": yolov7_tiny, "yolov7-w6-training": yolov7_w6_training}
+ARCHS = {"yolov7-w6": yolov7_w6, "yolov7-tiny": yolov7_tiny, "yolov7-w6-training": yolov7_w6_training,
+         "yolov7": yolov7, "yolov7x": yolov7x, "yolov7-e6": yolov7_e6, "yolov7-d6": yolov7_d6, "yolov7-e6e": yolov7_e6e}

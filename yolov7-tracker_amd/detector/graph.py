@@ -1,11 +1,12 @@
 """Graph parse + lowering.
 
 `parse(spec)` restates the subset of /root/reference/models/yolo.py:443-520 (parse_model) that the yolov7-w6 /
-yolov7-tiny graphs use -- Conv, ReOrg, Concat, MP, SP, SPPCSPC, nn.Upsample, Detect / IDetect / IAuxDetect -- and
-expands SPPCSPC (models/common.py:262-280) into its 7 convs + 3 pools.  `lower(nodes, H, W)` turns the node list into
+yolov7-tiny / yolov7 / yolov7x / yolov7-e6 / -d6 / -e6e graphs use -- Conv, RepConv, ReOrg, Concat, Shortcut, MP, SP, SPPCSPC, DownC, nn.Upsample, Detect / IDetect /
+IAuxDetect -- and expands SPPCSPC (models/common.py:262-280) into its 7 convs + 3 pools and DownC (common.py:181-192) into its 3 convs + pool + concat.  `lower(nodes, H, W)` turns the node list into
 the static launch list of include/y7t.h (`y7t_op`) over an NHWC fp16 arena:
   * every tensor lives in exactly one buffer; a tensor consumed by a Concat lives INSIDE the concat's buffer at its
-    channel offset, so Concat (models/common.py:56-62) costs nothing (17 concats in w6);
+    channel offset, so Concat (models/common.py:56-62) costs nothing (17 concats in w6); a Concat that is itself a source of another Concat (DownC's, read by the
+    bottom-up Concats of e6 / d6 / e6e) is a channel range of the outer buffer: its producers write at outer offset + inner offset with the outer buffer's row length;
   * ReOrg is fused into the input layout kernel; branches that do not reach the Detect head (the aux head of
     training checkpoints, models/yolo.py:141-153) are dropped.
 """
@@ -23,7 +24,7 @@ def make_divisible(x, divisor):
 
 
 class Node:
-    """one tensor-producing op after expansion. kind: input|reorg|conv|concat|up|pool|detect"""
+    """one tensor-producing op after expansion. kind: input|reorg|conv|concat|up|pool|add|detect"""
     __slots__ = ("idx", "kind", "src", "c", "k", "s", "p", "act", "wkey", "layer", "extra", "h", "w", "home", "coff", "ld", "virt_up", "virtual")
 
     def __init__(self, kind, src, c, k=1, s=1, p=0, act=0, wkey=None, layer=-1, extra=None):
@@ -78,6 +79,14 @@ def parse(spec, ch=3):
                 raise NotImplementedError("grouped conv")
             act = _act_code(args[5] if len(args) > 5 else True)
             out = add(Node("conv", src, c2, k, s, p, act, "model.%d" % i, i))
+        elif m == "RepConv":      # models/common.py:463-640: 3x3 + 1x1 (+ identity) branches, ONE 3x3 conv after re-parameterisation (weights.folded)
+            c2 = make_divisible(args[0] * gw, 8)
+            k = args[1] if len(args) > 1 else 3
+            s = args[2] if len(args) > 2 else 1
+            if k != 3 or (len(args) > 3 and args[3] not in (None, "None", 1)) or (len(args) > 4 and args[4] not in (1, None)):
+                raise NotImplementedError("RepConv%r" % (args,))
+            act = _act_code(args[5] if len(args) > 5 else True)
+            out = add(Node("conv", src, c2, 3, s, 1, act, "model.%d" % i, i, extra={"rep": True, "identity": c2 == cin[0] and s == 1}))
         elif m == "ReOrg":
             out, c2 = add(Node("reorg", src, cin[0] * 4, layer=i)), cin[0] * 4
         elif m == "Concat":
@@ -93,6 +102,20 @@ def parse(spec, ch=3):
             if args[0] not in (None, "None") or args[1] != 2 or args[2] != "nearest":
                 raise NotImplementedError("Upsample%r" % (args,))
             out, c2 = add(Node("up", src, cin[0], layer=i)), cin[0]
+        elif m == "Shortcut":     # models/common.py:80-86: x[0] + x[1]
+            if len(src) != 2 or cin[0] != cin[1]:
+                raise NotImplementedError("Shortcut of %d tensors with %r channels" % (len(src), cin))
+            out, c2 = add(Node("add", src, cin[0], layer=i)), cin[0]
+        elif m == "DownC":        # models/common.py:181-192: cat(cv2(cv1(x)), cv3(mp(x))); args after parse_model: [c2, n, k]
+            c2 = make_divisible(args[0] * gw, 8)
+            k = args[2] if len(args) > 2 else 2
+            key = "model.%d." % i
+            cv1 = add(Node("conv", src, cin[0], 1, 1, 0, 1, key + "cv1", i))
+            cv2 = add(Node("conv", [cv1], c2 // 2, 3, k, 1, 1, key + "cv2", i))
+            mp = add(Node("pool", src, cin[0], k, k, 0, layer=i))
+            cv3 = add(Node("conv", [mp], c2 // 2, 1, 1, 0, 1, key + "cv3", i))
+            out = add(Node("concat", [cv2, cv3], c2 // 2 * 2, layer=i))
+            c2 = c2 // 2 * 2
         elif m == "SPPCSPC":
             c2 = make_divisible(args[0] * gw, 8)
             c_ = int(2 * c2 * 0.5)
@@ -115,7 +138,7 @@ def parse(spec, ch=3):
             out = add(Node("detect", src[:nl], no, layer=i, extra={"kind": m, "nl": nl, "na": na, "no": nc + 5, "cin": cin[:nl]}))
             c2 = no
         else:
-            raise NotImplementedError("module %s (layer %d) is outside the yolov7-w6 / yolov7-tiny hot path" % (m, i))
+            raise NotImplementedError("module %s (layer %d) is outside the yolov7 family's hot path" % (m, i))
         layer_out.append(out)
         chs.append(c2)
     return nodes, layer_out
@@ -291,23 +314,46 @@ def lower(nodes, H, W, max_batch=1):
             n.h, n.w = s0.h, s0.w
             for j in n.src:
                 assert (nodes[j].h, nodes[j].w) == (n.h, n.w), "concat of mismatched maps"
+        elif n.kind == "add":
+            n.h, n.w = s0.h, s0.w
+            for j in n.src:
+                assert (nodes[j].h, nodes[j].w, nodes[j].c) == (n.h, n.w, n.c), "Shortcut of mismatched maps"
     # ---- homes: a tensor consumed by a concat lives inside that concat's buffer ----
     bufs = []  # (elems_per_image, itemsize)
 
     def new_buf(n, ld, itemsize=2):
         bufs.append((n.h * n.w * ld, itemsize))
         return len(bufs) - 1
-    extra_copies = []  # (src_node, concat_node, coff) for tensors that sit in more than one concat
+    extra_copies = []  # (src_node, concat_node, channel offset in the concat's buffer) for tensors that sit in more than one concat
+    # a concat that is a source of other concats is a channel range of the FIRST of them (its other outer concats get a copy)
+    outer = {}
     for n in nodes:
         if n.idx in live and n.kind == "concat":
-            if any(n.idx in nodes[j].src for j in live if nodes[j].kind == "concat"):
-                raise NotImplementedError("nested Concat")
+            for j in n.src:
+                if nodes[j].kind == "concat":
+                    outer.setdefault(j, n.idx)
+
+    def home_concat(n):
+        if n.home is not None:
+            return
+        if n.idx in outer:
+            o = nodes[outer[n.idx]]
+            if n.idx in o.src[o.src.index(n.idx) + 1:]:
+                raise NotImplementedError("Concat of one Concat twice")
+            home_concat(o)
+            n.home, n.coff, n.ld = o.home, o.coff + sum(nodes[j].c for j in o.src[:o.src.index(n.idx)]), o.ld
+        else:
             n.home, n.coff, n.ld = new_buf(n, n.c), 0, n.c
-            off = 0
+    for n in nodes:
+        if n.idx in live and n.kind == "concat":
+            home_concat(n)
+            off = n.coff
             for j in n.src:
                 t = nodes[j]
-                if t.home is None and t.kind not in ("input", "reorg", "concat"):
-                    t.home, t.coff, t.ld = n.home, off, n.c
+                if t.kind == "concat" and outer.get(j) == n.idx:
+                    assert (t.home, t.coff, t.ld) == (n.home, off, n.ld)
+                elif t.home is None and t.kind not in ("input", "reorg", "concat"):
+                    t.home, t.coff, t.ld = n.home, off, n.ld
                 else:
                     extra_copies.append((j, n.idx, off))
                 off += t.c
@@ -426,6 +472,8 @@ def lower(nodes, H, W, max_batch=1):
         ops.append(op)
         wlayout.append(dict(korder=korder, wkey=wkey, cin=cin_real, cin_pad=cin, cout=cout, cout_pad=cout_pad, k=n.k, K=K, K_pad=K_pad, w_off=w_off,
                             b_off=b_off, kind=kind, act=act, macs=n.h * n.w * cout * n.k * n.k * cin_real))
+        if n.extra and n.extra.get("rep"):      # RepConv: weights.folded re-parameterises its branches into this one 3x3
+            wlayout[-1]["rep"] = True
         w_off += cout_pad * K_pad
         b_off += cout_pad
 
@@ -510,6 +558,10 @@ def lower(nodes, H, W, max_batch=1):
                 emit_simple(1, n, nodes[n.src[0]])
         elif n.kind == "pool":
             emit_simple(2, n, nodes[n.src[0]], n.k, n.s, n.p)
+        elif n.kind == "add":      # Y7T_OP_ADD: the second operand travels in the up_* fields (include/y7t.h)
+            emit_simple(3, n, nodes[n.src[0]])
+            b2 = nodes[n.src[1]]
+            ops[-1]["up_buf"], ops[-1]["up_ld"], ops[-1]["up_coff"] = b2.home, b2.ld, b2.coff
         elif n.kind == "detect":
             ex = n.extra
             for l, j in enumerate(n.src):

@@ -143,14 +143,15 @@ class Detector:
             plan = graph.lower(nodes, hw[0], hw[1], self.max_batch)
             # the kernels address a tensor through 32-bit byte offsets (2 GiB).  A conv whose input or output tensor of `max_batch` frames is larger goes out as
             # several launches over runs of frames (csrc/y7t_detector.hip::forward_impl; w6 @ 1280: the 640^2 / 320^2 layers above 40 frames); the pools, the
-            # materialised upsample and the input layout kernel are single launches
+            # materialised upsample, the adds and the input layout kernel are single launches
             one = max(e * isz for e, isz in plan.buf_elems)
             if one >= 1 << 31:
                 raise ValueError("%dx%d: the largest activation tensor of ONE frame would be %.1f GiB (limit 2 GiB)" % (hw[0], hw[1], one / 2 ** 30))
-            single = [max(int(o["H"]) * int(o["W"]) * int(o["in_ld"]), int(o["Ho"]) * int(o["Wo"]) * int(o["out_ld"])) * 2 for o in plan.ops if int(o["type"]) != 0]
+            single = [max(int(o["H"]) * int(o["W"]) * int(o["in_ld"]), int(o["Ho"]) * int(o["Wo"]) * int(o["out_ld"]),
+                          int(o["H"]) * int(o["W"]) * int(o["up_ld"]) if int(o["type"]) == 3 else 0) * 2 for o in plan.ops if int(o["type"]) != 0]      # (type 3, add: up_* is its second operand)
             single.append(plan.buf_elems[0][0] * plan.buf_elems[0][1])
             if max(single) * self.max_batch >= 1 << 31:
-                raise ValueError("max_batch=%d at %dx%d: a tensor of a single-launch op (pool / upsample / input layout) would be %.1f GiB (limit 2 GiB); "
+                raise ValueError("max_batch=%d at %dx%d: a tensor of a single-launch op (pool / upsample / add / input layout) would be %.1f GiB (limit 2 GiB); "
                                  "split the batch (max_batch <= %d)" % (self.max_batch, hw[0], hw[1], max(single) * self.max_batch / 2 ** 30,
                                                                          ((1 << 31) - 1) // max(single)))
             if self._sd is None:

@@ -1,6 +1,6 @@
 """Weights: deterministic random initialisation (no trained checkpoint ships with the reference), BatchNorm folding
 (restating /root/reference/utils/torch_utils.py:181-201 fuse_conv_and_bn; BN eps = 1e-3 as set by
-utils/torch_utils.py initialize_weights), IDetect implicit-layer folding (what tools/reparameterization.ipynb does:
+utils/torch_utils.py initialize_weights), RepConv re-parameterisation (models/common.py:509-552 get_equivalent_kernel_bias), IDetect implicit-layer folding (what tools/reparameterization.ipynb does:
 m(x + ia) * im), and packing into the [Cout_pad][K_pad] fp16 layout of the implicit-GEMM kernel."""
 import numpy as np
 
@@ -33,6 +33,35 @@ def random_state_dict(wlayout, seed=0, fused=False, bn_bias_mean=0.0):
             sd[w["wkey"] + ".bias"] = torch.from_numpy(rng.normal(0, 0.5, cout).astype(np.float32))
             continue
         gain = {0: 1.0, 1: GAIN_SILU, 2: GAIN_LEAKY}[w.get('act', 1)]
+        if w.get("rep"):          # RepConv, training form (models/common.py:463-506): 3x3 + BN, 1x1 + BN, and a BN of the input itself when cin == cout
+            branches = [("rbr_dense", 3), ("rbr_1x1", 1)] + ([("rbr_identity", 0)] if cin == cout else [])
+            nb = len(branches)    # the branches are summed before the activation: each carries 1 / nb of the shift and 1 / sqrt(nb) of the spread
+            Wsum, bsum = np.zeros((cout, cin, 3, 3)), np.zeros(cout)
+            for name, kk in branches:
+                g = rng.uniform(0.7, 1.3, cout) / np.sqrt(nb)
+                b = (rng.normal(0, 0.1, cout) + bn_bias_mean) / nb
+                mu, var = rng.normal(0, 0.1, cout), rng.uniform(0.8, 1.2, cout)
+                pre = "%s.%s" % (w["wkey"], name)
+                if kk:
+                    Wb = rng.normal(0, gain / np.sqrt(cin * kk * kk), (cout, cin, kk, kk)).astype(np.float32)
+                    sd[pre + ".0.weight"] = torch.from_numpy(Wb)
+                    pre += ".1"
+                    K3 = np.zeros((cout, cin, 3, 3))
+                    K3[:, :, 1 - kk // 2:2 + kk // 2, 1 - kk // 2:2 + kk // 2] = Wb
+                else:
+                    K3 = np.zeros((cout, cin, 3, 3))
+                    K3[np.arange(cout), np.arange(cout), 1, 1] = 1.0
+                for nm, v in (("weight", g), ("bias", b), ("running_mean", mu), ("running_var", var)):
+                    sd["%s.%s" % (pre, nm)] = torch.from_numpy(v.astype(np.float32))
+                scale = g.astype(np.float32).astype(np.float64) / np.sqrt(var.astype(np.float32).astype(np.float64) + BN_EPS)
+                Wsum += K3 * scale[:, None, None, None]
+                bsum += b.astype(np.float32) - mu.astype(np.float32) * scale
+            if fused:             # deploy form: what fuse_repvgg_block leaves (rbr_reparam, a 3x3 conv with bias)
+                for k2 in [k2 for k2 in sd if k2.startswith(w["wkey"] + ".rbr_")]:
+                    del sd[k2]
+                sd[w["wkey"] + ".rbr_reparam.weight"] = torch.from_numpy(Wsum.astype(np.float32))
+                sd[w["wkey"] + ".rbr_reparam.bias"] = torch.from_numpy(bsum.astype(np.float32))
+            continue
         W = rng.normal(0, gain / np.sqrt(fan_in), (cout, cin, k, k)).astype(np.float32)
         g = rng.uniform(0.7, 1.3, cout).astype(np.float32)
         b = (rng.normal(0, 0.1, cout) + bn_bias_mean).astype(np.float32)
@@ -61,11 +90,24 @@ def calibrate_bn(nodes, sd, hw=(640, 640), seed=0, image=None):
     for n in nodes[1:]:
         if n.kind == "detect" or any(j not in vals for j in n.src):
             continue
-        if n.kind == "conv" and n.wkey + ".conv.weight" not in sd:      # a dead branch (the aux head of training graphs): not in the plan, no weights drawn
+        is_rep = n.kind == "conv" and bool(n.extra and n.extra.get("rep"))
+        if n.kind == "conv" and n.wkey + (".rbr_dense.0.weight" if is_rep else ".conv.weight") not in sd:      # a dead branch (the aux head of training graphs): not in the plan, no weights drawn
             continue
         x = vals[n.src[0]]
         if n.kind == "reorg":
             y = torch.cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2]], 1)
+        elif is_rep:              # every branch's BatchNorm learns the statistics of its own branch (models/common.py:507: act(bn(dense(x)) + bn(1x1(x)) + bn(x)))
+            y = 0
+            for pre, z in ((n.wkey + ".rbr_dense.1", F.conv2d(x, sd[n.wkey + ".rbr_dense.0.weight"], None, stride=n.s, padding=1)),
+                           (n.wkey + ".rbr_1x1.1", F.conv2d(x, sd[n.wkey + ".rbr_1x1.0.weight"], None, stride=n.s, padding=0)),
+                           (n.wkey + ".rbr_identity", x)):
+                if pre + ".weight" not in sd:
+                    continue
+                mu, var = z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=False)
+                sd[pre + ".running_mean"], sd[pre + ".running_var"] = mu.clone(), var.clone()
+                y = y + (z - mu[None, :, None, None]) / torch.sqrt(var[None, :, None, None] + BN_EPS) * sd[pre + ".weight"][None, :, None, None] \
+                    + sd[pre + ".bias"][None, :, None, None]
+            y = F.silu(y) if n.act == 1 else (F.leaky_relu(y, 0.1) if n.act == 2 else y)
         elif n.kind == "conv":
             y = F.conv2d(x, sd[n.wkey + ".conv.weight"], None, stride=n.s, padding=n.p)
             mu, var = y.mean((0, 2, 3)), y.var((0, 2, 3), unbiased=False)
@@ -79,10 +121,40 @@ def calibrate_bn(nodes, sd, hw=(640, 640), seed=0, image=None):
             y = F.interpolate(x, scale_factor=2, mode="nearest")
         elif n.kind == "pool":
             y = F.max_pool2d(x, n.k, n.s, n.p)
+        elif n.kind == "add":
+            y = x + vals[n.src[1]]
         else:
             raise NotImplementedError(n.kind)
         vals[n.idx] = y
     return sd
+
+
+def _bn_affine(sd, pre):
+    """BatchNorm `pre` in inference mode as y = x * scale + shift, float64 (eps = BN_EPS, as for Conv)"""
+    g, b = sd[pre + ".weight"].double().cpu().numpy(), sd[pre + ".bias"].double().cpu().numpy()
+    mu, var = sd[pre + ".running_mean"].double().cpu().numpy(), sd[pre + ".running_var"].double().cpu().numpy()
+    scale = g / np.sqrt(var + BN_EPS)
+    return scale, b - mu * scale
+
+
+def folded_repconv(key, sd):
+    """RepConv `key` as ONE 3x3 convolution -> (W' float64 (cout, cin, 3, 3), b' float64): the deploy form's rbr_reparam as it is, or the training form's branches
+    re-parameterised like get_equivalent_kernel_bias (models/common.py:509-552): the BN-folded 3x3, the BN-folded 1x1 zero-padded to the centre tap, and -- when the
+    layer has one -- the identity branch as the BN-scaled unit kernel"""
+    if key + ".rbr_reparam.weight" in sd:
+        return sd[key + ".rbr_reparam.weight"].detach().double().cpu().numpy(), sd[key + ".rbr_reparam.bias"].detach().double().cpu().numpy()
+    W3 = sd[key + ".rbr_dense.0.weight"].detach().double().cpu().numpy()
+    s3, t3 = _bn_affine(sd, key + ".rbr_dense.1")
+    W, b = W3 * s3[:, None, None, None], t3.copy()
+    s1, t1 = _bn_affine(sd, key + ".rbr_1x1.1")
+    W[:, :, 1, 1] += sd[key + ".rbr_1x1.0.weight"].detach().double().cpu().numpy()[:, :, 0, 0] * s1[:, None]
+    b += t1
+    if key + ".rbr_identity.weight" in sd:
+        si, ti = _bn_affine(sd, key + ".rbr_identity")
+        assert W.shape[0] == W.shape[1]
+        W[np.arange(W.shape[0]), np.arange(W.shape[0]), 1, 1] += si
+        b += ti
+    return W, b
 
 
 def folded(w, sd):
@@ -91,6 +163,8 @@ def folded(w, sd):
     if isinstance(key, tuple):   # fused twin 1x1 convs: stack the folded weights in channel order
         parts = [folded(dict(w, wkey=k), sd) for k in key]
         return np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts], 0)
+    if w["kind"] == "conv" and w.get("rep"):
+        return folded_repconv(key, sd)
     if w["kind"] == "conv":
         W = sd[key + ".conv.weight"].detach().double().cpu().numpy()
         if key + ".bn.weight" in sd:
