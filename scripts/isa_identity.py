@@ -60,6 +60,7 @@ def short_names(mangled):
     out = subprocess.run([CXXFILT], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.splitlines()
     res = {}
     for m, d in zip(mangled, out):
+        d = d.replace("(anonymous namespace)::", "")      # (its '(' is not the parameter list's)
         depth, start, end = 0, 0, len(d)
         for i, ch in enumerate(d):      # the name lies between the last blank and the first '(' outside template brackets
             if ch == "<":

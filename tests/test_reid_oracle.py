@@ -213,82 +213,39 @@ def test_preprocess_oracle_shapes():
 
 
 def _interpret_fused_blob(blob, x):
-    """run OSNet x0_25 FROM the parameter blob of the fused kernel (tracker/reid.py::pack_fused), reading it in the kernel's consumption order
-    (csrc/y7t_reid_fused.hip) -- in float32 torch ops, so what is checked is the blob's content and layout, not the kernel's fp16 storage.
-    x: (N, 3, 128, 64) -> (N, 512)"""
+    """run OSNet x0_25 FROM the parameter blob of the fused kernel (tracker/reid.py::pack_fused), read in the kernel's consumption order
+    (csrc/y7t_reid_fused.hip) by tests/reid_fused_ref.py::decode_blob -- the one decoder, shared with the staged references of the kernel's taps -- in float32
+    torch ops, so what is checked is the blob's content and layout, not the kernel's fp16 storage.  x: (N, 3, 128, 64) -> (N, 512)"""
     import torch.nn.functional as F
-    buf = memoryview(blob.tobytes())
-    pos = [0]
+    from tests import reid_fused_ref as FR
+    P = FR.decode_blob(blob)
+    tt = torch.from_numpy
 
-    def take(nbytes, dtype):
-        a = np.frombuffer(buf[pos[0]:pos[0] + nbytes], dtype=dtype)
-        pos[0] += nbytes
-        return a
-
-    def unfrag(ng, nk):
-        fr = take(ng * nk * 512, np.float16).reshape(ng, nk, 64, 4).astype(np.float32)
-        M = np.zeros((ng * 16, nk * 16), np.float32)
-        lane = np.arange(64)
-        for g in range(ng):
-            for k in range(nk):
-                for e in range(4):
-                    M[g * 16 + lane % 16, k * 16 + 4 * (lane // 16) + e] = fr[g, k, :, e]
-        return torch.from_numpy(M)
-
-    def f32(n):
-        return torch.from_numpy(take(4 * n, np.float32).copy())
-
-    def conv1x1(t, cout_p, cin_p, bias=True, relu=False):
-        W = unfrag(cout_p // 16, cin_p // 16)
-        b = f32(cout_p) if bias else None
-        y = F.conv2d(t, W[:, :, None, None], b)
+    def conv1x1(t, wb, relu=False):
+        y = F.conv2d(t, tt(wb[0])[:, :, None, None], tt(wb[1]) if wb[1] is not None else None)
         return F.relu(y) if relu else y
 
-    # conv1 7x7: fragments [kh*2 + half][lane][e]: row lane % 16, input pixel kw = 4 * half + lane // 16, channel e
-    fr = take(14 * 512, np.float16).reshape(14, 64, 4).astype(np.float32)
-    W1 = np.zeros((16, 3, 7, 7), np.float32)
-    lane = np.arange(64)
-    for kh in range(7):
-        for h in range(2):
-            kw = 4 * h + lane // 16
-            for c in range(3):
-                ok = kw < 7
-                W1[(lane % 16)[ok], c, kh, kw[ok]] = fr[kh * 2 + h, ok, c]
-    t = F.relu(F.conv2d(x, torch.from_numpy(W1), f32(16), stride=2, padding=3))
+    t = F.relu(F.conv2d(x, tt(P["stem"][0]), tt(P["stem"][1]), stride=2, padding=3))
     t = F.max_pool2d(t, 3, 2, 1)
-
-    def block(t, cin, cout, midp, R):
-        x1_W = unfrag(midp // 16, cin // 16); x1_b = f32(midp)
-        w1 = f32(R * midp).reshape(R, midp); b1 = f32(4)[:R]; w2 = f32(R * midp).reshape(R, midp); b2 = f32(midp)
-        W3 = unfrag(cout // 16, midp // 16); b3 = f32(cout)
-        Wd = unfrag(cout // 16, cin // 16) if cin != cout else None
-        x1 = F.relu(F.conv2d(t, x1_W[:, :, None, None], x1_b))
-        x2 = 0
+    for blk in P["blocks"]:
+        midp = blk["c1w"].shape[0]
+        w1, b1, w2, b2 = tt(blk["g_w1"]), tt(blk["g_b1"]), tt(blk["g_w2"]), tt(blk["g_b2"])
+        x1 = conv1x1(t, (blk["c1w"], blk["c1b"]), relu=True)
+        x2, lights = 0, iter(blk["lights"])
         for n in (1, 2, 3, 4):
             u = x1
             for _ in range(n):
-                Wl = unfrag(midp // 16, midp // 16)
-                dw = f32(midp * 9).reshape(midp // 8, 9, 8).permute(0, 2, 1).reshape(midp, 1, 3, 3)
-                db = f32(midp)
-                u = F.relu(F.conv2d(F.conv2d(u, Wl[:, :, None, None]), dw, db, padding=1, groups=midp))
+                Wl, dw, db = next(lights)
+                u = F.relu(F.conv2d(conv1x1(u, (Wl, None)), tt(dw).reshape(midp, 1, 3, 3), tt(db), padding=1, groups=midp))
             g = u.mean((2, 3))
             g = torch.sigmoid(F.relu(g @ w1.T + b1) @ w2 + b2)
             x2 = x2 + u * g[:, :, None, None]
-        y = F.conv2d(x2, W3[:, :, None, None], b3)
-        return F.relu(y + (F.conv2d(t, Wd[:, :, None, None]) if Wd is not None else t))
-
-    t = block(t, 16, 64, 16, 1); t = block(t, 64, 64, 16, 1)
-    t = F.avg_pool2d(conv1x1(t, 64, 64, relu=True), 2)
-    t = block(t, 64, 96, 32, 1); t = block(t, 96, 96, 32, 1)
-    t = F.avg_pool2d(conv1x1(t, 96, 96, relu=True), 2)
-    t = block(t, 96, 128, 32, 2); t = block(t, 128, 128, 32, 2)
-    t = conv1x1(t, 128, 128, relu=True)
-    v = t.mean((2, 3))
-    wt = torch.from_numpy(take(64 * 512 * 4, np.float16).reshape(64, 512, 2).astype(np.float32))      # [channel pair][output][2]
-    Wf = wt.permute(1, 0, 2).reshape(512, 128)
-    out = F.relu(v @ Wf.T + f32(512))
-    assert pos[0] == len(buf), "the kernel's walk and the blob's length disagree"
-    return out
+        y = conv1x1(x2, (blk["c3w"], blk["c3b"]))
+        t = F.relu(y + (conv1x1(t, (blk["dnw"], None)) if blk["dnw"] is not None else t))
+        if blk["name"] in FR.TRANS:
+            t = F.avg_pool2d(conv1x1(t, P[FR.TRANS[blk["name"]][0]], relu=True), 2)
+    t = conv1x1(t, P["conv5"], relu=True)
+    return F.relu(t.mean((2, 3)) @ tt(P["fc"][0]).T + tt(P["fc"][1]))
 
 
 def test_fused_blob_encodes_the_network():

@@ -46,6 +46,18 @@ __device__ __forceinline__ half4 to_half4(floatx4 v) {
 }
 __device__ __forceinline__ floatx4 relu4(floatx4 v) { floatx4 r; for (int e = 0; e < 4; ++e) r[e] = fmaxf(v[e], 0.f); return r; }
 
+// The TAP instance (measuring build only; tests/test_reid_fused_taps_gpu.py) copies every tensor a phase has finished -- `bytes` of LDS, pixel pitch and all -- to the
+// crop's tap buffer in global memory and carries on.  Called behind the barrier that completes the tensor; the barrier of its own keeps the next phase from overwriting
+// what is still being read.  The order and sizes of the calls are restated by y7t_reid_fused_tap_layout() below.  TAP == false: nothing.
+template <bool TAP>
+__device__ __forceinline__ void tap(char*& tp, const char* src, int bytes, int tid) {
+    if constexpr (TAP) {
+        for (int i = tid; i < bytes / 16; i += NT) ((floatx4*)tp)[i] = ((const floatx4*)src)[i];
+        tp += bytes;
+        __syncthreads();
+    }
+}
+
 // one MFMA task: D[16 couts][16 pixels of group pg] += sum_nk A[nk] . B(pixels, channels nk*16..)
 template <int NK, int W, int PS>
 __device__ __forceinline__ floatx4 gemm_task(floatx4 acc, const half4 (&a)[NK], const char* src, int pg, int lane) {
@@ -215,8 +227,8 @@ __device__ __forceinline__ void dwconv3(const char* U, char* T, const float* dww
 // O_WH / O_WL: where the block's parameters are staged in LDS (header = conv1, gate, conv3, downsample; lights = the ten LightConv3x3), O_WH < 0: the
 // header is read from global memory.  A phase that fetches its own weights pays an L2 round trip (~1.4 us) before it can start, and a block is ~25 phases
 // of a few hundred cycles of work each; one cooperative copy per block replaces them.
-template <int H, int W, int CIN, int COUT, int MID, int R, int O_XIN, int O_XOUT, int O_X1, int O_T, int O_U, int O_S, int O_WH, int O_WL>
-__device__ __forceinline__ const char* osblock(char* lds, const char* wp, int tid) {
+template <bool TAP, int H, int W, int CIN, int COUT, int MID, int R, int O_XIN, int O_XOUT, int O_X1, int O_T, int O_U, int O_S, int O_WH, int O_WL>
+__device__ __forceinline__ const char* osblock(char* lds, const char* wp, int tid, char*& tp) {
     constexpr int NPX = H * W, PIN = Pitch<CIN>::v, POUT = Pitch<COUT>::v, PM = Pitch<MID>::v;
     constexpr bool DOWN = CIN != COUT;
     constexpr int U_BYTES = (H + 2) * (W + 2) * PM;
@@ -260,6 +272,7 @@ __device__ __forceinline__ const char* osblock(char* lds, const char* wp, int ti
     for (int i = 0; i < AccShape<NPX, COUT>::N; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
     if (DOWN) acc_add<NPX, W, CIN, COUT, PIN, false>(acc, lds + O_XIN, dnf, nullptr, wave, lane);
     __syncthreads();
+    tap<TAP>(tp, lds + O_X1, NPX * PM, tid);
 
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -270,9 +283,11 @@ __device__ __forceinline__ const char* osblock(char* lds, const char* wp, int ti
             const float* dwb = (const float*)lp; lp += MID * 4;
             conv1x1<NPX, W, MID, MID, PM, PM, true, false, false>(lds + (j == 0 ? O_X1 : O_T), lds + O_U, lf, nullptr, wave, lane);
             __syncthreads();
+            tap<TAP>(tp, lds + O_U, U_BYTES, tid);
             if (j == s) dwconv3<H, W, MID, true>(lds + O_U, lds + O_T, dww, dwb, S, tid);
             else dwconv3<H, W, MID, false>(lds + O_U, lds + O_T, dww, dwb, nullptr, tid);
             __syncthreads();
+            tap<TAP>(tp, lds + O_T, NPX * PM, tid);
         }
         // ChannelGate (OSNet.py:162-220): g = sigmoid(fc2(relu(fc1(mean)))); the hidden layer is 1-2 values, every thread computes it
         float* gate = S + NW * MID;
@@ -292,21 +307,24 @@ __device__ __forceinline__ const char* osblock(char* lds, const char* wp, int ti
             gate[tid] = 1.0f / (1.0f + __expf(-a));
         }
         __syncthreads();
+        tap<TAP>(tp, (const char*)S, (NW + 1) * MID * 4, tid);      // S[NW][MID] | gate[MID]
         acc_add<NPX, W, MID, COUT, PM, true>(acc, lds + O_T, c3f, gate, wave, lane);
     }
     acc_store<NPX, W, COUT, POUT, !DOWN>(acc, lds + O_XOUT, c3b, wave, lane);
     __syncthreads();
+    tap<TAP>(tp, lds + O_XOUT, NPX * POUT, tid);
     return wp;
 }
 
 // Conv1x1 + BN + ReLU then AvgPool2d(2)  (OSNet.py:338-350): X -> Y (full resolution) -> OUT (half resolution)
-template <int H, int W, int C, int O_X, int O_Y, int O_OUT>
-__device__ __forceinline__ const char* transition(char* lds, const char* wp, int tid) {
+template <bool TAP, int H, int W, int C, int O_X, int O_Y, int O_OUT>
+__device__ __forceinline__ const char* transition(char* lds, const char* wp, int tid, char*& tp) {
     constexpr int P = Pitch<C>::v, NPX = H * W;
     const char* f = wp; wp += (C / 16) * (C / 16) * 512;
     const float* b = (const float*)wp; wp += C * 4;
     conv1x1<NPX, W, C, C, P, P, false, true, true>(lds + O_X, lds + O_Y, f, b, tid >> 6, tid & 63);
     __syncthreads();
+    tap<TAP>(tp, lds + O_Y, NPX * P, tid);
     constexpr int CG = C / 8, TASKS = (NPX / 4) * CG;
     for (int task = tid; task < TASKS; task += NT) {
         const int cg = task % CG, px = task / CG, y = px / (W / 2), x = px % (W / 2);
@@ -318,6 +336,7 @@ __device__ __forceinline__ const char* transition(char* lds, const char* wp, int
         *(half8*)(lds + O_OUT + px * P + cg * 16) = o;
     }
     __syncthreads();
+    tap<TAP>(tp, lds + O_OUT, NPX / 4 * P, tid);
     return wp;
 }
 
@@ -331,10 +350,21 @@ constexpr int S3_XIN = 77824, S3_X = 96256, S3_X1 = 0, S3_T = 10240, S3_U = 2048
 constexpr int S4_XIN = 40960, S4_X = 49152, S4_X1 = 0, S4_T = 2560, S4_U = 5120, S4_S = 9984, S4_Y5 = 61440, S4_V = 71680, S4_WL = 73728, S4_WH = 108544;
 constexpr int LDS_BYTES = 163840;
 
-__global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
+// the TAP instance's arguments: the product's and where the taps go
+struct Y7TReidTapArgs : Y7TReidFusedArgs {
+    char* taps;                 // (N, tap_stride) bytes
+    long long tap_stride;
+};
+template <bool TAP> struct KArgs { using type = Y7TReidFusedArgs; };
+template <> struct KArgs<true> { using type = Y7TReidTapArgs; };
+
+template <bool TAP>
+__global__ void __launch_bounds__(NT) k_osnet_x025(const typename KArgs<TAP>::type p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = blockIdx.x;
     const char* wp = p.blob;
+    char* tp = nullptr;
+    if constexpr (TAP) tp = p.taps + (size_t)n * p.tap_stride;
     int stamp = 0;
 #define REID_PROF() do { if (p.prof && n == 0 && tid == 0) p.prof[stamp] = clock64(); ++stamp; } while (0)
     REID_PROF();
@@ -373,6 +403,7 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
         }
     }
     __syncthreads();
+    tap<TAP>(tp, lds + O_CR, CR_H * CR_W * 8, tid);
 
     REID_PROF();
     // ---- conv1: 7x7 / stride 2 / pad 3, 3 -> 16, BN, ReLU as an implicit GEMM: K-step (kh, half) = 4 pixels x 4 channels of input row 2*yo - 3 + kh ----
@@ -396,6 +427,7 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
         }
     }
     __syncthreads();
+    tap<TAP>(tp, lds + O_C1, 64 * 32 * 32, tid);
     REID_PROF();
     // ---- maxpool 3x3 / stride 2 / pad 1 -> X0 (32 x 16 x 16ch); inputs are >= 0, so skipping the padding == -inf padding ----
     for (int task = tid; task < 32 * 16 * 2; task += NT) {
@@ -417,23 +449,24 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
         *(half8*)(lds + S2_X0 + px * 32 + cg * 16) = m;
     }
     __syncthreads();
+    tap<TAP>(tp, lds + S2_X0, 32 * 16 * 32, tid);
 
     REID_PROF();
-    wp = osblock<32, 16, 16, 64, 16, 1, S2_X0, S2_X, S2_X1, S2_T, S2_U, S2_S, -1, S2_WL>(lds, wp, tid);
+    wp = osblock<TAP, 32, 16, 16, 64, 16, 1, S2_X0, S2_X, S2_X1, S2_T, S2_U, S2_S, -1, S2_WL>(lds, wp, tid, tp);
     REID_PROF();
-    wp = osblock<32, 16, 64, 64, 16, 1, S2_X, S2_X, S2_X1, S2_T, S2_U, S2_S, -1, S2_WL>(lds, wp, tid);
+    wp = osblock<TAP, 32, 16, 64, 64, 16, 1, S2_X, S2_X, S2_X1, S2_T, S2_U, S2_S, -1, S2_WL>(lds, wp, tid, tp);
     REID_PROF();
-    wp = transition<32, 16, 64, S2_X, S2_Y, S3_XIN>(lds, wp, tid);
+    wp = transition<TAP, 32, 16, 64, S2_X, S2_Y, S3_XIN>(lds, wp, tid, tp);
     REID_PROF();
-    wp = osblock<16, 8, 64, 96, 32, 1, S3_XIN, S3_X, S3_X1, S3_T, S3_U, S3_S, S3_WH, S3_WL>(lds, wp, tid);
+    wp = osblock<TAP, 16, 8, 64, 96, 32, 1, S3_XIN, S3_X, S3_X1, S3_T, S3_U, S3_S, S3_WH, S3_WL>(lds, wp, tid, tp);
     REID_PROF();
-    wp = osblock<16, 8, 96, 96, 32, 1, S3_X, S3_X, S3_X1, S3_T, S3_U, S3_S, S3_WH, S3_WL>(lds, wp, tid);
+    wp = osblock<TAP, 16, 8, 96, 96, 32, 1, S3_X, S3_X, S3_X1, S3_T, S3_U, S3_S, S3_WH, S3_WL>(lds, wp, tid, tp);
     REID_PROF();
-    wp = transition<16, 8, 96, S3_X, S3_Y, S4_XIN>(lds, wp, tid);
+    wp = transition<TAP, 16, 8, 96, S3_X, S3_Y, S4_XIN>(lds, wp, tid, tp);
     REID_PROF();
-    wp = osblock<8, 4, 96, 128, 32, 2, S4_XIN, S4_X, S4_X1, S4_T, S4_U, S4_S, S4_WH, S4_WL>(lds, wp, tid);
+    wp = osblock<TAP, 8, 4, 96, 128, 32, 2, S4_XIN, S4_X, S4_X1, S4_T, S4_U, S4_S, S4_WH, S4_WL>(lds, wp, tid, tp);
     REID_PROF();
-    wp = osblock<8, 4, 128, 128, 32, 2, S4_X, S4_X, S4_X1, S4_T, S4_U, S4_S, S4_WH, S4_WL>(lds, wp, tid);
+    wp = osblock<TAP, 8, 4, 128, 128, 32, 2, S4_X, S4_X, S4_X1, S4_T, S4_U, S4_S, S4_WH, S4_WL>(lds, wp, tid, tp);
     REID_PROF();
 
     // ---- conv5 (1x1 + BN + ReLU), global average pool, fc + BatchNorm1d + ReLU ----
@@ -443,6 +476,7 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
         const float* b = (const float*)wp; wp += 128 * 4;
         conv1x1<32, 4, 128, 128, P, P, false, true, true>(lds + S4_X, lds + S4_Y5, f, b, wave, lane);
         __syncthreads();
+        tap<TAP>(tp, lds + S4_Y5, 32 * P, tid);
         float* v = (float*)(lds + S4_V);
         if (tid < 128) {
             float s = 0.f;
@@ -450,6 +484,7 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
             v[tid] = s * (1.0f / 32.0f);
         }
         __syncthreads();
+        tap<TAP>(tp, lds + S4_V, 128 * 4, tid);
         const half2v* wt = (const half2v*)wp;                 // [64 channel pairs][512 outputs][2]
         const float* fb = (const float*)(wp + 64 * 512 * 4);
         float a = fb[tid];
@@ -460,6 +495,11 @@ __global__ void __launch_bounds__(NT) k_osnet_x025(const Y7TReidFusedArgs p) {
             a = __builtin_fmaf((float)w2[1], v[2 * c2 + 1], a);
         }
         p.feats[(size_t)n * 512 + tid] = fmaxf(a, 0.f);
+        if constexpr (TAP) {      // the feature itself (registers, not LDS), then the bytes walked: the test holds them against the layout table
+            ((float*)tp)[tid] = fmaxf(a, 0.f);
+            tp += 512 * 4;
+            if (tid == 0) *(long long*)tp = (long long)(tp - (p.taps + (size_t)n * p.tap_stride));
+        }
     }
     REID_PROF();
 }
@@ -483,7 +523,7 @@ size_t y7t_reid_fused_blob_bytes() {
 int y7t_reid_fused_launch(const Y7TReidFusedArgs& a, hipStream_t s) {
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
     if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_osnet_x025, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_osnet_x025<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         return 0;
     })) return e_;
     if (a.N <= 0) return 0;
@@ -492,7 +532,7 @@ int y7t_reid_fused_launch(const Y7TReidFusedArgs& a, hipStream_t s) {
     if (prof < 0) { prof = y7t_exp_switch("Y7T_REID_PROF", 0); if (prof) Y7T_HIP_CHECK(hipMalloc((void**)&prof_dev, 32 * sizeof(long long))); }
     Y7TReidFusedArgs b = a;
     b.prof = prof ? prof_dev : nullptr;
-    hipLaunchKernelGGL(k_osnet_x025, dim3(a.N), dim3(NT), LDS_BYTES, s, b);
+    hipLaunchKernelGGL(k_osnet_x025<false>, dim3(a.N), dim3(NT), LDS_BYTES, s, b);
     Y7T_LAUNCH_CHECK();
     if (prof) {      // diagnostics only: synchronous
         long long h[32];
@@ -507,3 +547,75 @@ int y7t_reid_fused_launch(const Y7TReidFusedArgs& a, hipStream_t s) {
     y7t_note_kernel("osnet_x025_fused");
     return 0;
 }
+
+#ifdef Y7T_ABLATE_BUILD
+// ---- the TAP instance's entry points: the measuring build only, bound by tests/test_reid_fused_taps_gpu.py itself (not part of include/y7t.h) ----
+// One tapped tensor: `offset` bytes into the crop's tap buffer, h x w pixels of `pitch` elements each, the first c of them channels (the rest is the LDS pitch's padding)
+struct Y7TReidTap { char name[40]; long long offset; int dtype /* 0 fp16, 1 fp32, 2 int64 */, h, w, c, pitch; };
+
+// the tap buffer's layout in the order k_osnet_x025<true> walks it -> entries (written up to `cap`); *stride: bytes per crop
+extern "C" int y7t_reid_fused_tap_layout(Y7TReidTap* out, int cap, long long* stride) {
+    int n = 0;
+    long long off = 0;
+    auto put = [&](const char* name, int dtype, int h, int w, int c, int pitch) {
+        if (out && n < cap) {
+            Y7TReidTap& t = out[n];
+            snprintf(t.name, sizeof(t.name), "%s", name);
+            t.offset = off; t.dtype = dtype; t.h = h; t.w = w; t.c = c; t.pitch = pitch;
+        }
+        ++n;
+        off += (long long)h * w * pitch * (dtype == 0 ? 2 : dtype == 1 ? 4 : 8);
+    };
+    auto pitch = [](int c) { return (c == 16 ? 32 : c * 2 + 16) / 2; };      // Pitch<C> in elements
+    char nm[64];
+    auto block = [&](const char* name, int H, int W, int cout, int mid) {
+        snprintf(nm, sizeof(nm), "%s.x1", name); put(nm, 0, H, W, mid, pitch(mid));
+        for (int s = 0, l = 0; s < 4; ++s) {
+            for (int j = 0; j <= s; ++j, ++l) {
+                snprintf(nm, sizeof(nm), "%s.light%d.U", name, l); put(nm, 0, H + 2, W + 2, mid, pitch(mid));
+                snprintf(nm, sizeof(nm), "%s.light%d.T", name, l); put(nm, 0, H, W, mid, pitch(mid));
+            }
+            snprintf(nm, sizeof(nm), "%s.stream%d.S", name, s); put(nm, 1, NW, 1, mid, mid);
+            snprintf(nm, sizeof(nm), "%s.stream%d.gate", name, s); put(nm, 1, 1, 1, mid, mid);
+        }
+        snprintf(nm, sizeof(nm), "%s.X", name); put(nm, 0, H, W, cout, pitch(cout));
+    };
+    auto trans = [&](const char* name, int H, int W, int c) {
+        snprintf(nm, sizeof(nm), "%s.Y", name); put(nm, 0, H, W, c, pitch(c));
+        snprintf(nm, sizeof(nm), "%s.pool", name); put(nm, 0, H / 2, W / 2, c, pitch(c));
+    };
+    put("CR", 0, CR_H, CR_W, 4, 4);
+    put("C1", 0, 64, 32, 16, 16);
+    put("X0", 0, 32, 16, 16, 16);
+    block("conv2.0", 32, 16, 64, 16); block("conv2.1", 32, 16, 64, 16); trans("conv2.2", 32, 16, 64);
+    block("conv3.0", 16, 8, 96, 32); block("conv3.1", 16, 8, 96, 32); trans("conv3.2", 16, 8, 96);
+    block("conv4.0", 8, 4, 128, 32); block("conv4.1", 8, 4, 128, 32);
+    put("Y5", 0, 8, 4, 128, pitch(128));
+    put("v", 1, 1, 1, 128, 128);
+    put("feats", 1, 1, 1, 512, 512);
+    put("walked", 2, 1, 1, 1, 2);       // the bytes the kernel walked up to here == this entry's offset (16 bytes keep the stride a multiple of 16)
+    if (stride) *stride = off;
+    return n;
+}
+
+extern "C" int y7t_reid_fused_taps(const void* frames, int n_frames, int H, int W, const float* boxes, const int* frame_idx, int N, const void* blob, long long blob_bytes,
+                                   float* feats, void* taps, long long tap_bytes, void* stream) {
+    long long stride = 0;
+    y7t_reid_fused_tap_layout(nullptr, 0, &stride);
+    Y7T_ARG_CHECK(frames && boxes && blob && feats && taps && n_frames >= 1 && H > 0 && W > 0 && N >= 0);
+    Y7T_ARG_CHECK(blob_bytes == (long long)y7t_reid_fused_blob_bytes() && tap_bytes >= (long long)N * stride && ((size_t)taps & 15) == 0);
+    static Y7TOncePerDevice attr;
+    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
+        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_osnet_x025<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+        return 0;
+    })) return e_;
+    if (N == 0) return 0;
+    Y7TReidTapArgs a;
+    a.frames = (const uint8_t*)frames; a.frame_stride = (long long)H * W * 3; a.H = H; a.W = W; a.boxes = boxes; a.frame_idx = frame_idx; a.n_frames = n_frames; a.N = N;
+    a.blob = (const char*)blob; a.feats = feats; a.prof = nullptr; a.taps = (char*)taps; a.tap_stride = stride;
+    hipLaunchKernelGGL(k_osnet_x025<true>, dim3(N), dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
+    Y7T_LAUNCH_CHECK();
+    y7t_note_kernel("osnet_x025_fused taps");
+    return 0;
+}
+#endif
