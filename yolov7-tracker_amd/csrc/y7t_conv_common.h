@@ -11,6 +11,14 @@ typedef __attribute__((ext_vector_type(16))) float floatx16;
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 
+// Lane predicates of the dense strips (y7t_conv_patch.hip).  A per-lane bool that lives across a loop is kept by the compiler as a wave-wide lane mask in an
+// SGPR pair, and y7t_lds_select(a, z, m) -- the LDS address `z` where m holds, `a` elsewhere -- is ONE v_cndmask on that pair: a selection (never a
+// multiplication: what lies at `a` may be Inf or NaN).
+typedef bool y7t_mask_t;
+__device__ __forceinline__ y7t_mask_t y7t_lane_mask(bool c) { return c; }
+__device__ __forceinline__ const half8* y7t_lds_select(const char* a, const char* z, y7t_mask_t m) { return (const half8*)(m ? z : a); }
+__device__ __forceinline__ const half8* y7t_lds_select2(const char* a, const char* z, y7t_mask_t m0, y7t_mask_t m1) { return (const half8*)((m0 | m1) ? z : a); }
+
 // compile-time activation: the epilogues branch ONCE on p.act and run a specialised body (a per-element run-time switch cost ~3
 // scalar branches + hazard nops per value: 40 % of the epilogue's instructions)
 template <int ACT>

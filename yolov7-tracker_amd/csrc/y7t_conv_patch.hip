@@ -27,10 +27,13 @@ constexpr unsigned kOOB = 0xFF000000u;   // voffset of a zero-filled lane: out o
 template <int TW, int TH, int BN>
 struct PatchCfg {
     static constexpr int PIXB = 80;                                       // bytes per patch pixel in LDS (64 data + 16 pad)
-    // TW == 0: FLAT tiling for narrow maps (W = 20, 40).  The batch is one long strip of zero-padded images, (H+2) rows of
-    // PW = W+2 positions each; a workgroup owns 256 CONSECUTIVE positions of the strip (padding positions are computed and dropped:
-    // W*H / ((W+2)*(H+2)) useful, 91 % at 40x40, where 16x16 tiles would be 69 %), its patch is the same strip PW+1 positions
-    // longer at both ends, and tap (kh, kw) is the shift kh*PW + kw.  TH carries PW.
+    // TW == 0: FLAT tiling for narrow maps (W = 20, 40).  The batch is one DENSE strip: its B*H*W pixels in NHWC order, no padding
+    // position anywhere; a workgroup owns 256 CONSECUTIVE pixels of the strip (every position is a real pixel, where 16x16 tiles
+    // would be 69 % useful at 40x40), its patch is the same strip PW+1 pixels longer at both ends, and tap (kh, kw) is the shift
+    // kh*PW + kw.  TH carries PW = W.  A tap that leaves the image would read the wrapped neighbour (the end of the previous row,
+    // the last row of the previous image): the lanes whose pixel lies on the image's border read a ZEROED LDS region instead,
+    // selected by wave-wide lane masks (x == 0, x == W-1, y == 0, y == H-1 per MFMA tile, built once per workgroup) -- the same
+    // zero the padded strip of earlier rounds (PW = W+2, 83 % / 91 % useful positions) multiplied there.
     static constexpr bool FLAT = (TW == 0);
     static constexpr int PW = TH;
     static constexpr int NPOS = 256 + 2 * PW + 2;                         // FLAT: patch positions
@@ -48,8 +51,13 @@ struct PatchCfg {
     static constexpr int LDS_LOOP = P_OFF + 2 * PATCH_BYTES;
     static constexpr int OROW = BN * 2 + 16;
     static constexpr int LDS_EPI = 256 * OROW;
-    static constexpr int BIAS_OFF = LDS_LOOP > LDS_EPI + 1024 ? LDS_LOOP : LDS_EPI + 1024;   // (+ the FLAT epilogue's 256-entry pixel table)
-    static constexpr int LDS = BIAS_OFF + BN * 4;                         // this workgroup's BN biases, fetched in the prologue
+    static constexpr int BIAS_OFF = LDS_LOOP > LDS_EPI + 1024 ? LDS_LOOP : LDS_EPI + 1024;   // (+ 1 KiB nobody uses since the strips are dense)
+    static constexpr int ZERO_OFF = BIAS_OFF + BN * 4;                    // this workgroup's BN biases, fetched in the prologue
+    // FLAT: the zeros a border lane reads.  Its address keeps the 16-byte slot (mod 16) of the patch address it replaces -- lane part
+    // (5 * l31 + hi32) & 15, tap part (5 * shift) & 15, k-substep 0 / 2 -- so a service group still touches 16 different slots
+    static constexpr int ZERO_BYTES = FLAT ? 240 + 240 + 32 + 16 + 48 : 0;
+    static constexpr int LDS = ZERO_OFF + ZERO_BYTES;
+    static_assert(ZERO_OFF % 256 == 0 && P_OFF % 256 == 0 && PATCH_BYTES % 256 == 0, "slot arithmetic of the zero region");
     static constexpr int WN = BN / 64, WM = 4 / WN;                       // waves along channels / pixels
     static constexpr int TM = 8 / WM;                                     // 32-pixel MFMA tiles per wave (4 or 2)
     static constexpr int RPT = (TW == 16) ? 2 : 1;                        // image rows per MFMA tile
@@ -99,8 +107,8 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
     const int tile_n = bid % n_tiles_n;
     int pt = bid / n_tiles_n;
     int b = 0, h0 = 0, w0 = 0;
-    const int g0 = pt * 256;                                   // FLAT: first strip position of this workgroup
-    const int img_pos = (p.H + 2) * C::PW, strip = p.B * img_pos;
+    const int g0 = pt * 256;                                   // FLAT: first strip pixel of this workgroup
+    const int npix = p.B * p.H * p.W;                          // FLAT: pixels of the strip
     if (!FLAT) {
         constexpr int TWd = FLAT ? 1 : TW;
         const int tiles_x = (p.W + TWd - 1) / TWd, tiles_y = (p.H + TH - 1) / TH;
@@ -135,13 +143,8 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
             const int byte = I * 1024 + lane * 16;
             if (FLAT) {
                 const int q = byte / PIXB, cs = (byte - q * PIXB) >> 4;
-                const int g = g0 - C::PW - 1 + q;                   // strip position of patch slot q
-                if (cs < 4 && q < C::NPOS && g >= 0 && g < strip) {
-                    const int bb = g / img_pos, rem = g - bb * img_pos;
-                    const int yy = rem / C::PW, xx = rem - yy * C::PW;
-                    if (yy >= 1 && yy <= p.H && xx >= 1 && xx <= p.W)
-                        v = (unsigned)(((((bb * p.H + yy - 1) * p.W + xx - 1) * p.ldin + p.cin_off) + cs * 8) * 2);
-                }
+                const int g = g0 - C::PW - 1 + q;                   // strip pixel of patch slot q
+                if (cs < 4 && q < C::NPOS && g >= 0 && g < npix) v = ((unsigned)g * (unsigned)p.ldin + (unsigned)(p.cin_off + cs * 8)) * 2u;
             } else {
             const int r = byte / RP, rb = byte - r * RP;
             const int x = rb / PIXB, cs = (rb - x * PIXB) >> 4;
@@ -172,15 +175,24 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
     const int s_odd = p.korder == 2 ? 9 * C::W_BYTES : 64;                  // odd chunk of a pair relative to the even one
     const int s_pair = p.korder == 2 ? 18 * C::W_BYTES : p.korder ? 3 * 128 : 128;
     int cbase = 0;
+    // FLAT: the DMA destinations are formed where they are used (wave part + constant, one s_add into M0).  Left alone the compiler keeps every
+    // one of them -- ~45 values -- in an SGPR of its own across the K loop, and those SGPRs are needed for the border masks.
     auto issue_w = [&](int slot, int coff, int kh, int kw, bool real) {
         const int so = kh * s_kh + kw * s_kw + coff;
+        int wv = wave;
+        if (FLAT) asm volatile("" : "+s"(wv));
 #pragma unroll
         for (int i = 0; i < C::NWX; ++i)   // weight waves only
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (LDS_AS void*)(smem + C::W_OFF + slot * C::W_BYTES + (wave * C::NWX + i) * 1024), 16,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (LDS_AS void*)(smem + C::W_OFF + slot * C::W_BYTES + (wv * C::NWX + i) * 1024), 16,
                                                      real ? off[i] : kOOB, real ? so : 0, 0, 0);
     };
     auto issue_patch_piece = [&](int pb, int c, int i, bool real) {   // patch waves only
-        const int I = ((wave - 2) + 2 * i < C::PATCH_DMA) ? (wave - 2) + 2 * i : C::PATCH_DMA - 1;
+        int wv = wave - 2;
+        if (FLAT) {
+            asm volatile("" : "+s"(wv));
+            wv &= 1;      // (waves 2, 3: says so to the compiler, which then clamps only the last piece)
+        }
+        const int I = (wv + 2 * i < C::PATCH_DMA) ? wv + 2 * i : C::PATCH_DMA - 1;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (LDS_AS void*)(smem + C::P_OFF + pb * C::PATCH_BYTES + I * 1024), 16,
                                                  real ? off[i] : kOOB, c << 6, 0, 0);
     };
@@ -206,13 +218,61 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
         for (int i = 0; i < C::NPX; ++i) issue_patch_piece(0, 0, i, true);
     }
 
+    // FLAT: the four border facts of every lane's pixel (lane predicates: the compiler keeps them as wave-wide masks, 4 SGPR pairs per MFMA tile), the lane's address in the
+    // zero region, and the region's zeros -- all behind the first DMAs, under their latency
+    typedef __attribute__((ext_vector_type(4))) unsigned zero4v;
+    y7t_mask_t mx0[TM] = {}, mxw[TM] = {}, my0[TM] = {}, myh[TM] = {};
+    const int zlane = C::ZERO_OFF + (((5 * l31 + hi32) & 15) << 4);
+    if (FLAT) {
+        if (tid * 16 < C::ZERO_BYTES) *(zero4v*)(smem + C::ZERO_OFF + tid * 16) = zero4v{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+            const int g = g0 + (wm * TM + j) * 32 + l31;
+            const int r = g / C::PW, x = g - r * C::PW, y = r % p.H;
+            mx0[j] = y7t_lane_mask(x == 0);
+            mxw[j] = y7t_lane_mask(x == C::PW - 1);
+            my0[j] = y7t_lane_mask(y == 0);
+            myh[j] = y7t_lane_mask(y == p.H - 1);
+        }
+    }
+    // fragment (tile j, k-substep ks) of tap (kh, kw); ps = the lane's patch address shifted by the tap, zs = its zero address (FLAT).  FLAT: the
+    // lanes for which the tap leaves the image read zeros (one v_add + one v_cndmask per tap and tile, nothing that waits for returned data)
+    auto patch_frag = [&](const char* ps, const char* zs, int kh, int kw, int j, int ks) -> half8 {
+        if (FLAT && (kh != 1 || kw != 1)) {
+            const char* a = ps + j * C::JOFF;
+            y7t_mask_t my = 0, mx = 0;
+            if (kh == 0) my = my0[j];
+            if (kh == 2) my = myh[j];
+            if (kw == 0) mx = mx0[j];
+            if (kw == 2) mx = mxw[j];
+            if (kh != 1 && kw != 1) return y7t_lds_select2(a, zs, my, mx)[ks * 2];      // a corner tap: two facts
+            return y7t_lds_select(a, zs, kh != 1 ? my : mx)[ks * 2];
+        }
+        return *(const half8*)(ps + j * C::JOFF + ks * 32);
+    };
+    // FLAT: the lane's patch and zero addresses go through an empty statement of the step they are used in.  Formed there (v_add of a constant), they
+    // are not ~80 values of which the compiler tries to keep as many as it can in VGPRs across the K loop.
+    auto step_plane = [&]() -> const char* {
+        if (!FLAT) return plane;
+        int pl = C::P_OFF + (wm * TM * 32 + l31) * PIXB + hi32 * 16;
+        asm volatile("" : "+v"(pl));
+        return smem + pl;
+    };
+    auto step_zero = [&](int kh, int kw) -> const char* {
+        if (!FLAT) return smem;
+        int zl = zlane;
+        asm volatile("" : "+v"(zl));
+        return smem + zl + (((5 * (kh * C::PW + kw)) & 15) << 4);
+    };
+
     static_assert(C::PPT * 7 >= C::NPX, "patch pieces fit into taps 0..6");
     static_assert(C::LDS <= 81920, "two workgroups per CU");
     half8 wf[2][2][2], xf[2][2][TM];   // [register buffer][k-substep][tile]
     auto read_frags = [&](int buf, int slot, int pb, int kh, int kw) {
         const char* ws0 = wlane0 + slot * C::W_BYTES;
         const char* ws1 = wlane1 + slot * C::W_BYTES;
-        const char* ps = plane + pb * C::PATCH_BYTES + kh * RP + kw * PIXB;
+        const char* ps = step_plane() + pb * C::PATCH_BYTES + kh * RP + kw * PIXB;
+        const char* zs = step_zero(kh, kw);
         if (ABL & 4) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -228,7 +288,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) wf[buf][ks][i] = *(const half8*)((ks ? ws1 : ws0) + i * 32 * C::WROWB);
 #pragma unroll
-            for (int j = 0; j < TM; ++j) xf[buf][ks][j] = *(const half8*)(ps + j * C::JOFF + ks * 32);
+            for (int j = 0; j < TM; ++j) xf[buf][ks][j] = patch_frag(ps, zs, kh, kw, j, ks);
         }
     };
     auto mfma_half = [&](int buf, int ks) {
@@ -248,6 +308,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
     };
     if (wrole) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * C::NWX) : "memory");   // W(0) landed (W(1), W(2) may be in flight)
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             // patch(0) landed
+    if (FLAT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                      // ... and the zero region written
     __builtin_amdgcn_s_barrier();
     read_frags(0, 0, 0, 0, 0);
 
@@ -274,7 +335,8 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
             const int c = c0 + cc, cur = u & 1;
             if (ABL == 0) {
                 const int un = u + 1, tn = un % 9, kh = tn / 3, kw = tn % 3;
-                const char* ps = plane + ((un / 9) & 1) * C::PATCH_BYTES + kh * RP + kw * PIXB;
+                const char* ps = step_plane() + ((un / 9) & 1) * C::PATCH_BYTES + kh * RP + kw * PIXB;
+                const char* zs = step_zero(kh, kw);
                 const char* ws0 = wlane0 + (un % 3) * C::W_BYTES;
                 const char* ws1 = wlane1 + (un % 3) * C::W_BYTES;
                 __builtin_amdgcn_s_setprio(1);
@@ -282,7 +344,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
                 for (int q = 0; q < 2 * TM; ++q) {           // first half: MFMA q, then patch fragment q of the next step
                     const int i = q / TM, j = q % TM;
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[cur][0][i], xf[cur][0][j], acc[i][j], 0, 0, 0);
-                    if (t < 8) xf[cur ^ 1][q / TM][q % TM] = *(const half8*)(ps + (q % TM) * C::JOFF + (q / TM) * 32);
+                    if (t < 8) xf[cur ^ 1][q / TM][q % TM] = patch_frag(ps, zs, kh, kw, q % TM, q / TM);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -299,7 +361,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
                     const int i = q / TM, j = q % TM;
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[cur][1][i], xf[cur][1][j], acc[i][j], 0, 0, 0);
                     if (q < 4) wf[cur ^ 1][q >> 1][q & 1] = *(const half8*)(((q >> 1) ? ws1 : ws0) + (q & 1) * 32 * C::WROWB);
-                    if (t == 8) xf[cur ^ 1][q / TM][q % TM] = *(const half8*)(ps + (q % TM) * C::JOFF + (q / TM) * 32);
+                    if (t == 8) xf[cur ^ 1][q / TM][q % TM] = patch_frag(ps, zs, kh, kw, q % TM, q / TM);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -367,17 +429,6 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
         }
     }
     });
-    int* otab = (int*)(smem + C::LDS_EPI);   // FLAT: output pixel index of each of the 256 positions (-1: padding / past the strip)
-    if (FLAT) {
-        const int g = g0 + tid;
-        int o = -1;
-        if (g < strip) {
-            const int bb = g / img_pos, rem = g - bb * img_pos;
-            const int yy = rem / C::PW, xx = rem - yy * C::PW;
-            if (yy >= 1 && yy <= p.H && xx >= 1 && xx <= p.W) o = (bb * p.H + yy - 1) * p.W + xx - 1;
-        }
-        otab[tid] = o;
-    }
     __syncthreads();
     {
         typedef __attribute__((ext_vector_type(4))) unsigned uint4v;
@@ -401,7 +452,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
                 const int cidx = tid + (c0 + k) * 256, pix = cidx / CPP, ch = cidx - pix * CPP;
                 const int n = n0 + ch * 8;
                 long long opix;
-                if (FLAT) opix = otab[pix];
+                if (FLAT) opix = g0 + pix < npix ? g0 + pix : -1;      // the tile's output rows are contiguous
                 else {
                     constexpr int TWd = FLAT ? 1 : TW;
                     const int r = pix / TWd, x = pix - r * TWd;
@@ -669,7 +720,7 @@ int launch_patch(const Y7TConvArgs& a, hipStream_t s) {
         Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_patch<TW, TH, BN, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
         return 0;
     })) return e_;
-    const int ptiles = C::FLAT ? (a.B * (a.H + 2) * C::PW + 255) / 256 : a.B * ((a.H + TH - 1) / TH) * ((a.W + (C::FLAT ? 1 : TW) - 1) / (C::FLAT ? 1 : TW));
+    const int ptiles = C::FLAT ? (a.B * a.H * a.W + 255) / 256 : a.B * ((a.H + TH - 1) / TH) * ((a.W + (C::FLAT ? 1 : TW) - 1) / (C::FLAT ? 1 : TW));
     const int tiles = ptiles * (a.Cout_pad / BN);
     hipLaunchKernelGGL((k_conv3x3_patch<TW, TH, BN, ABL>), dim3(tiles), dim3(256), C::LDS, s, a);
     Y7T_LAUNCH_CHECK();
@@ -699,7 +750,7 @@ int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s) {
     const double e16 = eff(16, 16), e32 = eff(32, 8);
     const bool use16 = e16 >= e32;
     const bool wide = a.Cout_pad % 128 == 0 && !a.panel64;
-    const double eflat = (a.W == 40 || a.W == 20) ? (double)(a.W * a.H) / ((a.W + 2) * (a.H + 2)) : 0.0;   // strip tiling (instantiated for W = 20, 40)
+    const double eflat = (a.W == 40 || a.W == 20) ? 1.0 : 0.0;   // dense strip (instantiated for W = 20, 40): every position is a real pixel
     // too few workgroups for 256 CUs (batch-1 latency mode): the generic kernel with split-K fills the chip better
     if (!a.force_patch && a.korder != 2 && (long long)a.B * a.H * a.W * (a.Cout_pad / (wide ? 128 : 64)) < 256ll * 256) return 0;
     const int abl = Y7T_ABLATE ? a.ablate : 0;      // (ABL = 512, the step's DMAs behind its MFMAs, was measured in round 3: 15.98 vs 16.02 ms for the list -- not instantiated any more)
@@ -707,12 +758,12 @@ int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s) {
         int rcf;
 #if Y7T_ABLATE
         if (abl == 2048) {
-            if (a.W == 40) rcf = wide ? launch_patch<0, 42, 128, 2048>(a, s) : launch_patch<0, 42, 64, 2048>(a, s);
-            else rcf = wide ? launch_patch<0, 22, 128, 2048>(a, s) : launch_patch<0, 22, 64, 2048>(a, s);
+            if (a.W == 40) rcf = wide ? launch_patch<0, 40, 128, 2048>(a, s) : launch_patch<0, 40, 64, 2048>(a, s);
+            else rcf = wide ? launch_patch<0, 20, 128, 2048>(a, s) : launch_patch<0, 20, 64, 2048>(a, s);
         } else
 #endif
-        if (a.W == 40) rcf = wide ? launch_patch<0, 42, 128>(a, s) : launch_patch<0, 42, 64>(a, s);
-        else rcf = wide ? launch_patch<0, 22, 128>(a, s) : launch_patch<0, 22, 64>(a, s);
+        if (a.W == 40) rcf = wide ? launch_patch<0, 40, 128>(a, s) : launch_patch<0, 40, 64>(a, s);
+        else rcf = wide ? launch_patch<0, 20, 128>(a, s) : launch_patch<0, 20, 64>(a, s);
         return rcf ? rcf : 1;
     }
     if (!a.force_patch && a.korder != 2 && (use16 ? e16 : e32) < 0.8) return 0;

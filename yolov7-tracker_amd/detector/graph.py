@@ -192,7 +192,7 @@ def patch_eligible(H, W, cin, cout, k, s, p, out_ld, out_coff, out_f32, B=1 << 2
     if not (k == 3 and s == 1 and p == 1 and cin % 64 == 0 and not out_f32 and cout % 8 == 0 and out_ld % 8 == 0 and out_coff % 8 == 0):
         return False
     eff = lambda tw, th: (W * H) / float(-(-W // tw) * tw * -(-H // th) * th)
-    eflat = (W * H) / float((W + 2) * (H + 2)) if W in (20, 40) else 0.0      # strip tiling of narrow maps
+    eflat = 1.0 if W in (20, 40) else 0.0      # dense strip tiling of narrow maps: every position is a real pixel
     return max(eff(16, 16), eff(32, 8), eflat) >= 0.8
 
 
