@@ -288,6 +288,35 @@ const char* y7t_tracker_field_name(int i);
 
 
 /* ---------------------------------------------------------------- detector (YOLOv7 forward) ---- */
+/* How a conv op's weights are packed -- and therefore which kernel reads them.  The values are ABI: y7t_op::korder carries them, and so do recorded plans.
+ * Python mirror: detector/layout.py::WeightLayout (with the packer of each); packers in detector/weights.py, kernels in csrc/. */
+typedef enum y7t_weight_layout {
+    Y7T_WL_TAP_MAJOR = 0,         /* rows [Cout_pad][K_pad], k = (kh*KW + kw)*Cin + ci; weights.pack itself; the generic kernel (y7t_conv.hip), the patch kernel on large maps */
+    Y7T_WL_LINE_MAJOR = 1,        /* the same rows with k in (kh, 64-channel chunk, kw) order (3x3, Cin % 64 == 0); weights.pack itself; y7t_conv.hip, y7t_conv_patch.hip */
+    Y7T_WL_PATCH = 2,             /* per K-step the swizzled LDS image of a 128-row (Cout_pad % 128) or 64-row panel; panel_pack; y7t_conv_patch.hip */
+    Y7T_WL_PANEL_1X1 = 3,         /* 1x1: per 32-deep K-step one contiguous 128- or 64-row panel; panel_pack_linear; the 32-deep kernel of y7t_conv.hip */
+    Y7T_WL_PATCH_S2 = 4,          /* stride-2 3x3: per (16-channel chunk, tap) a 256- or 128-row panel; panel_pack_s2; y7t_conv_patch_s2.hip */
+    Y7T_WL_WS64 = 5,              /* the 64 -> 64 3x3 filter bank as MFMA A-fragments; pack_ws; y7t_conv_ws.hip */
+    Y7T_WL_WS128 = 6,             /* the 128 -> 128 k 3x3 bank as A-fragments per 128-channel tile, stride 1 and 2; pack_ws128; y7t_conv_ws128.hip */
+    Y7T_WL_P8 = 7,                /* 1x1, Cout_pad % 256 == 0: per (channel tile, 64-deep K-tile) the swizzled LDS image of a 256 x 64 panel; panel_pack_p8; y7t_conv_p8.hip */
+    Y7T_WL_WS_S2 = 8,             /* the 64 -> 128 3x3 / stride 2 bank as A-fragments; pack_ws_s2; y7t_conv_ws_s2.hip */
+    Y7T_WL_PATCH_N64 = 9,         /* Y7T_WL_PATCH with 64-row panels although Cout_pad % 128 == 0 (small maps); panel_pack(narrow); y7t_conv_patch.hip */
+    Y7T_WL_PANEL_1X1_N64 = 10,    /* Y7T_WL_PANEL_1X1 with 64-row panels although Cout_pad % 128 == 0; panel_pack_linear(narrow); y7t_conv.hip */
+    Y7T_WL_WS_S2_TWIN = 11,       /* Y7T_WL_WS_S2 FOLLOWED by the 128 -> 128 bank of the twin 1x1 convolution that consumes the layer and its 128 biases behind the layer's own:
+                                     one launch computes both, Cout / out_* describe the 1x1 layer's output, the tensor between them is never written; pack_ws_s2 then
+                                     pack_ws_s2_tail (blob-only layout 12, TWIN_TAIL in detector/layout.py: it never appears in an op); y7t_conv_ws_s2.hip */
+    Y7T_WL_COUNT = 12
+} y7t_weight_layout;
+/* The same choice in the `act` argument of y7t_conv2d_nhwc_f16: bits 0-7 the activation, bit 8 layout 1, bit 9 forces the patch kernel on an eligible 3x3 / stride 1
+ * layer whatever its size (tests), bit 8 + L layout L for L = 2 .. 11.  Of several layout bits the highest layout wins. */
+#define Y7T_ACT_FORCE_PATCH 512
+#define Y7T_ACT_LAYOUT_BITS(layout) ((layout) <= 0 ? 0 : (layout) == 1 ? 256 : 256 << (layout))
+static inline int Y7T_ACT_LAYOUT(int act) {      /* the inverse (a function: it loops) */
+    for (int l = Y7T_WL_COUNT - 1; l >= 2; --l)
+        if (act & Y7T_ACT_LAYOUT_BITS(l)) return l;
+    return (act >> 8) & 1;
+}
+
 /* One op of a lowered detector graph.  The host (Python) lowers the reference's model graph
  * (models/yolo.py:321-351 forward_once over the yaml layer list, models/yolo.py:443-520 parse_model) into a
  * static launch list over a pre-planned NHWC fp16 activation arena: concat is eliminated (producers write
@@ -302,13 +331,7 @@ typedef struct y7t_op {
     int32_t KH, KW, stride, pad;        /* conv / pool window */
     int32_t K, K_pad;
     int32_t act;                        /* 0 none, 1 SiLU, 2 LeakyReLU(0.1) */
-    int32_t korder;                     /* weight packing: 0 k = (kh*KW+kw)*Cin + ci; 1 (kh, 64-ch chunk, kw); 2 LDS-patch panels; 3 1x1 panels;
-                                           4 stride-2 LDS-patch panels (detector/weights.py::panel_pack_s2); 5 the 64 -> 64 filter bank as MFMA A-fragments
-                                           (weights-stationary kernel, pack_ws); 7 1x1 layers with Cout % 256 == 0: per (channel tile, 64-deep K-tile) the swizzled LDS image of the 256 x 64 panel
-                                           (csrc/y7t_conv_p8.hip, weights.py::panel_pack_p8); 8 the 64 -> 128 3x3 / stride 2 filter bank as MFMA A-fragments
-                                           (csrc/y7t_conv_ws_s2.hip, pack_ws_s2); 9 / 10 as 2 / 3 with 64-row panels although Cout_pad % 128 == 0 (small maps);
-                                           11 as 8 FOLLOWED by the 128 -> 128 bank of the twin 1x1 convolution that consumes the layer (pack_ws_s2_tail) and its 128 biases
-                                           behind the layer's own: one launch computes both, Cout / out_* describe the 1x1 layer's output, the tensor between them is never written */
+    int32_t korder;                     /* a y7t_weight_layout: how this op's weights are packed, and therefore which kernel runs it */
     int32_t detect_level;               /* -1: ordinary layer.  l >= 0: the 1x1 conv of Detect level l (models/yolo.py:46); in a fused forward
                                            (y7t_det_forward_fused) its epilogue decodes + filters instead of writing the head tensor */
     int64_t w_off;                      /* element offset into the fp16 weight blob */

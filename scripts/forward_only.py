@@ -36,7 +36,7 @@ for oi, op in enumerate(p.ops):
     if int(op["type"]) == 0:
         wl = p.wlayout[ci]; ci += 1
         macs = wl["macs"]
-        if wl.get("fused_next"):      # korder 11: the stride-2 layer + the twin 1x1 behind it are ONE launch (two weight banks)
+        if wl.get("fused_next"):      # WeightLayout.WS_S2_TWIN: the stride-2 layer + the twin 1x1 behind it are ONE launch (two weight banks)
             macs += p.wlayout[ci]["macs"]; ci += 1
         d["gflop"] = 2 * macs * B / 1e9
         cin_bytes = (int(op["Cin"]) - int(op["up_C"])) * int(op["H"]) * int(op["W"]) + int(op["up_C"]) * int(op["H"]) * int(op["W"]) // 4

@@ -10,6 +10,8 @@ import collections
 import torch
 import torch.nn.functional as F
 
+from yolov7_tracker_amd.detector.layout import WeightLayout
+
 
 def conv_tolerance(ref, absum, K, extra_tol=0.0):
     """the convolution bar of the module docstring for a result `ref` of K-term sums with sum_k |w_k x_k| = absum (|act'| <= 1.1 (SiLU; LeakyReLU 1): the pre-activation
@@ -49,10 +51,10 @@ def check_every_op(det, B, frames, x0, names):
             x = x[:, :wl["cin"]]                                   # the real channels of a padded layout (the stem's 12 of 16, tiny's 3 of 8)
             k, s_, pd = int(op["KH"]), int(op["stride"]), int(op["pad"])
             extra_tol = 0.0
-            if wl["kind"] == "conv" and wl.get("fused_next"):      # korder 11: the stride-2 layer + the twin 1x1 behind it in one launch; the tensor between them is never written
+            if wl["kind"] == "conv" and wl.get("fused_next"):      # WeightLayout.WS_S2_TWIN: the stride-2 layer + the twin 1x1 behind it in one launch; the tensor between them is never written
                 w2 = p.wlayout[ci]
                 ci += 1
-                assert int(op["korder"]) == 11 and w2.get("fused_prev") and isinstance(w2["wkey"], tuple)
+                assert op["korder"] == WeightLayout.WS_S2_TWIN and w2.get("fused_prev") and isinstance(w2["wkey"], tuple)
                 mid = dt._conv_bn_act(x, sd, wl["wkey"], k, s_, pd, wl["act"], fp16=True, round_out=True)        # (fp16 in LDS, as it would be in memory)
                 ref = torch.cat([dt._conv_bn_act(mid, sd, key, 1, 1, 0, w2["act"], fp16=True, round_out=False) for key in w2["wkey"]], 1)
                 absum = torch.cat([dt.conv_abs_sum(mid, sd, key, 1, 0) for key in w2["wkey"]], 1)

@@ -40,6 +40,47 @@ def test_hostsim_tracker_kinds_are_the_header_enumerators():
     assert len(enum) == 8 and HostSimTracker.TRACKERS == enum
 
 
+def test_weight_layouts_are_the_header_enumerators_and_each_has_one_packer():
+    """detector/layout.py::WeightLayout is y7t_weight_layout of include/y7t.h by name and value (TWIN_TAIL aside: blob-only, no op carries it), Y7T_WL_COUNT counts the
+    layouts an op may carry, and weights.PACKERS has one packer for every layout -- the blob-only one included"""
+    from yolov7_tracker_amd.detector import weights
+    from yolov7_tracker_amd.detector.layout import OP_LAYOUTS, WeightLayout
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "y7t.h")).read(), flags=re.S)
+    enum = {name: int(v) for name, v in re.findall(r"\bY7T_WL_([A-Z0-9_]+)\s*=\s*(\d+)", txt)}
+    count = enum.pop("COUNT")
+    assert enum == {l.name: int(l) for l in OP_LAYOUTS} and count == len(OP_LAYOUTS) == 12
+    assert [int(l) for l in OP_LAYOUTS] == list(range(count)) and WeightLayout.TWIN_TAIL == count
+    assert sorted(weights.PACKERS) == sorted(WeightLayout) and all(callable(f) for f in weights.PACKERS.values())
+
+
+def test_act_bits_of_the_single_layer_entry_point_are_pinned():
+    """the second encoding of a layout, in y7t_conv2d_nhwc_f16's `act` argument: the table below is the ABI (bit 8 layout 1, bit 9 forces the patch kernel, bit 8 + L
+    layout L); act_bits / layout_of are inverses on it, and of two layout bits the higher layout wins, as in the library's decoder"""
+    from yolov7_tracker_amd.detector.layout import FORCE_PATCH, OP_LAYOUTS, WeightLayout, act_bits, layout_of
+    pinned = {0: 0, 1: 256, 2: 1024, 3: 2048, 4: 4096, 5: 8192, 6: 16384, 7: 32768, 8: 65536, 9: 131072, 10: 262144, 11: 524288}
+    assert {int(l): act_bits(l) for l in OP_LAYOUTS} == pinned and FORCE_PATCH == 512
+    for l in OP_LAYOUTS:
+        for force in (False, True):
+            for act in (0, 1, 2):
+                bits = act | act_bits(l, force)
+                assert bits == act | pinned[l] | (512 if force else 0) and layout_of(bits) == (l, force) and isinstance(layout_of(bits)[0], WeightLayout)
+    for lo in OP_LAYOUTS[1:]:
+        for hi in OP_LAYOUTS[lo + 1:]:
+            assert layout_of(1 | pinned[lo] | pinned[hi]) == (hi, False)
+    with pytest.raises((AssertionError, ValueError)):
+        act_bits(WeightLayout.TWIN_TAIL)
+    # the C side of the same rule (the header's macro and decoder, nothing else checks Y7T_ACT_LAYOUT), compiled for the host: needs `cc` on PATH, like build()'s oracle
+    import subprocess
+    import tempfile
+    src = ('#include <stdio.h>\n#include "y7t.h"\nint main(void) { for (int l = 0; l < Y7T_WL_COUNT; ++l) for (int h = l; h < Y7T_WL_COUNT; ++h) '
+           'printf("%d %d %d %d\\n", l, h, Y7T_ACT_LAYOUT_BITS(l), Y7T_ACT_LAYOUT(2 | Y7T_ACT_FORCE_PATCH | Y7T_ACT_LAYOUT_BITS(l) | Y7T_ACT_LAYOUT_BITS(h))); return 0; }\n')
+    with tempfile.TemporaryDirectory() as tmp:
+        open(os.path.join(tmp, "t.c"), "w").write(src)
+        subprocess.run(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "t.c"), "-o", os.path.join(tmp, "t")], check=True)
+        rows = [[int(v) for v in r.split()] for r in subprocess.run([os.path.join(tmp, "t")], capture_output=True, text=True, check=True).stdout.splitlines()]
+    assert len(rows) == 78 and all(bits == pinned[l] and got == h for l, h, bits, got in rows)
+
+
 def test_version_and_error_string(lib):
     assert lib.y7t_version() >= 100
     assert isinstance(lib.y7t_last_error(), bytes)

@@ -8,51 +8,19 @@ import pytest
 import torch
 
 from tests import _convsim as cs
+from tests.util import layer_cout_pad, pack_w
+from yolov7_tracker_amd.detector.layout import WeightLayout as WL
 
 pytestmark = pytest.mark.skipif(not __import__("os").path.exists(cs._CLANG), reason="needs the ROCm clang++ (host compile of the kernel source)")
 
 
-def pack_w(W, cin_pad, cout_pad, korder=0):
-    cout, cin, k, _ = W.shape
-    K = k * k * cin_pad
-    Kp = (K + 63) // 64 * 64
-    Wt = np.zeros((cout, k, k, cin_pad), np.float32)
-    Wt[..., :cin] = W.transpose(0, 2, 3, 1)
-    if korder == 1:      # (kh, 64-channel chunk, kw) K order
-        Wt = Wt.reshape(cout, k, k, cin_pad // 64, 64).transpose(0, 1, 3, 2, 4)
-    blk = np.zeros((cout_pad, Kp), np.float16)
-    blk[:cout, :K] = Wt.reshape(cout, -1).astype(np.float16)
-    if korder in (2, 9):      # the patch kernel's panel order (9: 64-row panels although Cout_pad % 128 == 0)
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack(blk, cin_pad, narrow=korder == 9)
-    if korder in (3, 10):      # the 1x1 panel order (10: 64-row panels although Cout_pad % 128 == 0)
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_linear(blk, narrow=korder == 10)
-    if korder == 5:      # the weights-stationary kernel's register-fragment order
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws(blk)
-    if korder == 4:      # the stride-2 patch kernel's panel order
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_s2(blk, cin_pad)
-    if korder == 6:      # the 128-channel weights-stationary kernel's register-fragment order
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws128(blk)
-    if korder == 7:      # the 256 x 64 panels of the ping-pong 1x1 kernel
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_p8(blk)
-    if korder == 8:      # register-fragment order of the stride-2 weights-stationary kernel
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws_s2(blk)
-    return blk
-
-
-def run_case(L, B, H, W, Cin, Cout, k, s, act, tile, in_ld=None, in_coff=0, out_ld=None, out_coff=0, out_f32=0, korder=0, splitk=0, seed=0, force_patch=0):
+def run_case(L, B, H, W, Cin, Cout, k, s, act, tile, in_ld=None, in_coff=0, out_ld=None, out_coff=0, out_f32=0, korder=WL.TAP_MAJOR, splitk=0, seed=0, force_patch=0):
     in_ld, out_ld = in_ld or Cin, out_ld or Cout
     rng = np.random.default_rng(seed)
     x = rng.normal(0, 1, (B, H, W, in_ld)).astype(np.float16)
     Wt = (rng.normal(0, 1, (Cout, Cin, k, k)) / np.sqrt(Cin * k * k)).astype(np.float32)
     bias = rng.normal(0, 0.5, Cout).astype(np.float32)
-    cp = (Cout + 255) // 256 * 256 if korder == 7 else (Cout + 63) // 64 * 64 if korder not in (4, 6, 8) else (Cout + 127) // 128 * 128
+    cp = layer_cout_pad(Cout, korder)
     wp = pack_w(Wt, Cin, cp, korder)
     bp = np.zeros(cp, np.float32)
     bp[:Cout] = bias
@@ -82,13 +50,13 @@ CASES = [
     (1, 16, 16, 16, 64, 3, 1, 1, 256064032, {}),                                       # stem-like: Cin = 16, K = 144 (ragged K)
     (1, 8, 8, 96, 192, 1, 1, 2, 0, {"in_ld": 256, "in_coff": 64, "out_ld": 384, "out_coff": 192}),      # slices of wider buffers, LeakyReLU, dispatch rules
     (1, 8, 8, 256, 45, 1, 1, 0, 0, {"out_ld": 45, "out_f32": 1}),                      # Detect head (plain): fp32 out, Cout not a multiple of 4
-    (1, 11, 9, 128, 128, 3, 1, 1, 128128064, {"korder": 1}),                          # (kh, chunk, kw) K order
-    (1, 13, 11, 192, 64, 3, 2, 1, 128064064, {"korder": 1, "in_ld": 256, "in_coff": 64}),
+    (1, 11, 9, 128, 128, 3, 1, 1, 128128064, {"korder": WL.LINE_MAJOR}),              # (kh, chunk, kw) K order
+    (1, 13, 11, 192, 64, 3, 2, 1, 128064064, {"korder": WL.LINE_MAJOR, "in_ld": 256, "in_coff": 64}),
     (1, 17, 17, 64, 256, 3, 1, 1, 256256064, {}),                                      # the 256 x 256 tile
     (1, 10, 10, 128, 128, 3, 1, 1, 128128064, {"splitk": 1}),                          # split-K + k_splitk_reduce
     (1, 12, 12, 64, 128, 3, 1, 1, 128128364, {}),                                      # three-stage ring
-    (2, 9, 9, 128, 128, 1, 1, 1, 0, {"korder": 3}),                                   # 1x1 panels through the dispatch rules: 128-row panels
-    (2, 9, 9, 128, 256, 1, 1, 2, 0, {"korder": 10, "out_ld": 320, "out_coff": 64}),      # ... 64-row panels on a 256-channel layer (korder 10)
+    (2, 9, 9, 128, 128, 1, 1, 1, 0, {"korder": WL.PANEL_1X1}),                        # 1x1 panels through the dispatch rules: 128-row panels
+    (2, 9, 9, 128, 256, 1, 1, 2, 0, {"korder": WL.PANEL_1X1_N64, "out_ld": 320, "out_coff": 64}),  # ... 64-row panels on a 256-channel layer
 ]
 
 
@@ -99,7 +67,7 @@ def test_shipped_kernel_source_on_the_host(case):
     assert name.startswith("igemm<") and (tile == 0 or ("splitK" in name) == bool(kw.get("splitk")))      # (the dispatch rules split K of small problems themselves)
 
 
-@pytest.mark.parametrize("korder,Cout,lat_first,force", [(0, 128, True, 0), (3, 192, False, 0), (3, 256, True, 0)], ids=["rows-128", "panels-64", "panels-128"])
+@pytest.mark.parametrize("korder,Cout,lat_first,force", [(WL.TAP_MAJOR, 128, True, 0), (WL.PANEL_1X1, 192, False, 0), (WL.PANEL_1X1, 256, True, 0)], ids=["rows-128", "panels-64", "panels-128"])
 def test_upsample_on_read_loader_on_the_host(korder, Cout, lat_first, force):
     """the DUAL instance of the 1x1 fast path (default launch list: the three convs behind Concat[lateral, Upsample(x)], /root/reference/cfg/deploy/yolov7-w6.yaml:75,89,103):
     K-steps whose channels lie in the upsampled range DMA pixel (y >> 1, x >> 1) of the half-resolution tensor -- against a conv over the materialised concat"""
@@ -114,8 +82,8 @@ def test_upsample_on_read_loader_on_the_host(korder, Cout, lat_first, force):
     Wt = (rng.normal(0, 1, (Cout, Cin, 1, 1)) / np.sqrt(Cin)).astype(np.float32)
     bias = rng.normal(0, 0.5, Cout).astype(np.float32)
     cp = (Cout + 63) // 64 * 64
-    wp = pack_w(Wt, Cin, cp, 0)
-    if korder == 3:
+    wp = pack_w(Wt, Cin, cp)
+    if korder == WL.PANEL_1X1:
         from yolov7_tracker_amd.detector import weights
         wp = weights.panel_pack_linear(wp)
     bp = np.zeros(cp, np.float32)
@@ -133,7 +101,7 @@ def test_upsample_on_read_loader_on_the_host(korder, Cout, lat_first, force):
     np.testing.assert_allclose(out.astype(np.float32), ref, rtol=2e-3, atol=2e-3)
 
 
-# the 256 x 256 x 64 ping-pong 1x1 kernel (csrc/y7t_conv_p8.hip, korder 7): B, H, W, Cin, Cout, act, extras.  Every case runs twice: with the buffer->LDS DMAs landing at
+# the 256 x 256 x 64 ping-pong 1x1 kernel (csrc/y7t_conv_p8.hip, P8): B, H, W, Cin, Cout, act, extras.  Every case runs twice: with the buffer->LDS DMAs landing at
 # issue (the earliest they can: a half-tile re-staged while somebody still reads it gives wrong results) and landing only when the issuing lane's own `vmcnt` wait forces
 # them (the latest: a fragment read that no wait + barrier covers sees the 0xAB fill) -- the two ends of what the hardware can do with the kernel's schedule.
 P8_CASES = [
@@ -155,7 +123,7 @@ def test_pingpong_1x1_kernel_source_on_the_host(case, deferred):
     L = cs.lib()
     L.cs_set_dma_deferred(deferred)
     try:
-        name = run_case(L, B, H, W, Cin, Cout, 1, 1, act, 0, korder=7, seed=B * 1000 + H + W + Cin, **kw)
+        name = run_case(L, B, H, W, Cin, Cout, 1, 1, act, 0, korder=WL.P8, seed=B * 1000 + H + W + Cin, **kw)
     finally:
         L.cs_set_dma_deferred(0)
     assert name == "p8<256,256,64> 1x1", name
@@ -175,7 +143,7 @@ def test_pingpong_1x1_upsample_on_read_on_the_host(lat_first, deferred):
     half = rng.normal(0, 1, (B, H // 2, W // 2, 192)).astype(np.float16)  # ... it lives at half resolution, as channels [32, 32 + C_up) of a wider buffer
     Wt = (rng.normal(0, 1, (Cout, Cin, 1, 1)) / np.sqrt(Cin)).astype(np.float32)
     bias = rng.normal(0, 0.5, Cout).astype(np.float32)
-    wp = pack_w(Wt, Cin, Cout, 7)
+    wp = pack_w(Wt, Cin, Cout, WL.P8)
     out = np.full((B, H, W, Cout), 7.0, np.float16)
     L.cs_set_dma_deferred(deferred)
     try:
@@ -191,7 +159,7 @@ def test_pingpong_1x1_upsample_on_read_on_the_host(lat_first, deferred):
     np.testing.assert_allclose(out.astype(np.float32), ref, rtol=2e-3, atol=2e-3)
 
 
-# the stride-2 weights-stationary kernel for the 64 -> 128 down-sampling layer (csrc/y7t_conv_ws_s2.hip, korder 8): B, H, W, act, extras.  2 x 32 output tiles; the host
+# the stride-2 weights-stationary kernel for the 64 -> 128 down-sampling layer (csrc/y7t_conv_ws_s2.hip, WS_S2): B, H, W, act, extras.  2 x 32 output tiles; the host
 # model's three workgroups walk ranges of them through the three-buffer patch ring; both DMA landing times, as for the ping-pong kernel
 WS_S2_CASES = [
     (1, 4, 64, 1, {}),                                                                  # one tile
@@ -208,7 +176,7 @@ def test_stride2_weights_stationary_kernel_source_on_the_host(case, deferred):
     L = cs.lib()
     L.cs_set_dma_deferred(deferred)
     try:
-        name = run_case(L, B, H, W, 64, 128, 3, 2, act, 0, korder=8, seed=B * 1000 + H + W, **kw)
+        name = run_case(L, B, H, W, 64, 128, 3, 2, act, 0, korder=WL.WS_S2, seed=B * 1000 + H + W, **kw)
     finally:
         L.cs_set_dma_deferred(0)
     assert name == "ws_s2<2,32>", name
@@ -217,7 +185,7 @@ def test_stride2_weights_stationary_kernel_source_on_the_host(case, deferred):
 @pytest.mark.parametrize("deferred", [0, 1], ids=["dma-at-issue", "dma-at-wait"])
 @pytest.mark.parametrize("case", WS_S2_CASES, ids=lambda c: "%dx%dx%d_act%d" % c[:4])
 def test_stride2_weights_stationary_kernel_with_the_twin_1x1_behind_it_on_the_host(case, deferred):
-    """korder 11 (csrc/y7t_conv_ws_s2.hip, FUSE): 3x3 / stride 2 64 -> 128, activation, fp16 -- in the LDS gather, never in memory -- then the 128 -> 128 1x1 convolution
+    """WS_S2_TWIN (csrc/y7t_conv_ws_s2.hip, FUSE): 3x3 / stride 2 64 -> 128, activation, fp16 -- in the LDS gather, never in memory -- then the 128 -> 128 1x1 convolution
     (the two 1x1 layers that open the next ELAN block as one) + activation.  Reference: the two layers one after the other with the tensor between them rounded to fp16."""
     from yolov7_tracker_amd.detector import weights
     B, H, W, act, kw = case
@@ -237,7 +205,7 @@ def test_stride2_weights_stationary_kernel_with_the_twin_1x1_behind_it_on_the_ho
     L = cs.lib()
     L.cs_set_dma_deferred(deferred)
     try:
-        rc = L.cs_conv(x.ctypes.data, in_ld, in_coff, B, H, W, 64, wp.ctypes.data, bp.ctypes.data, out.ctypes.data, out_ld, out_coff, 0, 128, 128, 3, 3, 2, 1, act, 11, 0, 0, 0)
+        rc = L.cs_conv(x.ctypes.data, in_ld, in_coff, B, H, W, 64, wp.ctypes.data, bp.ctypes.data, out.ctypes.data, out_ld, out_coff, 0, 128, 128, 3, 3, 2, 1, act, WL.WS_S2_TWIN, 0, 0, 0)
     finally:
         L.cs_set_dma_deferred(0)
     assert rc == 0, L.cs_last_error().decode()
@@ -255,7 +223,7 @@ def test_stride2_weights_stationary_kernel_with_the_twin_1x1_behind_it_on_the_ho
 
 def test_stride2_weights_stationary_fragment_reads_are_bank_conflict_free_and_packing():
     """144-byte pixels: the 16 lanes of a ds_read_b128 service group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, + 32) are 16 columns of ONE patch row -> 16 different
-    16-byte bank quads for every tap plane and k-substep; and korder 8 is the documented permutation"""
+    16-byte bank quads for every tap plane and k-substep; and WS_S2 is the documented permutation"""
     from yolov7_tracker_amd.detector import weights
     groups = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
     for hi in (0, 1):
@@ -288,13 +256,13 @@ def test_pingpong_panel_packing_is_the_documented_lds_image():
 
 # the LDS-patch kernels (csrc/y7t_conv_patch.hip; 3x3 / stride 1): B, H, W, Cin, Cout, act, korder, extras -- forced onto the patch kernel like the GPU layer tests
 PATCH_CASES = [
-    (1, 24, 32, 64, 128, 1, 0, {}),                                                   # 16x16 tiles, 128-channel panels
-    (1, 16, 40, 128, 64, 2, 1, {"in_ld": 192, "in_coff": 64}),                        # 64-channel panels (multi-tile workgroups when forced), input slice
-    (1, 37, 53, 64, 128, 1, 2, {"out_ld": 192, "out_coff": 64}),                      # ragged edges, panel-packed weights, output slice
-    (2, 40, 40, 64, 128, 1, 2, {}),                                                   # strip tiling of the 40-wide map
-    (3, 20, 20, 128, 64, 1, 1, {}),                                                   # strip tiling, 20-wide, 64 channels
-    (2, 20, 20, 64, 128, 1, 9, {}),                                                   # korder 9: 64-row panels on a 128-channel layer, strip tiling
-    (1, 24, 32, 64, 256, 2, 9, {"out_ld": 320, "out_coff": 64}),                      # ... 16x16 tiles, four panels, output slice
+    (1, 24, 32, 64, 128, 1, WL.TAP_MAJOR, {}),                                        # 16x16 tiles, 128-channel panels
+    (1, 16, 40, 128, 64, 2, WL.LINE_MAJOR, {"in_ld": 192, "in_coff": 64}),            # 64-channel panels (multi-tile workgroups when forced), input slice
+    (1, 37, 53, 64, 128, 1, WL.PATCH, {"out_ld": 192, "out_coff": 64}),               # ragged edges, panel-packed weights, output slice
+    (2, 40, 40, 64, 128, 1, WL.PATCH, {}),                                            # strip tiling of the 40-wide map
+    (3, 20, 20, 128, 64, 1, WL.LINE_MAJOR, {}),                                       # strip tiling, 20-wide, 64 channels
+    (2, 20, 20, 64, 128, 1, WL.PATCH_N64, {}),                                        # 64-row panels on a 128-channel layer, strip tiling
+    (1, 24, 32, 64, 256, 2, WL.PATCH_N64, {"out_ld": 320, "out_coff": 64}),           # ... 16x16 tiles, four panels, output slice
 ]
 
 
@@ -322,7 +290,7 @@ def test_patch_kernel_burst_reads_schedule_on_the_host():
     assert r.stdout.count("burst-reads") >= 4, r.stdout
 
 
-# the stride-2 LDS-patch kernel (csrc/y7t_conv_patch_s2.hip; korder 4): B, H, W, Cin, Cout, act, extras
+# the stride-2 LDS-patch kernel (csrc/y7t_conv_patch_s2.hip; PATCH_S2): B, H, W, Cin, Cout, act, extras
 S2_CASES = [
     (1, 16, 32, 64, 128, 1, {}),                                                      # one full 8 x 16 output tile, 128-channel panels (6-slot weight ring)
     (1, 16, 32, 64, 256, 1, {}),                                                      # 256-channel panels (3-slot ring, four waves along the channels)
@@ -337,19 +305,19 @@ def test_stride2_patch_kernel_source_on_the_host(case):
     """csrc/y7t_conv_patch_s2.hip (parity-split patch columns, 16-channel chunks, panel-packed weights): its load geometry, plane addressing, ring
     positions and epilogue against a plain stride-2 convolution"""
     B, H, W, Cin, Cout, act, kw = case
-    name = run_case(cs.lib(), B, H, W, Cin, Cout, 3, 2, act, 0, korder=4, **kw)
+    name = run_case(cs.lib(), B, H, W, Cin, Cout, 3, 2, act, 0, korder=WL.PATCH_S2, **kw)
     cp = (Cout + 127) // 128 * 128
     assert name == "patch_s2<%d>" % (256 if cp % 256 == 0 else 128), name
 
 
 def test_stride2_patch_kernel_rejects_what_it_cannot_run():
-    """korder 4 weights are readable by the stride-2 patch kernel only: a stride-1 layer carrying them is an error, not a silent fallback"""
+    """PATCH_S2 weights are readable by the stride-2 patch kernel only: a stride-1 layer carrying them is an error, not a silent fallback"""
     L = cs.lib()
     x = np.zeros((1, 8, 8, 64), np.float16)
     w = np.zeros((128, 576), np.float16)
     b = np.zeros(128, np.float32)
     out = np.zeros((1, 8, 8, 128), np.float16)
-    rc = L.cs_conv(x.ctypes.data, 64, 0, 1, 8, 8, 64, w.ctypes.data, b.ctypes.data, out.ctypes.data, 128, 0, 0, 128, 128, 3, 3, 1, 1, 1, 4, 0, 0, 0)
+    rc = L.cs_conv(x.ctypes.data, 64, 0, 1, 8, 8, 64, w.ctypes.data, b.ctypes.data, out.ctypes.data, 128, 0, 0, 128, 128, 3, 3, 1, 1, 1, WL.PATCH_S2, 0, 0, 0)
     assert rc != 0 and b"korder 4" in L.cs_last_error()
 
 
@@ -399,7 +367,7 @@ WS_CASES = [
 @pytest.mark.parametrize("case", WS_CASES, ids=lambda c: "%dx%dx%d_act%d" % c[:4])
 def test_weights_stationary_kernel_source_on_the_host(case):
     B, H, W, act, kw = case
-    name = run_case(cs.lib(), B, H, W, 64, 64, 3, 1, act, 0, korder=5, seed=B * 1000 + H + W, **kw)
+    name = run_case(cs.lib(), B, H, W, 64, 64, 3, 1, act, 0, korder=WL.WS64, seed=B * 1000 + H + W, **kw)
     assert name == "ws64<16,16>", name
 
 
@@ -420,16 +388,16 @@ def test_weights_stationary_kernel_on_the_tile_counter_on_the_host(case):
     L = cs.lib()
     L.cs_set_dyn(1)
     try:
-        name = run_case(L, B, H, W, 64, 64, 3, 1, act, 0, korder=5, seed=B * 1000 + H + W, **kw)
+        name = run_case(L, B, H, W, 64, 64, 3, 1, act, 0, korder=WL.WS64, seed=B * 1000 + H + W, **kw)
         assert name == "ws64<16,16> dyn", name
         assert all(L.cs_tile_counter(i) == 0 for i in range(8))          # the last workgroup to leave handed the counter back at zero
-        name = run_case(L, B, H, W, 64, 64, 3, 1, act, 0, korder=5, seed=B * 1000 + H + W + 1, **kw)      # ... so the next launch starts from it
+        name = run_case(L, B, H, W, 64, 64, 3, 1, act, 0, korder=WL.WS64, seed=B * 1000 + H + W + 1, **kw)      # ... so the next launch starts from it
         assert name == "ws64<16,16> dyn" and all(L.cs_tile_counter(i) == 0 for i in range(8))
     finally:
         L.cs_set_dyn(0)
 
 
-# B, H, W, Cout, act, slices -- the 128-channel sibling (csrc/y7t_conv_ws128.hip, korder 6): 4 x 16 tiles, four waves on the same 64 pixels with 32 output channels
+# B, H, W, Cout, act, slices -- the 128-channel sibling (csrc/y7t_conv_ws128.hip, WS128): 4 x 16 tiles, four waves on the same 64 pixels with 32 output channels
 # each, two channel tiles for Cout = 256 (the fake device's three workgroups split 2 + 1 over them)
 WS128_CASES = [
     (1, 4, 16, 128, 1, {}),                                                            # one tile, one workgroup
@@ -449,7 +417,7 @@ def test_weights_stationary_128_kernel_source_on_the_host(case, dyn):
     L.cs_set_dyn(dyn)
     try:
         for rep in range(1 + dyn):      # (tile counter: the second launch starts from the counters the first one handed back)
-            name = run_case(L, B, H, W, 128, Cout, 3, 1, act, 0, korder=6, seed=B * 1000 + H + W + rep, **kw)
+            name = run_case(L, B, H, W, 128, Cout, 3, 1, act, 0, korder=WL.WS128, seed=B * 1000 + H + W + rep, **kw)
             assert name == ("ws128<4,16> dyn" if dyn else "ws128<4,16>"), name
             assert all(L.cs_tile_counter(i) == 0 for i in range(8))
     finally:
@@ -473,7 +441,7 @@ def test_weights_stationary_128_stride2_kernel_source_on_the_host(case, dyn):
     L.cs_set_dyn(dyn)
     try:
         for rep in range(1 + dyn):
-            name = run_case(L, B, H, W, 128, Cout, 3, 2, act, 0, korder=6, seed=B * 1000 + H + W + rep, **kw)
+            name = run_case(L, B, H, W, 128, Cout, 3, 2, act, 0, korder=WL.WS128, seed=B * 1000 + H + W + rep, **kw)
             assert name == ("ws128_s2<2,16> dyn" if dyn else "ws128_s2<2,16>"), name
             assert all(L.cs_tile_counter(i) == 0 for i in range(8))
     finally:
@@ -503,10 +471,10 @@ def test_weights_stationary_128_fragment_reads_are_bank_conflict_free():
 
 
 def test_weights_stationary_kernel_rejects_what_it_cannot_run():
-    """korder 5 weights are readable by that kernel only: a ragged map (its store count must be exact), other channel counts, a stride -> argument error"""
+    """WS64 weights are readable by that kernel only: a ragged map (its store count must be exact), other channel counts, a stride -> argument error"""
     L = cs.lib()
     x, w, b, out = np.zeros((1, 20, 16, 64), np.float16), np.zeros((64, 576), np.float16), np.zeros(64, np.float32), np.zeros((1, 20, 16, 64), np.float16)
-    rc = L.cs_conv(x.ctypes.data, 64, 0, 1, 20, 16, 64, w.ctypes.data, b.ctypes.data, out.ctypes.data, 64, 0, 0, 64, 64, 3, 3, 1, 1, 1, 5, 0, 0, 0)
+    rc = L.cs_conv(x.ctypes.data, 64, 0, 1, 20, 16, 64, w.ctypes.data, b.ctypes.data, out.ctypes.data, 64, 0, 0, 64, 64, 3, 3, 1, 1, 1, WL.WS64, 0, 0, 0)
     assert rc != 0 and b"whole 16 x 16 tiles" in L.cs_last_error()
 
 
@@ -521,3 +489,20 @@ def test_weights_stationary_fragment_reads_are_bank_conflict_free():
                 for ks in range(4):
                     addr = [((l >> 4) * RP + (l & 15) * PIXB + hi * 16 + kw * PIXB + ks * 32) for l in g]
                     assert len({(a // 16) % 16 for a in addr}) == 16
+
+
+@pytest.mark.parametrize("korder", [12, 13, -1])
+def test_dispatch_refuses_a_weight_layout_it_does_not_know(korder):
+    """a korder that is no y7t_weight_layout (12 is the blob-only TWIN_TAIL of detector/layout.py) is an argument error that names it, and nothing is launched: the
+    output keeps its fill pattern.  (Until the layouts had names such an op ran on the generic kernel, with weights in whatever order they were.)"""
+    L = cs.lib()
+    rng = np.random.default_rng(korder + 1)
+    x = rng.normal(0, 1, (1, 4, 4, 8)).astype(np.float16)
+    w, b = rng.normal(0, 1, (64, 64)).astype(np.float16), np.ones(64, np.float32)
+    out = np.full((1, 4, 4, 8), 7.0, np.float16)
+    rc = L.cs_conv(x.ctypes.data, 8, 0, 1, 4, 4, 8, w.ctypes.data, b.ctypes.data, out.ctypes.data, 8, 0, 0, 8, 64, 1, 1, 1, 0, 1, korder, 0, 0, 0)
+    assert rc == -1                                                  # Y7T_E_ARG
+    assert b"unknown weight layout %d" % korder in L.cs_last_error()
+    assert np.all(out == 7.0)
+    rc = L.cs_conv(x.ctypes.data, 8, 0, 1, 4, 4, 8, w.ctypes.data, b.ctypes.data, out.ctypes.data, 8, 0, 0, 8, 64, 1, 1, 1, 0, 1, WL.TAP_MAJOR, 0, 0, 0)
+    assert rc == 0 and not np.any(out == 7.0)                        # (the same call with a layout the library knows does run)

@@ -11,6 +11,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.util import layer_cout_pad, pack_w
+from yolov7_tracker_amd.detector.layout import FORCE_PATCH, WeightLayout as WL, act_bits, layout_of
+
 pytestmark = pytest.mark.gpu
 
 
@@ -19,40 +22,6 @@ def L():
     from yolov7_tracker_amd import _lib
     _lib.require_gpu()
     return _lib.load()
-
-
-def pack_w(W, cin_pad, cout_pad, korder=False):
-    cout, cin, k, _ = W.shape
-    K = k * k * cin_pad
-    K_pad = (K + 63) // 64 * 64
-    Wt = np.zeros((cout, k, k, cin_pad), np.float32)
-    Wt[..., :cin] = W.transpose(0, 2, 3, 1)
-    if korder == 1:   # (kh, 64-channel chunk, kw) K order
-        Wt = Wt.reshape(cout, k, k, cin_pad // 64, 64).transpose(0, 1, 3, 2, 4)
-    blk = np.zeros((cout_pad, K_pad), np.float16)
-    blk[:cout, :K] = Wt.reshape(cout, -1).astype(np.float16)
-    if korder in (2, 9):   # patch-kernel panel order (9: 64-row panels although Cout_pad % 128 == 0)
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack(blk, cin_pad, narrow=korder == 9)
-    if korder in (3, 10):   # 1x1 panel order (10: 64-row panels although Cout_pad % 128 == 0)
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_linear(blk, narrow=korder == 10)
-    if korder == 4:   # stride-2 patch-kernel panel order (opt-in experiment)
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_s2(blk, cin_pad)
-    if korder == 5:   # register-fragment order of the weights-stationary 64 -> 64 kernel
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws(blk)
-    if korder == 6:   # ... of its 128-channel sibling
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws128(blk)
-    if korder == 7:   # 256 x 64 panels of the ping-pong 1x1 kernel
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.panel_pack_p8(blk)
-    if korder == 8:   # register-fragment order of the stride-2 weights-stationary kernel
-        from yolov7_tracker_amd.detector import weights
-        blk = weights.pack_ws_s2(blk)
-    return blk
 
 
 CONV_CASES = [
@@ -65,40 +34,40 @@ CONV_CASES = [
     (1, 16, 16, 256, 45, 1, 1, 0, 256, 0, 45, 0, 1),        # Detect head: fp32 out, Cout not a multiple of 4
     (3, 9, 9, 512, 512, 3, 1, 1, 512, 0, 512, 0, 0),        # small map, deep K
     (1, 130, 130, 32, 64, 3, 2, 1, 32, 0, 64, 0, 0),        # M not a multiple of the tile
-    (2, 24, 40, 128, 128, 3, 1, 1 | 256, 128, 0, 128, 0, 0),  # weights in the (kh, chunk, kw) K order (act bit 8)
-    (1, 33, 31, 192, 64, 3, 2, 1 | 256, 256, 64, 64, 0, 0),   # same, stride 2, input slice of a wider buffer
+    (2, 24, 40, 128, 128, 3, 1, 1 | act_bits(WL.LINE_MAJOR), 128, 0, 128, 0, 0),  # weights in the (kh, chunk, kw) K order (act bit 8)
+    (1, 33, 31, 192, 64, 3, 2, 1 | act_bits(WL.LINE_MAJOR), 256, 64, 64, 0, 0),  # same, stride 2, input slice of a wider buffer
     # LDS-patch kernel (3x3 / stride 1, Cin % 64 == 0): 16x16 tiles, 32x8 tiles, 64- and 128-channel panels, both K orders,
     # ragged image edges (act bit 9 forces the kernel when the tile efficiency is below its dispatch threshold), slices
-    (2, 80, 80, 128, 128, 3, 1, 1 | 256, 128, 0, 128, 0, 0),
+    (2, 80, 80, 128, 128, 3, 1, 1 | act_bits(WL.LINE_MAJOR), 128, 0, 128, 0, 0),
     (1, 64, 96, 64, 64, 3, 1, 1, 256, 128, 192, 64, 0),
     (1, 24, 64, 64, 128, 3, 1, 2, 64, 0, 128, 0, 0),
-    (2, 24, 64, 192, 64, 3, 1, 1 | 256, 192, 0, 64, 0, 0),
-    (2, 37, 53, 192, 256, 3, 1, 1 | 256 | 512, 256, 64, 320, 64, 0),
-    (1, 37, 70, 128, 64, 3, 1, 1 | 512, 128, 0, 64, 0, 0),
-    (3, 20, 20, 512, 512, 3, 1, 1 | 256 | 512, 512, 0, 512, 0, 0),
+    (2, 24, 64, 192, 64, 3, 1, 1 | act_bits(WL.LINE_MAJOR), 192, 0, 64, 0, 0),
+    (2, 37, 53, 192, 256, 3, 1, 1 | act_bits(WL.LINE_MAJOR) | FORCE_PATCH, 256, 64, 320, 64, 0),
+    (1, 37, 70, 128, 64, 3, 1, 1 | FORCE_PATCH, 128, 0, 64, 0, 0),
+    (3, 20, 20, 512, 512, 3, 1, 1 | act_bits(WL.LINE_MAJOR) | FORCE_PATCH, 512, 0, 512, 0, 0),
     # the same kernel fed with panel-packed weights (act bit 10; what detector/graph.py chooses for eligible layers)
-    (2, 80, 80, 128, 128, 3, 1, 1 | 1024, 128, 0, 128, 0, 0),
-    (1, 24, 64, 192, 64, 3, 1, 2 | 1024, 256, 64, 64, 0, 0),
-    (2, 37, 53, 64, 256, 3, 1, 1 | 1024, 64, 0, 320, 64, 0),
+    (2, 80, 80, 128, 128, 3, 1, 1 | act_bits(WL.PATCH), 128, 0, 128, 0, 0),
+    (1, 24, 64, 192, 64, 3, 1, 2 | act_bits(WL.PATCH), 256, 64, 64, 0, 0),
+    (2, 37, 53, 64, 256, 3, 1, 1 | act_bits(WL.PATCH), 64, 0, 320, 64, 0),
     # strip tiling of the narrow maps (W = 40, 20): padded images laid end to end, 256 consecutive positions per workgroup
-    (3, 40, 40, 128, 128, 3, 1, 1 | 1024, 128, 0, 128, 0, 0),
-    (2, 24, 40, 64, 64, 3, 1, 2 | 256, 128, 64, 192, 128, 0),
-    (5, 20, 20, 192, 256, 3, 1, 1 | 1024, 192, 0, 256, 0, 0),
+    (3, 40, 40, 128, 128, 3, 1, 1 | act_bits(WL.PATCH), 128, 0, 128, 0, 0),
+    (2, 24, 40, 64, 64, 3, 1, 2 | act_bits(WL.LINE_MAJOR), 128, 64, 192, 128, 0),
+    (5, 20, 20, 192, 256, 3, 1, 1 | act_bits(WL.PATCH), 192, 0, 256, 0, 0),
     (1, 7, 20, 64, 64, 3, 1, 1, 64, 0, 64, 0, 0),
     # multi-tile workgroups of the 64-channel patch kernel (act bit 9 forces them on small problems): tile count not a multiple of 4,
     # ragged edges, 2 and 6 chunks per tile, all three weight orders, output slice
-    (3, 48, 48, 64, 64, 3, 1, 1 | 512 | 1024, 64, 0, 64, 0, 0),
-    (5, 20, 20, 256, 256, 3, 1, 1 | 131072, 256, 0, 256, 0, 0),          # korder 9: the patch kernel's 64-row panels on a layer whose Cout would allow 128 (strip tiling)
-    (2, 32, 48, 64, 128, 3, 1, 2 | 131072, 64, 0, 256, 128, 0),          # ... 16x16 tiles, output slice
-    (3, 20, 20, 256, 256, 1, 1, 1 | 262144, 256, 0, 256, 0, 0),          # korder 10: 64-row 1x1 panels on a layer whose Cout would allow 128
-    (1, 24, 24, 96, 128, 1, 1, 2 | 262144, 256, 64, 384, 192, 0),        # ... slices, LeakyReLU
-    (1, 37, 70, 192, 64, 3, 1, 2 | 512 | 256, 256, 64, 192, 64, 0),
-    (2, 24, 64, 64, 192, 3, 1, 1 | 512, 64, 0, 192, 0, 0),
+    (3, 48, 48, 64, 64, 3, 1, 1 | FORCE_PATCH | act_bits(WL.PATCH), 64, 0, 64, 0, 0),
+    (5, 20, 20, 256, 256, 3, 1, 1 | act_bits(WL.PATCH_N64), 256, 0, 256, 0, 0),  # PATCH_N64: the patch kernel's 64-row panels on a layer whose Cout would allow 128 (strip tiling)
+    (2, 32, 48, 64, 128, 3, 1, 2 | act_bits(WL.PATCH_N64), 64, 0, 256, 128, 0),  # ... 16x16 tiles, output slice
+    (3, 20, 20, 256, 256, 1, 1, 1 | act_bits(WL.PANEL_1X1_N64), 256, 0, 256, 0, 0),  # PANEL_1X1_N64: 64-row 1x1 panels on a layer whose Cout would allow 128
+    (1, 24, 24, 96, 128, 1, 1, 2 | act_bits(WL.PANEL_1X1_N64), 256, 64, 384, 192, 0),  # ... slices, LeakyReLU
+    (1, 37, 70, 192, 64, 3, 1, 2 | FORCE_PATCH | act_bits(WL.LINE_MAJOR), 256, 64, 192, 64, 0),
+    (2, 24, 64, 64, 192, 3, 1, 1 | FORCE_PATCH, 64, 0, 192, 0, 0),
     # 1x1 layers with panel-packed weights (act bit 11): 128- and 64-row panels, Cin % 64 == 32, split-K on a small map, fp32 head
-    (2, 40, 40, 256, 256, 1, 1, 1 | 2048, 256, 0, 256, 0, 0),
-    (1, 24, 24, 96, 192, 1, 1, 2 | 2048, 256, 64, 384, 192, 0),
-    (1, 20, 20, 1024, 512, 1, 1, 1 | 2048, 1024, 0, 512, 0, 0),
-    (1, 16, 16, 256, 45, 1, 1, 0 | 2048, 256, 0, 45, 0, 1),
+    (2, 40, 40, 256, 256, 1, 1, 1 | act_bits(WL.PANEL_1X1), 256, 0, 256, 0, 0),
+    (1, 24, 24, 96, 192, 1, 1, 2 | act_bits(WL.PANEL_1X1), 256, 64, 384, 192, 0),
+    (1, 20, 20, 1024, 512, 1, 1, 1 | act_bits(WL.PANEL_1X1), 1024, 0, 512, 0, 0),
+    (1, 16, 16, 256, 45, 1, 1, 0 | act_bits(WL.PANEL_1X1), 256, 0, 45, 0, 1),
 ]
 
 
@@ -110,8 +79,8 @@ def test_conv_layer_matches_torch_fp32(L, case):
     x = rng.normal(0, 1, (B, H, W, in_ld)).astype(np.float16)
     Wt = (rng.normal(0, 1, (Cout, Cin, k, k)) / np.sqrt(Cin * k * k)).astype(np.float32)
     bias = rng.normal(0, 0.5, Cout).astype(np.float32)
-    korder = 10 if act & 262144 else 9 if act & 131072 else 8 if act & 65536 else 7 if act & 32768 else 6 if act & 16384 else 5 if act & 8192 else 4 if act & 4096 else 3 if act & 2048 else 2 if act & 1024 else int(bool(act & 256))
-    cout_pad = (Cout + 255) // 256 * 256 if korder == 7 else (Cout + 63) // 64 * 64 if korder not in (4, 6, 8) else (Cout + 127) // 128 * 128
+    korder = layout_of(act)[0]
+    cout_pad = layer_cout_pad(Cout, korder)
     act_code = act
     act = act & 255
     if k == 3 and s == 1 and Cin % 64 == 0:    # the dispatcher must send these to the patch kernel when tiles are >= 80 % useful
@@ -140,15 +109,15 @@ def test_conv_layer_matches_torch_fp32(L, case):
 
 
 # csrc/y7t_conv_ws.hip: the 64 -> 64 3x3 layers with the filter bank resident in registers, one persistent workgroup per compute unit walking a range of
-# 16 x 16 tiles through a three-buffer patch ring (act bit 13: korder 5).  Shapes: fewer tiles than compute units; thousands of tiles (every workgroup
+# 16 x 16 tiles through a three-buffer patch ring (act bit 13: WS64).  Shapes: fewer tiles than compute units; thousands of tiles (every workgroup
 # walks many, the ring wraps, uneven ranges); slices of concat buffers; both activations; the benchmarked layer itself (320 x 320, 8 frames).
 WS_CASES = [
     # B, H, W, Cin, Cout, k, s, act (bit 13), in_ld, in_coff, out_ld, out_coff, out_f32
-    (1, 16, 16, 64, 64, 3, 1, 1 | 8192, 64, 0, 64, 0, 0),
-    (1, 48, 80, 64, 64, 3, 1, 1 | 8192, 64, 0, 64, 0, 0),
-    (3, 160, 160, 64, 64, 3, 1, 2 | 8192, 128, 64, 256, 128, 0),
-    (7, 96, 112, 64, 64, 3, 1, 0 | 8192, 64, 0, 64, 0, 0),
-    (8, 320, 320, 64, 64, 3, 1, 1 | 8192, 128, 0, 256, 192, 0),
+    (1, 16, 16, 64, 64, 3, 1, 1 | act_bits(WL.WS64), 64, 0, 64, 0, 0),
+    (1, 48, 80, 64, 64, 3, 1, 1 | act_bits(WL.WS64), 64, 0, 64, 0, 0),
+    (3, 160, 160, 64, 64, 3, 1, 2 | act_bits(WL.WS64), 128, 64, 256, 128, 0),
+    (7, 96, 112, 64, 64, 3, 1, 0 | act_bits(WL.WS64), 64, 0, 64, 0, 0),
+    (8, 320, 320, 64, 64, 3, 1, 1 | act_bits(WL.WS64), 128, 0, 256, 192, 0),
 ]
 
 
@@ -159,15 +128,15 @@ def test_weights_stationary_kernel_matches_torch_fp32(L, case):
     assert L.y7t_last_kernel().decode() == "ws64<16,16>"
 
 
-# csrc/y7t_conv_ws128.hip: the 128-channel sibling (act bit 14: korder 6), here through the single-layer entry point = its statically partitioned form; the tile-counter
+# csrc/y7t_conv_ws128.hip: the 128-channel sibling (act bit 14: WS128), here through the single-layer entry point = its statically partitioned form; the tile-counter
 # form runs inside a plan (test_weights_stationary_kernels_on_the_tile_counter_inside_a_plan below, tests/test_detector_pinned_gpu.py with Y7T_CONV_WS128=1)
 WS128_CASES = [
     # B, H, W, Cin, Cout, k, s, act (bit 14), in_ld, in_coff, out_ld, out_coff, out_f32
-    (1, 4, 16, 128, 128, 3, 1, 1 | 16384, 128, 0, 128, 0, 0),
-    (1, 48, 80, 128, 128, 3, 1, 1 | 16384, 128, 0, 128, 0, 0),
-    (3, 160, 160, 128, 128, 3, 1, 2 | 16384, 256, 128, 512, 128, 0),
-    (5, 80, 80, 128, 256, 3, 1, 0 | 16384, 128, 0, 256, 0, 0),
-    (8, 160, 160, 128, 128, 3, 1, 1 | 16384, 512, 0, 128, 0, 0),
+    (1, 4, 16, 128, 128, 3, 1, 1 | act_bits(WL.WS128), 128, 0, 128, 0, 0),
+    (1, 48, 80, 128, 128, 3, 1, 1 | act_bits(WL.WS128), 128, 0, 128, 0, 0),
+    (3, 160, 160, 128, 128, 3, 1, 2 | act_bits(WL.WS128), 256, 128, 512, 128, 0),
+    (5, 80, 80, 128, 256, 3, 1, 0 | act_bits(WL.WS128), 128, 0, 256, 0, 0),
+    (8, 160, 160, 128, 128, 3, 1, 1 | act_bits(WL.WS128), 512, 0, 128, 0, 0),
 ]
 
 
@@ -179,11 +148,11 @@ def test_weights_stationary_128_kernel_matches_torch_fp32(L, case):
 
 # ... and its stride-2 form (S2: 2 x 16 output tiles, parity-split 5 x 33 patch): the two w6 layers (128 -> 256 at 320 x 320 and 160 x 160) and small / sliced / multi-image cases
 WS128_S2_CASES = [
-    (1, 4, 32, 128, 128, 3, 2, 1 | 16384, 128, 0, 128, 0, 0),
-    (1, 48, 96, 128, 256, 3, 2, 1 | 16384, 128, 0, 256, 0, 0),
-    (3, 160, 160, 128, 256, 3, 2, 2 | 16384, 256, 128, 512, 256, 0),
-    (4, 320, 320, 128, 256, 3, 2, 1 | 16384, 128, 0, 512, 0, 0),
-    (7, 20, 64, 128, 128, 3, 2, 0 | 16384, 128, 0, 128, 0, 0),
+    (1, 4, 32, 128, 128, 3, 2, 1 | act_bits(WL.WS128), 128, 0, 128, 0, 0),
+    (1, 48, 96, 128, 256, 3, 2, 1 | act_bits(WL.WS128), 128, 0, 256, 0, 0),
+    (3, 160, 160, 128, 256, 3, 2, 2 | act_bits(WL.WS128), 256, 128, 512, 256, 0),
+    (4, 320, 320, 128, 256, 3, 2, 1 | act_bits(WL.WS128), 128, 0, 512, 0, 0),
+    (7, 20, 64, 128, 128, 3, 2, 0 | act_bits(WL.WS128), 128, 0, 128, 0, 0),
 ]
 
 
@@ -227,15 +196,15 @@ def test_weights_stationary_kernels_on_the_tile_counter_inside_a_plan(monkeypatc
 
 
 # csrc/y7t_conv_ws_s2.hip: the 64 -> 128 3x3 / stride 2 layer with the filter bank resident in registers, a persistent workgroup per compute unit walking 2 x 32 output
-# tiles through a three-buffer patch ring (act bit 16: korder 8).  Shapes: fewer tiles than compute units, thousands of tiles (uneven ranges, the ring wraps), slices of
+# tiles through a three-buffer patch ring (act bit 16: WS_S2).  Shapes: fewer tiles than compute units, thousands of tiles (uneven ranges, the ring wraps), slices of
 # wider buffers, the activations, and the benchmarked layer itself (640 x 640 -> 320 x 320, 8 frames).
 WS_S2_CASES = [
     # B, H, W, Cin, Cout, k, s, act (bit 16), in_ld, in_coff, out_ld, out_coff, out_f32
-    (1, 4, 64, 64, 128, 3, 2, 1 | 65536, 64, 0, 128, 0, 0),
-    (1, 96, 192, 64, 128, 3, 2, 1 | 65536, 64, 0, 128, 0, 0),
-    (3, 160, 320, 64, 128, 3, 2, 2 | 65536, 128, 64, 256, 128, 0),
-    (5, 100, 128, 64, 128, 3, 2, 0 | 65536, 64, 0, 128, 0, 0),
-    (8, 640, 640, 64, 128, 3, 2, 1 | 65536, 64, 0, 128, 0, 0),
+    (1, 4, 64, 64, 128, 3, 2, 1 | act_bits(WL.WS_S2), 64, 0, 128, 0, 0),
+    (1, 96, 192, 64, 128, 3, 2, 1 | act_bits(WL.WS_S2), 64, 0, 128, 0, 0),
+    (3, 160, 320, 64, 128, 3, 2, 2 | act_bits(WL.WS_S2), 128, 64, 256, 128, 0),
+    (5, 100, 128, 64, 128, 3, 2, 0 | act_bits(WL.WS_S2), 64, 0, 128, 0, 0),
+    (8, 640, 640, 64, 128, 3, 2, 1 | act_bits(WL.WS_S2), 64, 0, 128, 0, 0),
 ]
 
 
@@ -245,22 +214,22 @@ def test_stride2_weights_stationary_kernel_matches_torch_fp32(L, case):
     assert L.y7t_last_kernel().decode() == "ws_s2<2,32>"
 
 
-# csrc/y7t_conv_p8.hip: the 1x1 layers with Cout % 256 == 0 on the 256 x 256 x 64 ping-pong pipeline (act bit 15: korder 7).  Shapes: one K-tile (prologue + tail only), odd and
+# csrc/y7t_conv_p8.hip: the 1x1 layers with Cout % 256 == 0 on the 256 x 256 x 64 ping-pong pipeline (act bit 15: P8).  Shapes: one K-tile (prologue + tail only), odd and
 # even K-tile counts, ragged pixel tiles, several channel tiles, thousands of tiles (every CU runs many workgroups back to back), slices of concat buffers, the activations,
 # and two layers of the benchmarked list at 8 frames.
 P8_CASES = [
     # B, H, W, Cin, Cout, k, s, act (bit 15), in_ld, in_coff, out_ld, out_coff, out_f32
-    (1, 16, 16, 64, 256, 1, 1, 1 | 32768, 64, 0, 256, 0, 0),
-    (1, 15, 20, 192, 256, 1, 1, 0 | 32768, 192, 0, 256, 0, 0),
-    (2, 33, 47, 128, 512, 1, 1, 2 | 32768, 256, 128, 1024, 256, 0),
-    (3, 80, 80, 512, 256, 1, 1, 1 | 32768, 512, 0, 512, 256, 0),
-    (8, 80, 80, 1024, 512, 1, 1, 1 | 32768, 1024, 0, 512, 0, 0),
-    (8, 40, 40, 1536, 768, 1, 1, 1 | 32768, 1536, 0, 768, 0, 0),
+    (1, 16, 16, 64, 256, 1, 1, 1 | act_bits(WL.P8), 64, 0, 256, 0, 0),
+    (1, 15, 20, 192, 256, 1, 1, 0 | act_bits(WL.P8), 192, 0, 256, 0, 0),
+    (2, 33, 47, 128, 512, 1, 1, 2 | act_bits(WL.P8), 256, 128, 1024, 256, 0),
+    (3, 80, 80, 512, 256, 1, 1, 1 | act_bits(WL.P8), 512, 0, 512, 256, 0),
+    (8, 80, 80, 1024, 512, 1, 1, 1 | act_bits(WL.P8), 1024, 0, 512, 0, 0),
+    (8, 40, 40, 1536, 768, 1, 1, 1 | act_bits(WL.P8), 1536, 0, 768, 0, 0),
     # round 6, the persistent form (a workgroup walks a column of pixel tiles: more tiles than CUs, an even number of K-tiles): three channel tiles on 255 workgroups with a
     # ragged last pixel tile; one channel tile, slices of wider buffers, LeakyReLU; two K-tiles per tile (the shortest loop the cross-tile prefetch allows)
-    (5, 79, 79, 512, 768, 1, 1, 1 | 32768, 512, 0, 768, 0, 0),
-    (12, 80, 80, 256, 256, 1, 1, 2 | 32768, 512, 256, 768, 512, 0),
-    (6, 120, 120, 128, 256, 1, 1, 1 | 32768, 128, 0, 256, 0, 0),
+    (5, 79, 79, 512, 768, 1, 1, 1 | act_bits(WL.P8), 512, 0, 768, 0, 0),
+    (12, 80, 80, 256, 256, 1, 1, 2 | act_bits(WL.P8), 512, 256, 768, 512, 0),
+    (6, 120, 120, 128, 256, 1, 1, 1 | act_bits(WL.P8), 128, 0, 256, 0, 0),
 ]
 
 
@@ -289,7 +258,7 @@ def test_pingpong_1x1_kernel_is_deterministic_under_load(L):
         out = torch.zeros((B, H, W, Cout), dtype=torch.float16, device="cuda")
         with torch.cuda.stream(side):
             big[1].copy_(big[0], non_blocking=True)
-        _lib.check(L.y7t_conv2d_nhwc_f16(_lib.ptr(x), Cin, 0, B, H, W, Cin, _lib.ptr(wp), _lib.ptr(b), _lib.ptr(out), Cout, 0, 0, Cout, Cout, 1, 1, 1, 0, 1 | 32768,
+        _lib.check(L.y7t_conv2d_nhwc_f16(_lib.ptr(x), Cin, 0, B, H, W, Cin, _lib.ptr(wp), _lib.ptr(b), _lib.ptr(out), Cout, 0, 0, Cout, Cout, 1, 1, 1, 0, 1 | act_bits(WL.P8),
                                          _lib.ptr(zeros), _lib.stream_ptr()))
         outs.append(out)
     torch.cuda.synchronize()
@@ -317,15 +286,15 @@ def test_pingpong_1x1_upsample_on_read_equals_materialised_upsample(monkeypatch)
     assert all(torch.equal(x, y) for x, y in zip(a, b))
 
 
-# csrc/y7t_conv_patch_s2.hip: the stride-2 LDS-patch kernel (parity-split patch columns, 16-channel chunks; korder 4 = act bit 12), 128- and 256-channel panels
+# csrc/y7t_conv_patch_s2.hip: the stride-2 LDS-patch kernel (parity-split patch columns, 16-channel chunks; PATCH_S2 = act bit 12), 128- and 256-channel panels
 S2_CASES = [
-    # B, H, W, Cin, Cout, k, s, act (bit 12: korder 4), in_ld, in_coff, out_ld, out_coff, out_f32
-    (1, 16, 32, 64, 128, 3, 2, 1 | 4096, 64, 0, 128, 0, 0),
-    (2, 46, 90, 128, 256, 3, 2, 1 | 4096, 192, 64, 320, 64, 0),
-    (4, 80, 80, 256, 384, 3, 2, 1 | 4096, 256, 0, 384, 0, 0),
-    (2, 41, 37, 192, 248, 3, 2, 2 | 4096, 192, 0, 256, 0, 0),
-    (8, 160, 160, 64, 128, 3, 2, 1 | 4096, 64, 0, 128, 0, 0),
-    (2, 40, 40, 768, 1024, 3, 2, 1 | 4096, 768, 0, 1024, 0, 0),
+    # B, H, W, Cin, Cout, k, s, act (bit 12: PATCH_S2), in_ld, in_coff, out_ld, out_coff, out_f32
+    (1, 16, 32, 64, 128, 3, 2, 1 | act_bits(WL.PATCH_S2), 64, 0, 128, 0, 0),
+    (2, 46, 90, 128, 256, 3, 2, 1 | act_bits(WL.PATCH_S2), 192, 64, 320, 64, 0),
+    (4, 80, 80, 256, 384, 3, 2, 1 | act_bits(WL.PATCH_S2), 256, 0, 384, 0, 0),
+    (2, 41, 37, 192, 248, 3, 2, 2 | act_bits(WL.PATCH_S2), 192, 0, 256, 0, 0),
+    (8, 160, 160, 64, 128, 3, 2, 1 | act_bits(WL.PATCH_S2), 64, 0, 128, 0, 0),
+    (2, 40, 40, 768, 1024, 3, 2, 1 | act_bits(WL.PATCH_S2), 768, 0, 1024, 0, 0),
 ]
 
 
@@ -522,7 +491,7 @@ def test_fused_detect_forward_equals_plain_forward():
 @pytest.mark.parametrize("B,H,W,act,kw", [(1, 4, 64, 1, {}), (2, 8, 128, 2, {"in_ld": 128, "in_coff": 64, "out_ld": 256, "out_coff": 128}), (3, 64, 192, 1, {}), (1, 640, 640, 1, {})],
                          ids=["one-tile", "slices-leaky", "many-tiles", "640x640"])
 def test_stride2_weights_stationary_with_the_twin_1x1_behind_it(L, B, H, W, act, kw):
-    """korder 11 through the C ABI (y7t_conv2d_nhwc_f16, act bit 19): 3x3 / stride 2 64 -> 128 + activation, then -- on the tile in LDS, the tensor between the layers never
+    """WS_S2_TWIN through the C ABI (y7t_conv2d_nhwc_f16, act bit 19): 3x3 / stride 2 64 -> 128 + activation, then -- on the tile in LDS, the tensor between the layers never
     reaches memory -- the 128 -> 128 1x1 convolution + activation.  Reference: the two layers one after the other in fp32 on the fp16 weights, middle tensor rounded to fp16."""
     from yolov7_tracker_amd import _lib
     from yolov7_tracker_amd.detector import weights
@@ -539,7 +508,7 @@ def test_stride2_weights_stationary_with_the_twin_1x1_behind_it(L, B, H, W, act,
     out = torch.full((B, H // 2, W // 2, out_ld), 7.0, dtype=torch.float16, device="cuda")
     zeros = torch.zeros(128, dtype=torch.float16, device="cuda")
     _lib.check(L.y7t_conv2d_nhwc_f16(_lib.ptr(xd), in_ld, in_coff, B, H, W, 64, _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(out), out_ld, out_coff, 0, 128, 128, 3, 3, 2, 1,
-                                     act | 524288, _lib.ptr(zeros), _lib.stream_ptr()))
+                                     act | act_bits(WL.WS_S2_TWIN), _lib.ptr(zeros), _lib.stream_ptr()))
     torch.cuda.synchronize()
     assert L.y7t_last_kernel().decode() == "ws_s2<2,32> + 1x1"
     f = F.silu if act == 1 else (lambda t: F.leaky_relu(t, 0.1))

@@ -10,6 +10,7 @@ import torch
 from oracle import detector_torch as dt
 from tests import util
 from yolov7_tracker_amd.detector import arch, graph, weights
+from yolov7_tracker_amd.detector.layout import WeightLayout as WL
 
 CASES = [("tiny", "yolov7-tiny", 80, (64, 96)), ("w6", "yolov7-w6", 10, (128, 128))]
 
@@ -40,7 +41,7 @@ def test_graph_census_matches_survey():
     p = graph.lower(graph.parse(arch.yolov7_w6(10))[0], 1280, 1280, 1)
     n_convs = lambda pl: sum(len(w["wkey"]) if isinstance(w["wkey"], tuple) else 1 for w in pl.wlayout)
     assert n_convs(p) == 107 and abs(p.macs / 1e9 - 177.45) < 0.01
-    fused_s2 = 1      # ... and the stride-2 64 -> 128 layer with the first twin pair behind it (korder 11)
+    fused_s2 = 1      # ... and the stride-2 64 -> 128 layer with the first twin pair behind it (WS_S2_TWIN)
     assert (p.ops["type"] == 0).sum() == 107 - 11 - fused_s2       # the 11 twin 1x1 pairs of the ELAN blocks run as one launch each
     assert [h["stride"] for h in p.heads] == [8, 16, 32, 64] and sum(3 * h["ny"] * h["nx"] for h in p.heads) == 102000
     p = graph.lower(graph.parse(arch.yolov7_tiny(80))[0], 640, 640, 1)
@@ -151,7 +152,7 @@ def _strip_anchor_buffers(sd, tmp_path):
 
 
 def test_weight_panel_packings_are_permutations_with_the_documented_layout():
-    """CPU: the two panel orders of detector/weights.py (korder 2: LDS-patch kernel; korder 3: 1x1 layers of the generic kernel)
+    """CPU: the two panel orders of detector/weights.py (PATCH: LDS-patch kernel; PANEL_1X1: 1x1 layers of the generic kernel)
     are pure permutations of the [Cout_pad][K] block, and element (tile, K-step, row, slot) is where the kernels' DMA expects it:
     slot s of row r holds channel octet s ^ ((r >> 2) & 3) of the step's 32 channels"""
     import numpy as np
@@ -180,8 +181,8 @@ def test_weight_panel_packings_are_permutations_with_the_documented_layout():
 
 
 def test_stride2_panel_packing_and_opt_in_lowering(monkeypatch):
-    """CPU: korder 4 (csrc/y7t_conv_patch_s2.hip, opt-in experiment): the packing is a permutation with slot s of row r = channel octet s ^ ((r >> 3) & 1) of the
-    K-step's 16 channels; the default lowering of yolov7-w6 contains no korder-4 op, with Y7T_CONV_PATCH_S2=1 exactly the eight stride-2 3x3 layers with
+    """CPU: PATCH_S2 (csrc/y7t_conv_patch_s2.hip, opt-in experiment): the packing is a permutation with slot s of row r = channel octet s ^ ((r >> 3) & 1) of the
+    K-step's 16 channels; the default lowering of yolov7-w6 contains no PATCH_S2 op, with Y7T_CONV_PATCH_S2=1 exactly the eight stride-2 3x3 layers with
     Cin % 64 == 0 carry it (the stem's successor 64 -> 128 included) and nothing else changes"""
     import numpy as np
     from yolov7_tracker_amd.detector import arch, graph, weights
@@ -196,35 +197,35 @@ def test_stride2_panel_packing_and_opt_in_lowering(monkeypatch):
             o = ((((tile * nc16 + c) * 9 + tap) * BN + r) * 2 + s) * 8
             k = tap * cin + c * 16 + (s ^ ((r >> 3) & 1)) * 8
             assert np.array_equal(flat[o:o + 8], blk[tile * BN + r, k:k + 8])
-    monkeypatch.setenv("Y7T_CONV_WS_S2", "0")      # (round 4: the 640^2 64 -> 128 layer otherwise goes to its own weights-stationary kernel, korder 8, before this rule is asked)
-    monkeypatch.setenv("Y7T_CONV_WS128", "0")      # (round 5: the two Cin = 128 layers otherwise go to ws128's stride-2 form, korder 6)
+    monkeypatch.setenv("Y7T_CONV_WS_S2", "0")      # (round 4: the 640^2 64 -> 128 layer otherwise goes to its own weights-stationary kernel, WS_S2, before this rule is asked)
+    monkeypatch.setenv("Y7T_CONV_WS128", "0")      # (round 5: the two Cin = 128 layers otherwise go to ws128's stride-2 form, WS128)
     monkeypatch.setenv("Y7T_CONV_PATCH_S2", "0")
     base = graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
-    assert not any(int(op["korder"]) == 4 for op in base.ops)
+    assert not any(op["korder"] == WL.PATCH_S2 for op in base.ops)
     monkeypatch.delenv("Y7T_CONV_PATCH_S2")
     # the default rule = where the kernel measured faster (round 3): 256-channel panels, Cin >= 128, >= 50 000 output pixels per launch
     auto = graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
-    took = sorted((int(op["H"]), int(op["Cin"]), int(op["Cout"])) for op in auto.ops if int(op["korder"]) == 4)
+    took = sorted((int(op["H"]), int(op["Cin"]), int(op["Cout"])) for op in auto.ops if op["korder"] == WL.PATCH_S2)
     assert took == [(80, 512, 768), (160, 128, 256), (160, 256, 512), (320, 128, 256)], took
-    assert not any(int(op["korder"]) == 4 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=1).ops)      # batch 1: generic + split-K
+    assert not any(op["korder"] == WL.PATCH_S2 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=1).ops)      # batch 1: generic + split-K
     monkeypatch.setenv("Y7T_CONV_PATCH_S2", "1")
     exp = graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
     assert len(exp.ops) == len(base.ops)
     changed = [(a, b) for a, b in zip(base.ops, exp.ops) if int(a["korder"]) != int(b["korder"])]
-    assert len(changed) == 8 and all(int(b["korder"]) == 4 and int(b["stride"]) == 2 and int(b["KH"]) == 3 and int(b["Cin"]) % 64 == 0 for _, b in changed)
+    assert len(changed) == 8 and all(b["korder"] == WL.PATCH_S2 and int(b["stride"]) == 2 and int(b["KH"]) == 3 and int(b["Cin"]) % 64 == 0 for _, b in changed)
     for a, b in zip(base.ops, exp.ops):
         for f in a.dtype.names:
             assert f == "korder" or a[f] == b[f]
     # Y7T_CONV_PATCH_S2_MIN_COUT is an EXPERIMENT switch: the product library ignores it; the lowering honours it only beside the measuring build (liby7t_ablate.so)
     monkeypatch.setenv("Y7T_CONV_PATCH_S2_MIN_COUT", "256")
-    assert sum(int(op["korder"]) == 4 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32).ops) == 8
+    assert sum(op["korder"] == WL.PATCH_S2 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32).ops) == 8
     monkeypatch.setenv("Y7T_LIB", "/somewhere/liby7t_ablate.so")
     wide = graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
-    assert sum(int(op["korder"]) == 4 for op in wide.ops) == 7          # all but the 64 -> 128 layer at 640x640
+    assert sum(op["korder"] == WL.PATCH_S2 for op in wide.ops) == 7          # all but the 64 -> 128 layer at 640x640
 
 
 def test_weights_stationary_128_packing_and_lowering(monkeypatch):
-    """CPU: korder 6 = the filter bank of a 128 -> 128 k 3x3 layer as MFMA A-fragments per 128-channel output tile (csrc/y7t_conv_ws128.hip): a permutation with the
+    """CPU: WS128 = the filter bank of a 128 -> 128 k 3x3 layer as MFMA A-fragments per 128-channel output tile (csrc/y7t_conv_ws128.hip): a permutation with the
     documented index map; with Y7T_CONV_WS128=1 the lowering gives it the 128 -> 128 / 256 layers on maps of whole 4 x 16 tiles and nothing else changes; =0 leaves the
     plan without it"""
     from yolov7_tracker_amd.detector import arch, graph, weights
@@ -237,21 +238,21 @@ def test_weights_stationary_128_packing_and_lowering(monkeypatch):
     low = lambda: graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
     monkeypatch.setenv("Y7T_CONV_WS128", "0")
     base = low()
-    assert not any(int(op["korder"]) == 6 for op in base.ops)
+    assert not any(op["korder"] == WL.WS128 for op in base.ops)
     monkeypatch.setenv("Y7T_CONV_WS128", "1")
     exp = low()
-    took = [(int(op["H"]), int(op["Cin"]), int(op["Cout"]), int(op["stride"])) for op in exp.ops if int(op["korder"]) == 6]
+    took = [(int(op["H"]), int(op["Cin"]), int(op["Cout"]), int(op["stride"])) for op in exp.ops if op["korder"] == WL.WS128]
     assert sorted(took) == sorted([(160, 128, 128, 1)] * 4 + [(80, 128, 128, 1)] * 6 + [(160, 128, 256, 1)] + [(320, 128, 256, 2), (160, 128, 256, 2)]), took      # (the last two: the stride-2 form)
     for a, b in zip(base.ops, exp.ops):
         for f in a.dtype.names:
-            assert f == "korder" or a[f] == b[f] or (f in ("Cout_pad", "w_off", "bias_off") and int(b["korder"]) == 6), (f, a[f], b[f])
+            assert f == "korder" or a[f] == b[f] or (f in ("Cout_pad", "w_off", "bias_off") and b["korder"] == WL.WS128), (f, a[f], b[f])
     monkeypatch.setenv("Y7T_LIB", "/somewhere/liby7t_ablate.so")      # beside the measuring build the stride-2 form alone can be switched off (an experiment switch)
     monkeypatch.setenv("Y7T_CONV_WS128_S2", "0")
-    assert sum(int(op["korder"]) == 6 for op in low().ops) == 11
+    assert sum(op["korder"] == WL.WS128 for op in low().ops) == 11
 
 
 def test_weights_stationary_packing_and_lowering(monkeypatch):
-    """CPU: korder 5 = the 64 x 576 filter bank of a 64 -> 64 3x3 layer as MFMA A-fragments (csrc/y7t_conv_ws.hip): a permutation with the documented
+    """CPU: WS64 = the 64 x 576 filter bank of a 64 -> 64 3x3 layer as MFMA A-fragments (csrc/y7t_conv_ws.hip): a permutation with the documented
     index map; the lowering sends exactly the seven 64 -> 64 layers on the 320^2 / 160^2 maps to it and nothing else changes"""
     from yolov7_tracker_amd.detector import arch, graph, weights
     blk = np.random.default_rng(0).permutation(64 * 576).astype(np.float64).reshape(64, 576)
@@ -263,15 +264,15 @@ def test_weights_stationary_packing_and_lowering(monkeypatch):
     low = lambda: graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=32)
     monkeypatch.setenv("Y7T_CONV_WS", "0")
     base = low()
-    assert not any(int(op["korder"]) == 5 for op in base.ops)
+    assert not any(op["korder"] == WL.WS64 for op in base.ops)
     monkeypatch.delenv("Y7T_CONV_WS")
     exp = low()
-    took = [(int(op["H"]), int(op["Cin"]), int(op["Cout"])) for op in exp.ops if int(op["korder"]) == 5]
+    took = [(int(op["H"]), int(op["Cin"]), int(op["Cout"])) for op in exp.ops if op["korder"] == WL.WS64]
     assert took == [(320, 64, 64)] * 4 + [(160, 64, 64)] * 3
     for a, b in zip(base.ops, exp.ops):
         for f in a.dtype.names:
             assert f == "korder" or a[f] == b[f]
-    assert not any(int(op["korder"]) == 5 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=1).ops)      # 400 tiles: too few
+    assert not any(op["korder"] == WL.WS64 for op in graph.lower(graph.parse(arch.ARCHS["yolov7-w6"](10))[0], 1280, 1280, max_batch=1).ops)      # 400 tiles: too few
 
 
 def test_patch_eligibility_rule():
@@ -279,7 +280,7 @@ def test_patch_eligibility_rule():
     from yolov7_tracker_amd.detector import graph
     ok = lambda H, W, ci, co, B, **kw: graph.patch_eligible(H, W, ci, co, kw.get("k", 3), kw.get("s", 1), kw.get("p", 1), co, 0, 0, B)
     assert ok(80, 80, 256, 256, 32) and ok(320, 320, 64, 64, 32) and ok(40, 40, 384, 384, 32) and ok(20, 20, 512, 1024, 32)
-    assert ok(20, 20, 512, 512, 32) and ok(20, 20, 256, 256, 32)      # round 4: 64-row panels (korder 9) where 128 rows give fewer than 256 workgroups, threshold 200
+    assert ok(20, 20, 512, 512, 32) and ok(20, 20, 256, 256, 32)      # round 4: 64-row panels (PATCH_N64) where 128 rows give fewer than 256 workgroups, threshold 200
     assert graph.patch_panel_rows(20, 20, 512, 32) == 64 and graph.patch_panel_rows(20, 20, 1024, 80) == 128 and graph.patch_panel_rows(80, 80, 192, 32) == 64
     assert graph.patch_panel_rows(20, 20, 512, 80) == 64 and graph.patch_panel_rows(20, 20, 1024, 32) == 64      # round 6, measured at 80 frames: 64-row panels below 512 tiles of 128 rows (500 for the 20 x 20 512 -> 512 layers)
     assert ok(20, 20, 512, 512, 8) and not ok(20, 20, 512, 512, 4)      # 100 workgroups' worth of 256-pixel tiles (64-row panels): 8 * 400 * 8; 4 frames are too few
@@ -298,19 +299,19 @@ def test_lowering_of_the_benchmarked_list_by_weight_order(monkeypatch):
         monkeypatch.delenv(k, raising=False)
     import collections
     hist = lambda B: dict(sorted(collections.Counter(int(o["korder"]) for o in graph.lower(graph.parse(arch.yolov7_w6(10))[0], 1280, 1280, B).ops if int(o["type"]) == 0).items()))
-    # 0 stem (fused frame -> conv kernel); 1 generic 3x3 (three stride-2 layers); 2 LDS-patch (16x16 tiles + 40-wide strips); 3 1x1 panels (incl. 3 upsample-on-read, 4 Detect);
-    # 4 stride-2 LDS-patch; 5 weights-stationary 64 -> 64; 6 weights-stationary 128 -> 128 k (round 5: eleven of the former korder-2 launches at stride 1 + the two Cin = 128 stride-2 layers, formerly korder 4); 7 p8; 9 patch with 64-row panels (the 20x20 layers); 10 1x1 with 64-row panels (< 500 tiles);
-    # 11 the stride-2 weights-stationary layer + the twin 1x1 behind it in one launch
+    # TAP_MAJOR: the stem (fused frame -> conv kernel); LINE_MAJOR: generic 3x3 (three stride-2 layers); PATCH: 16x16 tiles + 40-wide strips; PANEL_1X1 incl. 3 upsample-on-read,
+    # 4 Detect; WS128: (round 5) eleven of the former PATCH launches at stride 1 + the two Cin = 128 stride-2 layers, formerly PATCH_S2; PATCH_N64: the 20x20 layers;
+    # PANEL_1X1_N64: < 500 tiles; WS_S2_TWIN: the stride-2 weights-stationary layer + the twin 1x1 behind it in one launch
     # (round 6: p8 on every 1x1 grid of >= 1500 tiles or of one full round of the chip, 64-row strip panels below 512 tiles: profiles/r06_batch_80.txt)
-    assert hist(80) == {0: 1, 1: 3, 2: 22, 3: 13, 4: 2, 5: 7, 6: 13, 7: 23, 9: 10, 11: 1}      # the benchmarked list
-    assert hist(32) == {0: 1, 1: 3, 2: 21, 3: 19, 4: 2, 5: 7, 6: 13, 7: 10, 9: 11, 10: 7, 11: 1}
-    assert hist(40) == {0: 1, 1: 3, 2: 21, 3: 18, 4: 2, 5: 7, 6: 13, 7: 17, 9: 11, 10: 1, 11: 1}      # 40 frames: six of the 20x20 1x1 layers reach 500 tiles of 128 rows
+    assert hist(80) == {WL.TAP_MAJOR: 1, WL.LINE_MAJOR: 3, WL.PATCH: 22, WL.PANEL_1X1: 13, WL.PATCH_S2: 2, WL.WS64: 7, WL.WS128: 13, WL.P8: 23, WL.PATCH_N64: 10, WL.WS_S2_TWIN: 1}      # the benchmarked list
+    assert hist(32) == {WL.TAP_MAJOR: 1, WL.LINE_MAJOR: 3, WL.PATCH: 21, WL.PANEL_1X1: 19, WL.PATCH_S2: 2, WL.WS64: 7, WL.WS128: 13, WL.P8: 10, WL.PATCH_N64: 11, WL.PANEL_1X1_N64: 7, WL.WS_S2_TWIN: 1}
+    assert hist(40) == {WL.TAP_MAJOR: 1, WL.LINE_MAJOR: 3, WL.PATCH: 21, WL.PANEL_1X1: 18, WL.PATCH_S2: 2, WL.WS64: 7, WL.WS128: 13, WL.P8: 17, WL.PATCH_N64: 11, WL.PANEL_1X1_N64: 1, WL.WS_S2_TWIN: 1}      # 40 frames: six of the 20x20 1x1 layers reach 500 tiles of 128 rows
     h1 = hist(1)
-    assert h1 == {0: 1, 1: 33, 2: 8, 3: 8, 9: 16, 10: 28, 11: 1} and h1.get(5, 0) == 0 and h1.get(7, 0) == 0 and h1.get(4, 0) == 0      # one frame: no persistent 64 -> 64 / p8 / stride-2 patch launches
+    assert h1 == {WL.TAP_MAJOR: 1, WL.LINE_MAJOR: 33, WL.PATCH: 8, WL.PANEL_1X1: 8, WL.PATCH_N64: 16, WL.PANEL_1X1_N64: 28, WL.WS_S2_TWIN: 1} and h1.get(WL.WS64, 0) == 0 and h1.get(WL.P8, 0) == 0 and h1.get(WL.PATCH_S2, 0) == 0      # one frame: no persistent 64 -> 64 / p8 / stride-2 patch launches
     monkeypatch.setenv("Y7T_CONV_WS_S2_FUSE", "0")      # an experiment switch: nothing changes for the product library ...
-    assert hist(32)[11] == 1
+    assert hist(32)[WL.WS_S2_TWIN] == 1
     monkeypatch.setenv("Y7T_LIB", "/somewhere/liby7t_ablate.so")      # ... beside the measuring build the fusion can be switched off
-    assert hist(32)[8] == 1 and 11 not in hist(32) and hist(32)[3] == 20
+    assert hist(32)[WL.WS_S2] == 1 and WL.WS_S2_TWIN not in hist(32) and hist(32)[WL.PANEL_1X1] == 20
 
 
 def test_training_graph_spec_and_liveness():

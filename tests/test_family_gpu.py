@@ -9,6 +9,7 @@ import torch
 
 from tests import family_ref as fr
 from tests import family_teacher, util
+from yolov7_tracker_amd.detector.layout import layout_of
 
 pytestmark = pytest.mark.gpu
 
@@ -199,24 +200,18 @@ def test_whole_network_heads_against_the_reference_golden(name):
 
 
 # ------------------------------------------------------------------------------------------------ d. the convolution shapes the graphs bring
-KORDER_BIT = {0: 0, 1: 256, 2: 1024, 3: 2048, 4: 4096, 5: 8192, 6: 16384, 7: 32768, 8: 65536, 9: 131072, 10: 262144}
-
-
-def _korder_of(act):
-    return next((k for k in range(10, 1, -1) if act & KORDER_BIT[k]), int(bool(act & 256)))
-
-
 def new_conv_cases():
     """every distinct (korder, Cin, Cout, k, stride) of the five plans at their nominal size (max_batch 8) that no case list of tests/test_detector_gpu.py runs,
     as a case of that file's test: the smallest map the kernel family of that weight order takes, batch 1, sliced into wider buffers where the plan slices"""
     from tests import test_detector_gpu as tdg
     from yolov7_tracker_amd.detector import arch, graph
+    from yolov7_tracker_amd.detector.layout import WeightLayout as WL, act_bits
     have = set()
     for attr in dir(tdg):
         if attr.endswith("_CASES"):
             for c in getattr(tdg, attr):
                 if isinstance(c, tuple) and len(c) == 13:
-                    have.add((_korder_of(c[7]), c[3], c[4], c[5], c[6]))
+                    have.add((layout_of(c[7])[0], c[3], c[4], c[5], c[6]))
     cases, seen = [], set()
     for name in fr.FAMILY:
         hw = fr.nominal_hw(name)
@@ -224,11 +219,11 @@ def new_conv_cases():
         for op in p.ops:
             o = {k: int(op[k]) for k in op.dtype.names}
             key = (o["korder"], o["Cin"], o["Cout"], o["KH"], o["stride"])
-            if o["type"] != 0 or o["korder"] == 11 or key in have or key in seen:      # (korder 11, the fused stride-2 + twin op, is w6's: tests/test_detector_pinned_gpu.py)
+            if o["type"] != 0 or o["korder"] == WL.WS_S2_TWIN or key in have or key in seen:      # (WS_S2_TWIN, the fused stride-2 + twin op, is w6's: tests/test_detector_pinned_gpu.py)
                 continue
             seen.add(key)
-            H, W = {0: (12, 20), 1: (12, 20), 3: (12, 20), 10: (12, 20), 7: (16, 16)}.get(o["korder"], (16, 64))
-            act = o["act"] | KORDER_BIT[o["korder"]]
+            H, W = {WL.TAP_MAJOR: (12, 20), WL.LINE_MAJOR: (12, 20), WL.PANEL_1X1: (12, 20), WL.PANEL_1X1_N64: (12, 20), WL.P8: (16, 16)}.get(o["korder"], (16, 64))
+            act = o["act"] | act_bits(o["korder"])
             cases.append((1, H, W, o["Cin"], o["Cout"], o["KH"], o["stride"], act, o["in_ld"], o["in_coff"], o["out_ld"], o["out_coff"], o["out_f32"]))
     return cases
 
@@ -236,7 +231,7 @@ def new_conv_cases():
 NEW_CONV_CASES = new_conv_cases()
 
 
-@pytest.mark.parametrize("case", NEW_CONV_CASES, ids=["k%d-%dto%d-%dx%ds%d" % (_korder_of(c[7]), c[3], c[4], c[5], c[5], c[6]) for c in NEW_CONV_CASES])
+@pytest.mark.parametrize("case", NEW_CONV_CASES, ids=["k%d-%dto%d-%dx%ds%d" % (layout_of(c[7])[0], c[3], c[4], c[5], c[5], c[6]) for c in NEW_CONV_CASES])
 def test_new_conv_shapes_match_torch_fp32(L, case):
     from tests.test_detector_gpu import test_conv_layer_matches_torch_fp32
     test_conv_layer_matches_torch_fp32(L, case)

@@ -15,10 +15,10 @@ pytestmark = pytest.mark.skipif(not __import__("os").path.exists(cs._CLANG), rea
 
 # B, H, W, Cin, Cout, act, korder, slices
 DENSE_CASES = [
-    (3, 20, 20, 64, 64, 1, 1, {}),                                                    # 1200 pixels: tiles straddle image boundaries, ragged last tile
-    (2, 7, 20, 128, 128, 1, 2, {}),                                                   # 280 pixels: one tile spans two image boundaries; two chunk pairs, 128-row panels
-    (1, 13, 40, 192, 64, 2, 1, {"in_ld": 256, "in_coff": 64, "out_ld": 192, "out_coff": 64}),   # three passes of the chunk-pair loop, slices, LeakyReLU
-    (2, 20, 20, 64, 128, 1, 9, {}),                                                   # 64-row panels on a 128-channel layer
+    (3, 20, 20, 64, 64, 1, t.WL.LINE_MAJOR, {}),                                      # 1200 pixels: tiles straddle image boundaries, ragged last tile
+    (2, 7, 20, 128, 128, 1, t.WL.PATCH, {}),                                          # 280 pixels: one tile spans two image boundaries; two chunk pairs, 128-row panels
+    (1, 13, 40, 192, 64, 2, t.WL.LINE_MAJOR, {"in_ld": 256, "in_coff": 64, "out_ld": 192, "out_coff": 64}),  # three passes of the chunk-pair loop, slices, LeakyReLU
+    (2, 20, 20, 64, 128, 1, t.WL.PATCH_N64, {}),                                      # 64-row panels on a 128-channel layer
 ]
 
 
@@ -49,10 +49,10 @@ def test_dense_strip_border_taps_are_selected_not_multiplied_on_the_host():
     rng = np.random.default_rng(4)
     Wt = (rng.normal(0, 1, (Cout, Cin, 3, 3)) / np.sqrt(Cin * 9)).astype(np.float32)
     bias = rng.normal(0, 0.5, Cout).astype(np.float32)
-    wp = t.pack_w(Wt, Cin, Cout, 1)
+    wp = t.pack_w(Wt, Cin, Cout, t.WL.LINE_MAJOR)
     out = np.full((B, H, W, Cout), 7.0, np.float16)
     L = cs.lib()
-    rc = L.cs_conv(x.ctypes.data, Cin, 0, B, H, W, Cin, wp.ctypes.data, bias.ctypes.data, out.ctypes.data, Cout, 0, 0, Cout, Cout, 3, 3, 1, 1, 0, 1, 0, 0, 1)
+    rc = L.cs_conv(x.ctypes.data, Cin, 0, B, H, W, Cin, wp.ctypes.data, bias.ctypes.data, out.ctypes.data, Cout, 0, 0, Cout, Cout, 3, 3, 1, 1, 0, t.WL.LINE_MAJOR, 0, 0, 1)
     assert rc == 0, L.cs_last_error().decode()
     assert L.cs_last_kernel().decode().startswith("patch_strip<20,")
     ref = torch.nn.functional.conv2d(torch.from_numpy(x.astype(np.float32)).permute(0, 3, 1, 2), torch.from_numpy(Wt.astype(np.float16).astype(np.float32)),

@@ -7,11 +7,10 @@ import torch
 import torch.nn.functional as F
 
 from tests.test_strip_dense_convsim import DENSE_CASES, poisoned_input
-from tests.test_detector_gpu import pack_w
+from tests.util import pack_w
+from yolov7_tracker_amd.detector.layout import act_bits
 
 pytestmark = pytest.mark.gpu
-
-FORCE, KORDER_BIT = 512, {1: 256, 2: 1024, 9: 131072}      # `act` bits of y7t_conv2d_nhwc_f16: force the patch kernel on a small problem; the weight order
 
 
 @pytest.fixture(scope="module")
@@ -33,7 +32,7 @@ def run_layer(L, x, Wt, bias, act, korder, in_coff=0, out_ld=None, out_coff=0):
     out = torch.full((B, H, W, out_ld), 7.0, dtype=torch.float16, device="cuda")
     zeros = torch.zeros(128, dtype=torch.float16, device="cuda")
     _lib.check(L.y7t_conv2d_nhwc_f16(_lib.ptr(xd), in_ld, in_coff, B, H, W, Cin, _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(out), out_ld, out_coff, 0, Cout, cout_pad,
-                                     3, 3, 1, 1, act | FORCE | KORDER_BIT[korder], _lib.ptr(zeros), _lib.stream_ptr()))
+                                     3, 3, 1, 1, act | act_bits(korder, force_patch=True), _lib.ptr(zeros), _lib.stream_ptr()))
     torch.cuda.synchronize()
     return out.float().cpu().numpy(), L.y7t_last_kernel().decode()
 

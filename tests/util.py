@@ -12,6 +12,28 @@ ORACLE_ONLY_CASES = DEEPSORT_CASES
 TLWH_RTOL, TLWH_ATOL = 1e-6, 1e-5
 
 
+def pack_w(W, cin_pad, cout_pad, layout=0):
+    """(Cout, Cin, k, k) fp32 weights of a single-layer test -> the [cout_pad][K_pad] fp16 block in weight layout `layout`, by the packers of detector/weights.py"""
+    from yolov7_tracker_amd.detector import weights
+    from yolov7_tracker_amd.detector.layout import WeightLayout as WL
+    cout, cin, k, _ = W.shape
+    K = k * k * cin_pad
+    Wt = np.zeros((cout, k, k, cin_pad), np.float32)
+    Wt[..., :cin] = W.transpose(0, 2, 3, 1)
+    if layout == WL.LINE_MAJOR:      # (kh, 64-channel chunk, kw) K order
+        Wt = Wt.reshape(cout, k, k, cin_pad // 64, 64).transpose(0, 1, 3, 2, 4)
+    blk = np.zeros((cout_pad, (K + 63) // 64 * 64), np.float16)
+    blk[:cout, :K] = Wt.reshape(cout, -1).astype(np.float16)
+    return weights.PACKERS[WL(layout)](blk, cin_pad)
+
+
+def layer_cout_pad(cout, layout):
+    """Cout_pad of a single-layer test: whole 256-, 128- or 64-row tiles, whichever the layout's kernel works on"""
+    from yolov7_tracker_amd.detector.layout import WeightLayout as WL
+    rows = 256 if layout == WL.P8 else 128 if layout in (WL.PATCH_S2, WL.WS128, WL.WS_S2) else 64
+    return (cout + rows - 1) // rows * rows
+
+
 def load_tracker_case(name):
     g = np.load(os.path.join(GOLDEN, "tracker_%s.npz" % name))
     counts = g["det_counts"]

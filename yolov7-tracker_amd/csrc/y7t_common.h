@@ -54,6 +54,14 @@ static inline int y7t_once_per_device(Y7TOncePerDevice& o, F&& setup) {
     o.done.fetch_or(bit, std::memory_order_release);
     return 0;
 }
+// hipFuncAttributeMaxDynamicSharedMemorySize = bytes for each of `kernels`, at the first call on a device (the launchers' instances that ask for more than 64 KiB of LDS)
+template <class... K>
+static inline int y7t_set_max_lds(Y7TOncePerDevice& once, int bytes, K... kernels) {
+    return y7t_once_per_device(once, [&]() -> int {
+        for (const void* k : {(const void*)kernels...}) Y7T_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        return 0;
+    });
+}
 // compute units of the current device (cached per device)
 static inline int y7t_num_cus() {
     static std::atomic<int> ncu[64];

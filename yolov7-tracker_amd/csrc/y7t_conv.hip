@@ -120,10 +120,10 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 || BM * BN >= 256 * 256 ? 1 
                 if (kh >= klo && kh <= khi) vmask[r] |= colbits << (kh * p.KW);
         }
     }
-    // korder 3 (1x1 layers, BK = 32; detector/weights.py::panel_pack_linear): the BN x 32 weight panel of every K-step is stored as one
+    // Y7T_WL_PANEL_1X1 (1x1 layers, BK = 32; detector/weights.py::panel_pack_linear): the BN x 32 weight panel of every K-step is stored as one
     // contiguous block that already is the swizzled LDS image -> a wave's DMA reads 1 KiB of consecutive bytes (8 full cache lines)
     // instead of 16 half lines from 16 weight rows (17 vs 46 clocks in the vector L1, scripts/ubench/dma_patterns.hip)
-    const bool wpanel = (p.korder == 3);
+    const bool wpanel = (p.korder == Y7T_WL_PANEL_1X1);
     int woff[RN];
 #pragma unroll
     for (int r = 0; r < RN; ++r)
@@ -162,20 +162,20 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 || BM * BN >= 256 * 256 ? 1 
                                                      wpanel ? (kt0 + kt) * (BN * ROWB) : (kt0 + kt) * BK * 2, 0, 0);
         }
     };
-    // K order.  Default: k = tap*Cin + ci (taps outermost).  korder = 1 (3x3, Cin % 64 == 0, weights packed to match):
+    // K order.  Default: k = tap*Cin + ci (taps outermost).  Y7T_WL_LINE_MAJOR (3x3, Cin % 64 == 0, weights packed to match):
     // (kh, 64-channel chunk, kw) -- the three kw taps of one chunk are consecutive K-steps and touch the same input lines
     // shifted by one pixel, so they hit in L1/L2 instead of coming back from the Infinity Cache a dozen steps later.
     const int nchunk = p.Cin >> 6;
     int o_kw = 0, o_c = 0, o_kh = 0, o_sub = 0;
     if (KM == 1) { tap = 0; ci = kt0 * BK; }
-    if (KM != 1 && UT && p.korder == 1) {   // decode the (kh, chunk, kw) odometer at this split's first K-step
+    if (KM != 1 && UT && p.korder == Y7T_WL_LINE_MAJOR) {   // decode the (kh, chunk, kw) odometer at this split's first K-step
         const int g = (kt0 * BK) >> 6;
         o_kw = g % p.KW; o_c = (g / p.KW) % nchunk; o_kh = g / (p.KW * nchunk); o_sub = ((kt0 * BK) & 63) / BK;
         tap = o_kh * p.KW + o_kw; ci = (o_c << 6) + o_sub * BK;
     }
     auto advance_k = [&]() {
         if (KM == 1) { ci += BK; return; }
-        if (UT && p.korder == 1) {
+        if (UT && p.korder == Y7T_WL_LINE_MAJOR) {
             if (BK < 64 && ++o_sub < 64 / BK) { ci += BK; return; }
             o_sub = 0;
             if (++o_kw == p.KW) { o_kw = 0; if (++o_c == nchunk) { o_c = 0; ++o_kh; } }
@@ -495,10 +495,7 @@ static int launch_conv_ut(const Y7TConvArgs& a, hipStream_t s) {
     constexpr unsigned lds_stage = NST * (BM + BN) * BK * 2, lds_epi = EPI == 1 ? BM * (BN + 1) * 4 : BM * (BN * 2 + 16);
     constexpr unsigned lds = (lds_stage > lds_epi ? lds_stage : lds_epi) + BN * 4;   // + the bias corner
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv_igemm<BM, BN, BK, NST, UT, KM, EPI, DUAL, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, (int)lds, k_conv_igemm<BM, BN, BK, NST, UT, KM, EPI, DUAL, NW>)) return e_;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.Cout_pad / BN, tiles = tiles_m * tiles_n;
     Y7TConvArgs b = a;
     const int nk = a.K_pad / BK;
@@ -568,23 +565,28 @@ int y7t_conv_launch(const Y7TConvArgs& a, hipStream_t s) {
     return conv_dispatch(b, s);
 }
 
-int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s);   // y7t_conv_patch.hip
-int y7t_conv_patch_s2_launch(const Y7TConvArgs& a, hipStream_t s);   // y7t_conv_patch_s2.hip (korder 4: opt-in experiment, Y7T_CONV_PATCH_S2=1)
-int y7t_conv_ws_launch(const Y7TConvArgs& a, hipStream_t s);         // y7t_conv_ws.hip (korder 5: 64 -> 64 3x3 layers, weights stationary in registers)
-int y7t_conv_ws128_launch(const Y7TConvArgs& a, hipStream_t s);      // y7t_conv_ws128.hip (korder 6: 128 -> 128 k 3x3 layers, the same idea on the tile counter)
-int y7t_conv_ws_s2_launch(const Y7TConvArgs& a, hipStream_t s);      // y7t_conv_ws_s2.hip (korder 8: the 64 -> 128 3x3 / stride 2 layer, weights stationary in registers)
-int y7t_conv_p8_launch(const Y7TConvArgs& a, hipStream_t s);         // y7t_conv_p8.hip (korder 7: 1x1 layers with Cout % 256 == 0 on the 256 x 256 x 64 ping-pong pipeline)
+// the launchers of the layouts that one kernel file reads (0 done, < 0 error; y7t_conv_patch_try also 0 = not taken, and reads the two row-major layouts too)
+int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s);         // y7t_conv_patch.hip: Y7T_WL_PATCH (_N64)
+int y7t_conv_patch_s2_launch(const Y7TConvArgs& a, hipStream_t s);   // y7t_conv_patch_s2.hip: Y7T_WL_PATCH_S2 (opt-in experiment, Y7T_CONV_PATCH_S2=1)
+int y7t_conv_ws_launch(const Y7TConvArgs& a, hipStream_t s);         // y7t_conv_ws.hip: Y7T_WL_WS64
+int y7t_conv_ws128_launch(const Y7TConvArgs& a, hipStream_t s);      // y7t_conv_ws128.hip: Y7T_WL_WS128
+int y7t_conv_ws_s2_launch(const Y7TConvArgs& a, hipStream_t s);      // y7t_conv_ws_s2.hip: Y7T_WL_WS_S2, Y7T_WL_WS_S2_TWIN
+int y7t_conv_p8_launch(const Y7TConvArgs& a, hipStream_t s);         // y7t_conv_p8.hip: Y7T_WL_P8
 
 static int conv_dispatch(const Y7TConvArgs& a0, hipStream_t s) {
     Y7TConvArgs a = a0;
-    if (a.korder == 9) { a.korder = 2; a.panel64 = 1; }          // the patch kernel's panel order with 64-row panels
-    if (a.korder == 10) { a.korder = 3; a.panel64 = 1; }         // the 1x1 panel order with 64-row panels (small maps: twice the workgroups)
-    if (a.korder == 8 || a.korder == 11) return y7t_conv_ws_s2_launch(a, s);      // stride-2 register-fragment order (11: with the twin 1x1 behind it): only that kernel reads it
-    if (a.korder == 7) return y7t_conv_p8_launch(a, s);         // 256 x 64 weight panels: only that kernel reads them (plain and upsample-on-read)
+    switch (a.korder) {
+    case Y7T_WL_WS_S2: case Y7T_WL_WS_S2_TWIN: return y7t_conv_ws_s2_launch(a, s);
+    case Y7T_WL_P8: return y7t_conv_p8_launch(a, s);             // (plain and upsample-on-read)
+    case Y7T_WL_PATCH_N64: a.korder = Y7T_WL_PATCH; a.panel64 = 1; break;
+    case Y7T_WL_PANEL_1X1_N64: a.korder = Y7T_WL_PANEL_1X1; a.panel64 = 1; break;      // (small maps: twice the workgroups)
+    case Y7T_WL_TAP_MAJOR: case Y7T_WL_LINE_MAJOR: case Y7T_WL_PATCH: case Y7T_WL_PANEL_1X1: case Y7T_WL_PATCH_S2: case Y7T_WL_WS64: case Y7T_WL_WS128: break;
+    default: y7t_set_error("conv: unknown weight layout %d", a.korder); return Y7T_E_ARG;
+    }
     if (a.epi || a.up_C > 0) {   // fused Detect epilogue / upsample-on-read loader: instances of the 1x1 fast path only
-        if (a.panel64) { y7t_set_error("conv: korder 10 (64-row 1x1 panels) is for plain 1x1 layers, not Detect-decode / upsample-on-read"); return Y7T_E_ARG; }
+        if (a.panel64) { y7t_set_error("conv: Y7T_WL_PANEL_1X1_N64 (korder 10, 64-row 1x1 panels) is for plain 1x1 layers, not Detect-decode / upsample-on-read"); return Y7T_E_ARG; }
         const bool fast = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.Cin % 64 == 0 && a.in_bytes <= 0xFF000000u - (1u << 24) &&
-                          (a.korder == 3 || a.korder == 0);
+                          (a.korder == Y7T_WL_PANEL_1X1 || a.korder == Y7T_WL_TAP_MAJOR);
         if (!fast) { y7t_set_error("conv: Detect-decode / upsample-on-read need a 1x1 stride-1 layer with Cin %% 64 == 0"); return Y7T_E_ARG; }
         if (a.epi) {
             if (a.Cout_pad != 64 || a.up_C > 0) { y7t_set_error("conv: fused Detect decode needs na * (5 + nc) <= 64 output channels (got %d)", a.Cout); return Y7T_E_ARG; }
@@ -602,14 +604,16 @@ static int conv_dispatch(const Y7TConvArgs& a0, hipStream_t s) {
         }
         return a.Cout_pad % 128 == 0 ? launch_conv_ut<128, 128, 32, 2, true, 1, 0, true>(a, s) : launch_conv_ut<128, 64, 32, 2, true, 1, 0, true>(a, s);
     }
-    if (a.korder == 4) return y7t_conv_patch_s2_launch(a, s);   // stride-2 LDS-patch kernel's panels: only that kernel reads them
-    if (a.korder == 5) return y7t_conv_ws_launch(a, s);         // register-fragment order: only the weights-stationary kernel reads it
-    if (a.korder == 6) return y7t_conv_ws128_launch(a, s);      // ... and its 128-channel sibling
-    if (a.korder == 3) {   // panel-packed 1x1 weights: only the 32-deep generic kernel reads that layout
-        if (a.KH != 1 || a.KW != 1 || a.Cin % 32) { y7t_set_error("conv: korder 3 (panel-packed weights) needs a 1x1 layer with Cin %% 32 == 0"); return Y7T_E_ARG; }
+    switch (a.korder) {      // a layout that one kernel reads: there is no other kernel to fall back to
+    case Y7T_WL_PATCH_S2: return y7t_conv_patch_s2_launch(a, s);
+    case Y7T_WL_WS64: return y7t_conv_ws_launch(a, s);
+    case Y7T_WL_WS128: return y7t_conv_ws128_launch(a, s);
+    case Y7T_WL_PANEL_1X1:      // only the 32-deep generic kernel reads these panels
+        if (a.KH != 1 || a.KW != 1 || a.Cin % 32) { y7t_set_error("conv: Y7T_WL_PANEL_1X1 (korder 3, panel-packed weights) needs a 1x1 layer with Cin %% 32 == 0"); return Y7T_E_ARG; }
         return a.Cout_pad % 128 == 0 && !a.panel64 ? launch_conv<128, 128, 32, 2>(a, s) : launch_conv<128, 64, 32, 2>(a, s);
+    default: break;      // Y7T_WL_TAP_MAJOR, Y7T_WL_LINE_MAJOR, Y7T_WL_PATCH: the patch kernel where it takes the layer, else the generic kernel (a new layout needs a case here)
     }
-    if ((conv_variant() == 0 && !a.no_patch) || a.korder == 2) {   // 3x3 / stride 1 on a large map: LDS-resident patch kernel
+    if ((conv_variant() == 0 && !a.no_patch) || a.korder == Y7T_WL_PATCH) {   // 3x3 / stride 1 on a large map: LDS-resident patch kernel
         const int rc = y7t_conv_patch_try(a, s);
         if (rc) return rc < 0 ? rc : 0;
     }

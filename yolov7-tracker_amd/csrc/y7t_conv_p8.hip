@@ -23,7 +23,7 @@
 //   * bias: fetched to LDS by the first DMA of the kernel, the accumulators START at the bias (the epilogue adds nothing); epilogue: activation, fp16, v_permlane32_swap
 //     into 16-byte pieces, each wave transposes ITS 128 pixels x 64 channels through its own 16 KiB of the (now idle) ring and stores full 128-byte lines.
 //   * upsample-on-read (DUAL): K-tiles whose channels lie in [up_c0, up_c0 + up_C) fetch pixel (y, x) from the half-resolution tensor `in2` at (y >> 1, x >> 1).
-// Weights: korder 7 (detector/weights.py::panel_pack_p8): per (channel tile, K-tile) one contiguous 32 KiB block that IS the swizzled LDS image of C0 then C1;
+// Weights: Y7T_WL_P8 (detector/weights.py::panel_pack_p8): per (channel tile, K-tile) one contiguous 32 KiB block that IS the swizzled LDS image of C0 then C1;
 // LDS row r of half h holds channel n0 + (r / 32) * 64 + h * 32 + r % 32, so a wave's 64 channels are CONTIGUOUS in the output (one 128-byte line per pixel).
 // Pixels: LDS row r of half h holds pixel m0 + (r / 64) * 128 + h * 64 + r % 64 (a group's 128 pixels are contiguous).
 // One workgroup per output tile and per CU (129 KiB of LDS): the hardware dispatcher balances the tiles over the CUs the tracker / NMS streams leave free (a statically
@@ -504,7 +504,7 @@ __global__ void __launch_bounds__(512, 2) k_conv1x1_p8p(const Y7TConvArgs p) {
 
 }   // namespace
 
-// korder 7 layers only (detector/graph.py::p8_eligible mirrors the conditions)
+// Y7T_WL_P8 layers only (detector/graph.py::p8_eligible mirrors the conditions)
 int y7t_conv_p8_launch(const Y7TConvArgs& a, hipStream_t s) {
     using C = P8;
     bool ok = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.Cin % C::BK == 0 && a.K_pad == a.Cin && a.Cout_pad % C::BN == 0 && !a.out_f32 && !a.epi &&
@@ -512,18 +512,14 @@ int y7t_conv_p8_launch(const Y7TConvArgs& a, hipStream_t s) {
     if (a.up_C > 0) ok = ok && a.up_c0 % C::BK == 0 && a.up_C % C::BK == 0 && a.up_c0 + a.up_C <= a.Cin && !(a.H & 1) && !(a.W & 1) && !(a.ldin2 & 7) && !(a.cin2_off & 7) &&
                          a.in2_bytes <= C::OOB - (1u << 24);
     if (!ok) {
-        y7t_set_error("conv: weights are in the 256 x 64 panel order (korder 7) but the layer is not a 1x1 / stride 1 convolution with Cin %% 64 == 0, Cout_pad %% 256 == 0 "
+        y7t_set_error("conv: weights are in the 256 x 64 panel order, Y7T_WL_P8 (korder 7), but the layer is not a 1x1 / stride 1 convolution with Cin %% 64 == 0, Cout_pad %% 256 == 0 "
                       "and an aligned fp16 output (Cin=%d Cout=%d Cout_pad=%d ldout=%d cout_off=%d up=[%d,%d))", a.Cin, a.Cout, a.Cout_pad, a.ldout, a.cout_off, a.up_c0,
                       a.up_c0 + a.up_C);
         return Y7T_E_ARG;
     }
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-#define P8_ATTR(ACT, DUAL) Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv1x1_p8<ACT, DUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        P8_ATTR(Y7T_ACT_NONE, false) P8_ATTR(Y7T_ACT_SILU, false) P8_ATTR(Y7T_ACT_LEAKY, false) P8_ATTR(Y7T_ACT_NONE, true) P8_ATTR(Y7T_ACT_SILU, true) P8_ATTR(Y7T_ACT_LEAKY, true)
-#undef P8_ATTR
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, C::LDS, k_conv1x1_p8<Y7T_ACT_NONE, false>, k_conv1x1_p8<Y7T_ACT_SILU, false>, k_conv1x1_p8<Y7T_ACT_LEAKY, false>,
+                                 k_conv1x1_p8<Y7T_ACT_NONE, true>, k_conv1x1_p8<Y7T_ACT_SILU, true>, k_conv1x1_p8<Y7T_ACT_LEAKY, true>)) return e_;
     const int grid = ((a.M + C::BM - 1) / C::BM) * (a.Cout_pad / C::BN);
     const bool dual = a.up_C > 0;
     // the persistent form (k_conv1x1_p8p) where a workgroup gets more than one tile and the K-tiles of a tile are an even number (the ring's parity)
@@ -532,13 +528,10 @@ int y7t_conv_p8_launch(const Y7TConvArgs& a, hipStream_t s) {
     // (at least two tiles per workgroup on average: with 500 tiles on 256 workgroups -- the 20 x 20 layers at 80 frames -- the persistent form measured 0-3 % behind, r6ax)
     if (persist && !a.ablate && ((a.Cin / C::BK) & 1) == 0 && gp_ > 0 && grid >= 2 * gp_) {
         static Y7TOncePerDevice attrp;
-        if (int e_ = y7t_once_per_device(attrp, [&]() -> int {
-#define P8P_ATTR(ACT, DUAL) Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv1x1_p8p<ACT, DUAL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS + 16)); \
-                            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv1x1_p8p<ACT, DUAL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS + 16));
-            P8P_ATTR(Y7T_ACT_NONE, false) P8P_ATTR(Y7T_ACT_SILU, false) P8P_ATTR(Y7T_ACT_LEAKY, false) P8P_ATTR(Y7T_ACT_NONE, true) P8P_ATTR(Y7T_ACT_SILU, true) P8P_ATTR(Y7T_ACT_LEAKY, true)
-#undef P8P_ATTR
-            return 0;
-        })) return e_;
+#define P8P_BOTH(ACT, DUAL) k_conv1x1_p8p<ACT, DUAL, false>, k_conv1x1_p8p<ACT, DUAL, true>
+        if (int e_ = y7t_set_max_lds(attrp, C::LDS + 16, P8P_BOTH(Y7T_ACT_NONE, false), P8P_BOTH(Y7T_ACT_SILU, false), P8P_BOTH(Y7T_ACT_LEAKY, false),
+                                     P8P_BOTH(Y7T_ACT_NONE, true), P8P_BOTH(Y7T_ACT_SILU, true), P8P_BOTH(Y7T_ACT_LEAKY, true))) return e_;
+#undef P8P_BOTH
         static const int dyn_env = y7t_switch("Y7T_CONV_WS_DYN", 1);      // (the persistent kernels' product switch: =0 the static column)
         const bool dyn = a.tile_ctr && dyn_env && n_tiles_n <= Y7T_TILE_CTR_DONE;
 #define P8P_GO(ACT) \

@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
             if (i < C::NWX) {
                 const int byte = (wave * C::NWX + i) * 1024 + lane * 16;
                 const int row = byte >> 6, slot = (byte >> 4) & 3;
-                if (p.korder == 2) v = (unsigned)(tile_n * (p.K_pad >> 5) * C::W_BYTES + byte);   // panel order: memory image == LDS image
+                if (p.korder == Y7T_WL_PATCH) v = (unsigned)(tile_n * (p.K_pad >> 5) * C::W_BYTES + byte);   // panel order: memory image == LDS image
                 else v = (unsigned)(((n0 + row) * p.K_pad + ((slot ^ ((row >> 2) & 3)) << 3)) * 2);
             }
         } else if (i < C::NPX) {
@@ -167,13 +167,13 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch(const Y7TConvArgs p) {
     const int nc32 = p.Cin >> 5;
     // byte offset (in a weight row) of K-step (chunk c, tap kh,kw) = kh * s_kh + kw * s_kw + chunk part; the chunk part of an even
     // chunk c0 is `cbase`, of c0 + 1 it is cbase + 64 in both packings, and a chunk pair advances it by s_pair
-    // korder 2 (panel order, detector/weights.py): the BN x 32 panel of K-step (c, tap) is one contiguous, pre-swizzled W_BYTES block
+    // Y7T_WL_PATCH (panel order, detector/weights.py): the BN x 32 panel of K-step (c, tap) is one contiguous, pre-swizzled W_BYTES block
     // at [tile_n][c * 9 + tap] -- 8 full cache lines per DMA instead of 16 half lines from 16 different weight rows, which the
     // vector L1 serves almost 3x faster (scripts/ubench/dma_patterns.hip: 17 vs 46 clocks per wave-DMA)
-    const int s_kh = p.korder == 2 ? 3 * C::W_BYTES : p.korder ? (p.Cin >> 6) * 3 * 128 : 3 * p.Cin * 2;
-    const int s_kw = p.korder == 2 ? C::W_BYTES : p.korder ? 128 : p.Cin * 2;
-    const int s_odd = p.korder == 2 ? 9 * C::W_BYTES : 64;                  // odd chunk of a pair relative to the even one
-    const int s_pair = p.korder == 2 ? 18 * C::W_BYTES : p.korder ? 3 * 128 : 128;
+    const int s_kh = p.korder == Y7T_WL_PATCH ? 3 * C::W_BYTES : p.korder ? (p.Cin >> 6) * 3 * 128 : 3 * p.Cin * 2;
+    const int s_kw = p.korder == Y7T_WL_PATCH ? C::W_BYTES : p.korder ? 128 : p.Cin * 2;
+    const int s_odd = p.korder == Y7T_WL_PATCH ? 9 * C::W_BYTES : 64;                  // odd chunk of a pair relative to the even one
+    const int s_pair = p.korder == Y7T_WL_PATCH ? 18 * C::W_BYTES : p.korder ? 3 * 128 : 128;
     int cbase = 0;
     // FLAT: the DMA destinations are formed where they are used (wave part + constant, one s_add into M0).  Left alone the compiler keeps every
     // one of them -- ~45 values -- in an SGPR of its own across the K loop, and those SGPRs are needed for the border masks.
@@ -532,7 +532,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch_mt(const Y7TConvArgs p
         for (int i = 0; i < C::NWX; ++i) {
             const int byte = (wave * C::NWX + i) * 1024 + lane * 16;
             const int row = byte >> 6, slot = (byte >> 4) & 3;
-            woff[i] = p.korder == 2 ? (unsigned)(tile_n * (p.K_pad >> 5) * C::W_BYTES + byte)
+            woff[i] = p.korder == Y7T_WL_PATCH ? (unsigned)(tile_n * (p.K_pad >> 5) * C::W_BYTES + byte)
                                     : (unsigned)(((n0 + row) * p.K_pad + ((slot ^ ((row >> 2) & 3)) << 3)) * 2);
         }
     } else {
@@ -545,10 +545,10 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_patch_mt(const Y7TConvArgs p
     const char* plane = smem + P_OFF + (wm * TM * RPT + (TW == 16 ? (l31 >> 4) : 0)) * RP + (TW == 16 ? (l31 & 15) : l31) * PIXB + hi32 * 16;
 
     const int nc32 = p.Cin >> 5, total = nt * nc32;     // chunks of this workgroup
-    const int s_kh = p.korder == 2 ? 3 * C::W_BYTES : p.korder ? (p.Cin >> 6) * 3 * 128 : 3 * p.Cin * 2;
-    const int s_kw = p.korder == 2 ? C::W_BYTES : p.korder ? 128 : p.Cin * 2;
+    const int s_kh = p.korder == Y7T_WL_PATCH ? 3 * C::W_BYTES : p.korder ? (p.Cin >> 6) * 3 * 128 : 3 * p.Cin * 2;
+    const int s_kw = p.korder == Y7T_WL_PATCH ? C::W_BYTES : p.korder ? 128 : p.Cin * 2;
     auto chunk_off = [&](int c) -> int {                // byte offset of chunk c (inside its tile) in a weight row / panel list
-        return p.korder == 2 ? c * 9 * C::W_BYTES : p.korder ? (c >> 1) * 3 * 128 + (c & 1) * 64 : c * 64;
+        return p.korder == Y7T_WL_PATCH ? c * 9 * C::W_BYTES : p.korder ? (c >> 1) * 3 * 128 + (c & 1) * 64 : c * 64;
     };
     auto issue_w = [&](int slot, int c_in_tile, int kh, int kw, bool real) {
         const int so = kh * s_kh + kw * s_kw + chunk_off(c_in_tile);
@@ -701,10 +701,7 @@ int launch_patch_mt(const Y7TConvArgs& a, hipStream_t s) {
     constexpr int lds = 3 * C0::W_BYTES + 2 * C0::PATCH_BYTES + 64 * 4;       // weight ring | patch A | patch B | biases
     static_assert(lds <= 81920, "two workgroups per CU");
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_patch_mt<TW, TH, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, lds, k_conv3x3_patch_mt<TW, TH, MT>)) return e_;
     const int ptiles = a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
     hipLaunchKernelGGL((k_conv3x3_patch_mt<TW, TH, MT>), dim3(((ptiles + MT - 1) / MT) * (a.Cout_pad / 64)), dim3(256), lds, s, a);
     Y7T_LAUNCH_CHECK();
@@ -716,10 +713,7 @@ template <int TW, int TH, int BN, int ABL = 0>
 int launch_patch(const Y7TConvArgs& a, hipStream_t s) {
     using C = PatchCfg<TW, TH, BN>;
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_patch<TW, TH, BN, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, C::LDS, k_conv3x3_patch<TW, TH, BN, ABL>)) return e_;
     const int ptiles = C::FLAT ? (a.B * a.H * a.W + 255) / 256 : a.B * ((a.H + TH - 1) / TH) * ((a.W + (C::FLAT ? 1 : TW) - 1) / (C::FLAT ? 1 : TW));
     const int tiles = ptiles * (a.Cout_pad / BN);
     hipLaunchKernelGGL((k_conv3x3_patch<TW, TH, BN, ABL>), dim3(tiles), dim3(256), C::LDS, s, a);
@@ -737,8 +731,8 @@ int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s) {
     if (mode < 0) mode = y7t_exp_switch("Y7T_CONV_PATCH", 1);
     const bool eligible = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 64 == 0 && !a.out_f32 && !(a.Cout & 7) && !(a.ldout & 7) &&
                           !(a.cout_off & 7) && a.Ho == a.H && a.Wo == a.W && a.in_bytes <= kOOB - (1u << 24) && a.w_bytes <= kOOB - (1u << 24);
-    if (a.korder == 2 && (!eligible || !mode)) {   // panel-packed weights only make sense to this kernel
-        y7t_set_error("conv: weights are in panel order (korder 2) but the layer cannot run on the patch kernel");
+    if (a.korder == Y7T_WL_PATCH && (!eligible || !mode)) {   // panel-packed weights only make sense to this kernel
+        y7t_set_error("conv: weights are in panel order, Y7T_WL_PATCH (korder 2), but the layer cannot run on the patch kernel");
         return Y7T_E_ARG;
     }
     if (!mode || !eligible) return 0;
@@ -752,7 +746,7 @@ int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s) {
     const bool wide = a.Cout_pad % 128 == 0 && !a.panel64;
     const double eflat = (a.W == 40 || a.W == 20) ? 1.0 : 0.0;   // dense strip (instantiated for W = 20, 40): every position is a real pixel
     // too few workgroups for 256 CUs (batch-1 latency mode): the generic kernel with split-K fills the chip better
-    if (!a.force_patch && a.korder != 2 && (long long)a.B * a.H * a.W * (a.Cout_pad / (wide ? 128 : 64)) < 256ll * 256) return 0;
+    if (!a.force_patch && a.korder != Y7T_WL_PATCH && (long long)a.B * a.H * a.W * (a.Cout_pad / (wide ? 128 : 64)) < 256ll * 256) return 0;
     const int abl = Y7T_ABLATE ? a.ablate : 0;      // (ABL = 512, the step's DMAs behind its MFMAs, was measured in round 3: 15.98 vs 16.02 ms for the list -- not instantiated any more)
     if (eflat > (use16 ? e16 : e32) && eflat >= 0.8 && (!abl || abl == 2048)) {
         int rcf;
@@ -766,7 +760,7 @@ int y7t_conv_patch_try(const Y7TConvArgs& a, hipStream_t s) {
         else rcf = wide ? launch_patch<0, 20, 128>(a, s) : launch_patch<0, 20, 64>(a, s);
         return rcf ? rcf : 1;
     }
-    if (!a.force_patch && a.korder != 2 && (use16 ? e16 : e32) < 0.8) return 0;
+    if (!a.force_patch && a.korder != Y7T_WL_PATCH && (use16 ? e16 : e32) < 0.8) return 0;
     int rc;
 #if Y7T_ABLATE      // liby7t_ablate.so only: the burst-read form and the timing ablations ("wrong results") of the 16 x 16 x 128 kernel
     if (abl == 2048) {      // A/B: the burst-read form (rounds 1-3a) of the default kernels, correct results

@@ -1,6 +1,6 @@
 // y7t_conv_patch_s2.hip -- 3x3 / STRIDE 2 / pad 1 Conv(+folded BN)+bias+activation with an LDS-resident input patch whose columns are
 // de-interleaved by parity.  EXPERIMENT, opt-in (Y7T_CONV_PATCH_S2=1 in the environment when the plan is lowered: detector/graph.py gives the
-// eligible layers weights in this kernel's panel order, korder 4, and only korder 4 reaches this file).  The default launch list does not use it.
+// eligible layers weights in this kernel's panel order, Y7T_WL_PATCH_S2, and only that layout reaches this file).  The default launch list does not use it.
 //
 // Same math as k_conv_igemm (y7t_conv.hip; /root/reference/models/common.py:99-111 after utils/torch_utils.py:181-201); the layers it is for are the
 // eight down-sampling convolutions of yolov7-w6 (/root/reference/cfg/deploy/yolov7-w6.yaml:18,27,36,45,54 and the head's :118,131,144), 3.2 ms of the
@@ -15,7 +15,7 @@
 // for every pixel pitch that keeps 16-byte alignment; 48-byte pixels at unit stride are conflict-free: 3 x mod 16 is a bijection.)  All fragment
 // addresses are lane base + compile-time immediate, as in y7t_conv_patch.hip.
 // K order: 16-channel chunk outermost, tap innermost; one K-step = one tap of one chunk = ONE v_mfma_f32_32x32x16_f16 per 32 x 32 tile.
-// Weights: panel order (korder 4, detector/weights.py::panel_pack_s2): the BN x 16 panel of K-step (chunk, tap) is one contiguous BN * 32 byte
+// Weights: panel order (Y7T_WL_PATCH_S2, detector/weights.py::panel_pack_s2): the BN x 16 panel of K-step (chunk, tap) is one contiguous BN * 32 byte
 // block that already is the swizzled LDS image (16-byte half h of row r sits in slot h ^ ((r >> 3) & 1): two rows per 64 bytes, so the 16 lanes
 // of a ds_read_b128 service group cover 16 distinct 16-byte bank groups).
 // Pipeline: as y7t_conv_patch.hip -- waves 0/1 stream the weight panels through an NWS-slot ring, waves 2/3 the next chunk's patch in pieces
@@ -289,10 +289,7 @@ template <int BN, int NW, int ORD>
 int launch_s2_ord(const Y7TConvArgs& a, hipStream_t s) {
     using C = S2Cfg<BN, NW>;
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-        Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3s2_patch<BN, NW, ORD>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, C::LDS, k_conv3x3s2_patch<BN, NW, ORD>)) return e_;
     const int ptiles = a.B * ((a.Ho + C::TH - 1) / C::TH) * ((a.Wo + C::TW - 1) / C::TW);
     hipLaunchKernelGGL((k_conv3x3s2_patch<BN, NW, ORD>), dim3(ptiles * (a.Cout_pad / BN)), dim3(C::NT), C::LDS, s, a);
     Y7T_LAUNCH_CHECK();
@@ -310,19 +307,19 @@ int launch_s2(const Y7TConvArgs& a, hipStream_t s) {
 
 }   // namespace
 
-// panel width the weights of a korder-4 layer are packed for (detector/weights.py::panel_pack_s2 uses the same rule)
+// panel width the weights of a Y7T_WL_PATCH_S2 layer are packed for (detector/weights.py::panel_pack_s2 uses the same rule)
 static int s2_bn(int Cout_pad) {
     static int force128 = -1;
     if (force128 < 0) force128 = y7t_exp_switch("Y7T_CONV_PATCH_S2_BN", 0) == 128 ? 1 : 0;
     return (Cout_pad % 256 == 0 && !force128) ? 256 : 128;
 }
 
-// korder 4 layers only: 0 on success, < 0 on error (there is no fallback: the weights are in this kernel's panel order)
+// Y7T_WL_PATCH_S2 layers only: 0 on success, < 0 on error (there is no fallback: the weights are in this kernel's panel order)
 int y7t_conv_patch_s2_launch(const Y7TConvArgs& a, hipStream_t s) {
     const bool ok = a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.Cin % 64 == 0 && a.Cout_pad % 128 == 0 && !a.out_f32 && !(a.Cout & 7) &&
                     !(a.ldout & 7) && !(a.cout_off & 7) && !a.epi && a.up_C == 0 && a.in_bytes <= kOOB - (1u << 24) && a.w_bytes <= kOOB - (1u << 24);
     if (!ok) {
-        y7t_set_error("conv: weights are in the stride-2 patch kernel's panel order (korder 4) but the layer cannot run on it");
+        y7t_set_error("conv: weights are in the stride-2 patch kernel's panel order, Y7T_WL_PATCH_S2 (korder 4), but the layer cannot run on it");
         return Y7T_E_ARG;
     }
     return s2_bn(a.Cout_pad) == 256 ? launch_s2<256, 4>(a, s) : launch_s2<128, 4>(a, s);

@@ -20,7 +20,7 @@
 //   * epilogue straight from registers (bias + activation + permlane32_swap -> 16-byte NHWC stores), of the PREVIOUS tile, interleaved with this tile's
 //     MFMAs (two accumulator sets: with one wave per SIMD nothing else would cover it); maps of whole tiles only, so that every store is issued and
 //     `s_waitcnt vmcnt` can count them next to the pieces.
-// Weight layout (korder 5, detector/weights.py::pack_ws): fragment f = (tap * 4 + ks) * 2 + i is 1 KiB, lane l holds W[i*32 + l%32][tap][ks*16 + 8*(l/32) .. +7].
+// Weight layout (Y7T_WL_WS64, detector/weights.py::pack_ws): fragment f = (tap * 4 + ks) * 2 + i is 1 KiB, lane l holds W[i*32 + l%32][tap][ks*16 + 8*(l/32) .. +7].
 #include "y7t_common.h"
 #include "y7t_conv_common.h"
 #include <stdlib.h>
@@ -403,26 +403,19 @@ __global__ void __launch_bounds__(256, 1) k_conv3x3_c64_ws(const Y7TConvArgs p) 
 
 }   // namespace
 
-// korder 5 layers only (detector/graph.py::ws_eligible mirrors the conditions): 3x3 / 1 / 1, Cin == 64, Cout_pad == 64, fp16 output in 16-byte pieces
+// Y7T_WL_WS64 layers only (detector/graph.py::ws_eligible mirrors the conditions): 3x3 / 1 / 1, Cin == 64, Cout_pad == 64, fp16 output in 16-byte pieces
 int y7t_conv_ws_launch(const Y7TConvArgs& a, hipStream_t s) {
     using C = WsCfg;
     const bool ok = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 64 && a.Cout_pad == 64 && !a.out_f32 && !(a.Cout & 7) && !(a.ldout & 7) &&
                     !(a.cout_off & 7) && !(a.ldin & 7) && !(a.cin_off & 7) && a.Ho == a.H && a.Wo == a.W && a.in_bytes < 0x80000000u && a.Cout == 64 &&      // (32-bit byte offsets: tensors below 2 GiB, as y7t_conv_launch enforces)
                     a.H % C::TH == 0 && a.W % C::TW == 0;      // whole tiles only: the kernel counts its stores (s_waitcnt vmcnt), none may be predicated off
     if (!ok) {
-        y7t_set_error("conv: weights are in register-fragment order (korder 5) but the layer is not a 3x3 / stride 1 / 64 -> 64 convolution on a map of whole 16 x 16 tiles with an aligned fp16 output");
+        y7t_set_error("conv: weights are in register-fragment order, Y7T_WL_WS64 (korder 5), but the layer is not a 3x3 / stride 1 / 64 -> 64 convolution on a map of whole 16 x 16 tiles with an aligned fp16 output");
         return Y7T_E_ARG;
     }
     static Y7TOncePerDevice attr;
-    if (int e = y7t_once_per_device(attr, []() -> int {
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_SILU>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_LEAKY>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_NONE, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_SILU, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c64_ws<Y7T_ACT_LEAKY, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            return 0;
-        })) return e;
+    if (int e = y7t_set_max_lds(attr, C::LDS, k_conv3x3_c64_ws<Y7T_ACT_NONE>, k_conv3x3_c64_ws<Y7T_ACT_SILU>, k_conv3x3_c64_ws<Y7T_ACT_LEAKY>,
+                                k_conv3x3_c64_ws<Y7T_ACT_NONE, 0, true>, k_conv3x3_c64_ws<Y7T_ACT_SILU, 0, true>, k_conv3x3_c64_ws<Y7T_ACT_LEAKY, 0, true>)) return e;
     static int wgs_env = -2;      // Y7T_CONV_WS_WGS: workgroups of a launch (default: one persistent workgroup per compute unit -- 150 KiB of LDS each)
     if (wgs_env == -2) wgs_env = y7t_exp_switch("Y7T_CONV_WS_WGS", -1);
     const int ncu = wgs_env > 0 ? wgs_env : y7t_num_cus();

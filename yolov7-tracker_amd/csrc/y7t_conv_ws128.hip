@@ -16,7 +16,7 @@
 //     set and a second set fits: the previous tile's epilogue (32 values per lane) runs as a micro-program between this tile's MFMAs, as in the 64 -> 64 kernel;
 //   * the 6 x 18 pixel x 128-channel patch (272-byte pixels: 256 data + 16 pad; 5 KiB rows) sits in a three-buffer LDS ring (3 x 30 KiB), one barrier per tile;
 //   * one ds_read_b128 per MFMA (pixel fragments), three substeps ahead, every address = lane base + immediate.
-// Weight layout (korder 6, detector/weights.py::pack_ws128): per 128-channel output tile n, fragment f = (n * 72 + tap * 8 + ks) * 4 + q is 1 KiB, lane l holds
+// Weight layout (Y7T_WL_WS128, detector/weights.py::pack_ws128): per 128-channel output tile n, fragment f = (n * 72 + tap * 8 + ks) * 4 + q is 1 KiB, lane l holds
 // W[n*128 + q*32 + l%32][tap][ks*16 + 8*(l/32) .. +7].
 #include "y7t_common.h"
 #include "y7t_conv_common.h"
@@ -356,21 +356,14 @@ __global__ void __launch_bounds__(256, 1) k_conv3x3_c128_ws(const Y7TConvArgs p)
 
 }   // namespace
 
-// korder 6 layers only (detector/graph.py::ws128_eligible / ws128_s2_eligible mirror the conditions): 3x3 / pad 1, Cin == 128, Cout a multiple of 128; stride 1 on maps of
+// Y7T_WL_WS128 layers only (detector/graph.py::ws128_eligible / ws128_s2_eligible mirror the conditions): 3x3 / pad 1, Cin == 128, Cout a multiple of 128; stride 1 on maps of
 // whole 4 x 16 tiles, or stride 2 on an even map whose output is whole 2 x 16 tiles
 template <bool S2>
 static int ws128_go(const Y7TConvArgs& a, hipStream_t s) {
     using C = Ws128CfgT<S2>;
     static Y7TOncePerDevice attr;
-    if (int e = y7t_once_per_device(attr, []() -> int {
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_NONE, false, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_SILU, false, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_LEAKY, false, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_NONE, true, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_SILU, true, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_c128_ws<Y7T_ACT_LEAKY, true, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-            return 0;
-        })) return e;
+    if (int e = y7t_set_max_lds(attr, C::LDS, k_conv3x3_c128_ws<Y7T_ACT_NONE, false, S2>, k_conv3x3_c128_ws<Y7T_ACT_SILU, false, S2>, k_conv3x3_c128_ws<Y7T_ACT_LEAKY, false, S2>,
+                                k_conv3x3_c128_ws<Y7T_ACT_NONE, true, S2>, k_conv3x3_c128_ws<Y7T_ACT_SILU, true, S2>, k_conv3x3_c128_ws<Y7T_ACT_LEAKY, true, S2>)) return e;
     const int ncu = y7t_num_cus();      // one persistent workgroup per compute unit (90 / 135 KiB of LDS, 512 registers per lane)
     const int n_nt = a.Cout_pad / 128;
     const int ptiles = a.B * (a.Ho / C::TH) * (a.Wo / C::TW);
@@ -405,7 +398,7 @@ int y7t_conv_ws128_launch(const Y7TConvArgs& a, hipStream_t s) {
     if (common && a.stride == 1 && a.Ho == a.H && a.Wo == a.W && a.H % Ws128CfgT<false>::TH == 0 && a.W % Ws128CfgT<false>::TW == 0) return ws128_go<false>(a, s);
     if (common && a.stride == 2 && !(a.H & 1) && !(a.W & 1) && a.Ho * 2 == a.H && a.Wo * 2 == a.W && a.Ho % Ws128CfgT<true>::TH == 0 && a.Wo % Ws128CfgT<true>::TW == 0)
         return ws128_go<true>(a, s);
-    y7t_set_error("conv: weights are in the 128-channel register-fragment order (korder 6) but the layer is neither a 3x3 / stride 1 / 128 -> 128 k convolution on a map of whole "
+    y7t_set_error("conv: weights are in the 128-channel register-fragment order, Y7T_WL_WS128 (korder 6), but the layer is neither a 3x3 / stride 1 / 128 -> 128 k convolution on a map of whole "
                   "4 x 16 tiles nor a 3x3 / stride 2 one on an even map whose output is whole 2 x 16 tiles, with an aligned fp16 output");
     return Y7T_E_ARG;
 }

@@ -18,7 +18,7 @@
 //   * ONE barrier per tile in the loop (72 MFMAs per wave) + one for the output transposition: the four waves' 32-channel pieces of a pixel are gathered in LDS
 //     (64 pixels x 256 bytes) and leave as full 128-byte lines;
 //   * the bias enters as the C operand of a tile's first MFMA.
-// Compiler-scheduled (no micro-programmed epilogue: this layer is bound by HBM, not by issue).  Weight layout: korder 8 (detector/weights.py::pack_ws_s2): fragment
+// Compiler-scheduled (no micro-programmed epilogue: this layer is bound by HBM, not by issue).  Weight layout: Y7T_WL_WS_S2 (detector/weights.py::pack_ws_s2): fragment
 // f = (tap * 4 + ks) * 4 + q is 1 KiB, lane l holds W[q * 32 + l % 32][tap][ks * 16 + 8 * (l / 32) .. + 7].
 #include "y7t_common.h"
 #include "y7t_conv_common.h"
@@ -53,7 +53,7 @@ struct Ws2 {
 // FUSE: the layer's only consumers are the two 1x1 convolutions that open the next ELAN block (cfg/deploy/yolov7-w6.yaml:19-21: 128 -> 64 twice, one launch of 128 -> 128
 // in this library) -- then the 320 x 320 x 128 tensor between them is never written: a tile's activated fp16 output sits in the LDS gather anyway (64 pixels x 128
 // channels = exactly the 1x1 conv's B operand), the 1x1 filter bank is 8 more A-fragments per lane (32 registers), 16 more MFMAs per wave and tile, and the gather is
-// reused for the result.  korder 11: the 1x1 bank follows the 3x3 bank in memory (fragment (36 + ks) * 4 + q: lane l holds W2[q * 32 + l % 32][ks * 16 + 8 * (l / 32) .. + 7]),
+// reused for the result.  Y7T_WL_WS_S2_TWIN: the 1x1 bank follows the 3x3 bank in memory (fragment (36 + ks) * 4 + q: lane l holds W2[q * 32 + l % 32][ks * 16 + 8 * (l / 32) .. + 7]),
 // its 128 biases follow the 3x3 layer's.  Saves the write and the read of 0.84 GB per 32 frames and one launch.
 template <int ACT, bool FUSE>
 __global__ void __launch_bounds__(256, 1) k_conv3x3s2_c64_ws(const Y7TConvArgs p) {
@@ -279,31 +279,26 @@ __global__ void __launch_bounds__(256, 1) k_conv3x3s2_c64_ws(const Y7TConvArgs p
 
 }   // namespace
 
-// korder 8 layers only (detector/graph.py::ws_s2_eligible mirrors the conditions): 3x3 / 2 / 1, Cin == 64, Cout == 128, even input, output map of whole 2 x 32 tiles
+// Y7T_WL_WS_S2 (_TWIN) layers only (detector/graph.py::ws_s2_eligible mirrors the conditions): 3x3 / 2 / 1, Cin == 64, Cout == 128, even input, output map of whole 2 x 32 tiles
 int y7t_conv_ws_s2_launch(const Y7TConvArgs& a, hipStream_t s) {
     using C = Ws2;
     const bool ok = a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.Cin == 64 && a.Cout == 128 && a.Cout_pad == 128 && !a.out_f32 && !(a.ldout & 7) &&
                     !(a.cout_off & 7) && !(a.ldin & 7) && !(a.cin_off & 7) && !(a.H & 1) && !(a.W & 1) && a.Ho * 2 == a.H && a.Wo * 2 == a.W && a.in_bytes < 0x80000000u &&
                     a.Ho % C::TH == 0 && a.Wo % C::TW == 0 && !a.epi && a.up_C == 0;
     if (!ok) {
-        y7t_set_error("conv: weights are in the stride-2 register-fragment order (korder 8) but the layer is not a 3x3 / stride 2 / 64 -> 128 convolution of an even map "
+        y7t_set_error("conv: weights are in the stride-2 register-fragment order, Y7T_WL_WS_S2 (korder 8), but the layer is not a 3x3 / stride 2 / 64 -> 128 convolution of an even map "
                       "whose output is whole 2 x 32 tiles with an aligned fp16 output");
         return Y7T_E_ARG;
     }
     static Y7TOncePerDevice attr;      // (the attribute is per device: ADVICE r4)
-    if (int e_ = y7t_once_per_device(attr, [&]() -> int {
-#define WS2_ATTR(ACT) Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3s2_c64_ws<ACT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS)); \
-                      Y7T_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv3x3s2_c64_ws<ACT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        WS2_ATTR(Y7T_ACT_NONE) WS2_ATTR(Y7T_ACT_SILU) WS2_ATTR(Y7T_ACT_LEAKY)
-#undef WS2_ATTR
-        return 0;
-    })) return e_;
+    if (int e_ = y7t_set_max_lds(attr, C::LDS, k_conv3x3s2_c64_ws<Y7T_ACT_NONE, false>, k_conv3x3s2_c64_ws<Y7T_ACT_NONE, true>, k_conv3x3s2_c64_ws<Y7T_ACT_SILU, false>,
+                                 k_conv3x3s2_c64_ws<Y7T_ACT_SILU, true>, k_conv3x3s2_c64_ws<Y7T_ACT_LEAKY, false>, k_conv3x3s2_c64_ws<Y7T_ACT_LEAKY, true>)) return e_;
     static int wgs_env = -2;      // Y7T_CONV_WS_WGS: workgroups of a launch (default: one persistent workgroup per compute unit -- 154 KiB of LDS, 144 + registers of weights per lane)
     if (wgs_env == -2) wgs_env = y7t_exp_switch("Y7T_CONV_WS_WGS", -1);
     const int ncu = wgs_env > 0 ? wgs_env : y7t_num_cus();
     const int ptiles = a.B * (a.Ho / C::TH) * (a.Wo / C::TW);
     const int grid = ptiles < ncu ? ptiles : ncu;
-    const bool fuse = a.korder == 11;      // + the twin 1x1 convolution behind it (its bank and biases follow this layer's)
+    const bool fuse = a.korder == Y7T_WL_WS_S2_TWIN;      // + the twin 1x1 convolution behind it (its bank and biases follow this layer's)
 #define WS2_GO(ACT) do { if (fuse) hipLaunchKernelGGL((k_conv3x3s2_c64_ws<ACT, true>), dim3(grid), dim3(256), C::LDS, s, a); \
                          else hipLaunchKernelGGL((k_conv3x3s2_c64_ws<ACT, false>), dim3(grid), dim3(256), C::LDS, s, a); } while (0)
     if (a.act == Y7T_ACT_SILU) WS2_GO(Y7T_ACT_SILU);

@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from .. import _lib
+from .layout import WeightLayout as WL
 
 
 def make_divisible(x, divisor):
@@ -162,7 +163,7 @@ class Plan:
 
 def patch_panel_rows(H, W, cout, B):
     """rows of a weight panel (= output channels of a workgroup) of the LDS-patch kernel: 128 when Cout allows -- unless that leaves fewer than 512 workgroups of
-    256 pixels for the whole batch: then 64 (korder 9), twice the workgroups.  Measured at 32 frames (round 4, profiles/r04_smallmap_patch.txt): the 20x20 layers with
+    256 pixels for the whole batch: then 64 (WeightLayout.PATCH_N64), twice the workgroups.  Measured at 32 frames (round 4, profiles/r04_smallmap_patch.txt): the 20x20 layers with
     256 output channels 71 -> 51 us and 39 -> 28 us against the generic kernel, 61 / 36 us with 128-row panels.  Y7T_CONV_PATCH_PANEL64_BELOW=0 switches the rule off."""
     cout_pad = -(-cout // 64) * 64
     if cout_pad % 128:
@@ -277,7 +278,7 @@ WS128_S2_DEFAULT = "1"      # round 5, sessions r5h / r5i: 786 -> 644 us and 190
 def ws128_s2_eligible(H, W, cin, cout, k, s, p, out_ld, out_coff, out_f32, in_ld, in_coff, B=1 << 20):
     """mirror of y7t_conv_ws128_launch's stride-2 form (csrc/y7t_conv_ws128.hip, S2): the 3x3 / stride 2 layers with 128 input channels (w6: 128 -> 256 at 320 x 320 and at
     160 x 160) with the filter bank of a 128-channel output tile in registers, 2 x 16 output tiles from the op's tile counter.  Same weight order as the stride-1 kernel
-    (korder 6).  Follows Y7T_CONV_WS128 (=0 switches both forms off); Y7T_CONV_WS128_S2=0 alone is an experiment switch (measuring build)."""
+    (WeightLayout.WS128).  Follows Y7T_CONV_WS128 (=0 switches both forms off); Y7T_CONV_WS128_S2=0 alone is an experiment switch (measuring build)."""
     if _lib.switch("Y7T_CONV_WS128_S2", WS128_S2_DEFAULT) != "1" or _lib.switch("Y7T_CONV_WS128", WS128_DEFAULT) != "1" or _lib.switch("Y7T_CONV_VARIANT", "0") != "0":
         return False
     Ho, Wo = H // 2, W // 2
@@ -409,7 +410,7 @@ def lower(nodes, H, W, max_batch=1):
     heads = []
 
     def emit_conv(n, src, out_buf, out_ld, out_coff, out_f32, cout, act, wkey, kind="conv", level=-1, fuse_twin=None):
-        """fuse_twin = (a, b): `n` is the 64 -> 128 stride-2 layer and its only consumers are the twin 1x1 convs a, b -- ONE op (korder 11, csrc/y7t_conv_ws_s2.hip) whose
+        """fuse_twin = (a, b): `n` is the 64 -> 128 stride-2 layer and its only consumers are the twin 1x1 convs a, b -- ONE op (WS_S2_TWIN, csrc/y7t_conv_ws_s2.hip) whose
         output is the twins' concat slice; the tensor between them is never written.  Two wlayout entries (the 3x3 bank, then the 1x1 bank: adjacent in the blobs)."""
         nonlocal w_off, b_off
         cin_real = src.c
@@ -425,42 +426,42 @@ def lower(nodes, H, W, max_batch=1):
         op["out_buf"], op["out_ld"], op["out_coff"], op["out_f32"] = out_buf, out_ld, out_coff, out_f32
         op["Ho"], op["Wo"], op["Cout"], op["Cout_pad"] = n.h, n.w, cout, cout_pad
         op["KH"], op["KW"], op["stride"], op["pad"], op["K"], op["K_pad"], op["act"] = n.k, n.k, n.s, n.p, K, K_pad, act
-        korder = int(n.k == 3 and cin % 64 == 0)     # (kh, 64-channel chunk, kw) K order: consecutive K-steps reuse input lines
+        korder = WL.LINE_MAJOR if n.k == 3 and cin % 64 == 0 else WL.TAP_MAJOR      # (kh, 64-channel chunk, kw) K order: consecutive K-steps reuse input lines
         if ws_eligible(src.h, src.w, cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, src.ld, src.coff, max_batch):
-            korder = 5                               # weights-stationary kernel: the filter bank as MFMA A-fragments (weights.pack_ws)
+            korder = WL.WS64                         # weights-stationary kernel: the filter bank as MFMA A-fragments (weights.pack_ws)
         elif ws_s2_eligible(src.h, src.w, cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, src.ld, src.coff, max_batch):
-            korder = 8                               # ... and its stride-2 sibling for the 64 -> 128 down-sampling layer (weights.pack_ws_s2)
+            korder = WL.WS_S2                        # ... and its stride-2 sibling for the 64 -> 128 down-sampling layer (weights.pack_ws_s2)
         elif ws128_eligible(src.h, src.w, cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, src.ld, src.coff, max_batch):
-            korder = 6                               # ... and its 128-channel sibling (weights.pack_ws128)
+            korder = WL.WS128                        # ... and its 128-channel sibling (weights.pack_ws128)
         elif ws128_s2_eligible(src.h, src.w, cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, src.ld, src.coff, max_batch):
-            korder = 6                               # ... and the stride-2 form of that kernel (same packing)
+            korder = WL.WS128                        # ... and the stride-2 form of that kernel (same packing)
         elif patch_eligible(src.h, src.w, cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, max_batch):
-            korder = 2                               # LDS-patch kernel: weights in its panel order (weights.panel_pack)
+            korder = WL.PATCH                        # LDS-patch kernel: weights in its panel order (weights.panel_pack)
             if cout_pad % 128 == 0 and patch_panel_rows(src.h, src.w, cout, max_batch) == 64:
-                korder = 9                           # ... with 64-row panels
+                korder = WL.PATCH_N64                # ... with 64-row panels
         elif patch_s2_eligible(cin, cout, n.k, n.s, n.p, out_ld, out_coff, out_f32, max_batch * n.h * n.w):
-            korder = 4                               # stride-2 LDS-patch kernel, weights in its panel order (weights.panel_pack_s2)
+            korder = WL.PATCH_S2                     # stride-2 LDS-patch kernel, weights in its panel order (weights.panel_pack_s2)
         elif p8_eligible(src.h, src.w, cin, cout, n.k, n.s, out_ld, out_coff, out_f32, src.ld, src.coff, max_batch,
                          up=(src.virt_up[1], src.virt_up[0].c) if getattr(src, "virt_up", None) is not None else None, detect=level >= 0):
-            korder = 7                               # 1x1, Cout % 256 == 0, a tile per CU: 256 x 64 panels of the ping-pong pipeline (weights.panel_pack_p8)
+            korder = WL.P8                           # 1x1, Cout % 256 == 0, a tile per CU: 256 x 64 panels of the ping-pong pipeline (weights.panel_pack_p8)
         elif n.k == 1 and cin % 32 == 0 and _lib.switch("Y7T_CONV_VARIANT", "0") == "0" and _lib.switch("Y7T_CONV_WPANEL", "1") != "0":
-            korder = 3                               # 1x1: contiguous per-K-step weight panels (weights.panel_pack_linear)
+            korder = WL.PANEL_1X1                    # 1x1: contiguous per-K-step weight panels (weights.panel_pack_linear)
             if (cout_pad % 128 == 0 and level < 0 and getattr(src, "virt_up", None) is None and
                     -(-max_batch * n.h * n.w // 128) * (cout_pad // 128) < int(_lib.switch("Y7T_CONV_1X1_PANEL64_BELOW", "500"))):
-                korder = 10                          # ... as 64-row panels where 128-row tiles number fewer than 500 (round 4, profiles/r04_smallmap_patch.txt: the 20x20
+                korder = WL.PANEL_1X1_N64            # ... as 64-row panels where 128-row tiles number fewer than 500 (round 4, profiles/r04_smallmap_patch.txt: the 20x20
                                                      # layers with <= 512 output channels 34 -> 30, 61 -> 53, 20 -> 18 us; at 800 tiles and above 64 rows lose)
         if fuse_twin is not None:
-            if not (korder == 8 and cout == 128 and K_pad == K):
+            if not (korder == WL.WS_S2 and cout == 128 and K_pad == K):
                 return False                         # this layer does not get the stride-2 weights-stationary kernel after all (a switch that only this path reads):
                                                      # nothing has been emitted yet -- the caller emits the layer and its twin 1x1 as two ops
-            korder = 11
+            korder = WL.WS_S2_TWIN
         op["w_off"], op["bias_off"], op["korder"], op["detect_level"] = w_off, b_off, korder, level
         if fuse_twin is not None:
             ta, tb = fuse_twin
             ops.append(op)
-            wlayout.append(dict(korder=8, wkey=wkey, cin=cin_real, cin_pad=cin, cout=n.c, cout_pad=128, k=n.k, K=K, K_pad=K_pad, w_off=w_off, b_off=b_off, kind=kind, act=act,
+            wlayout.append(dict(korder=WL.WS_S2, wkey=wkey, cin=cin_real, cin_pad=cin, cout=n.c, cout_pad=128, k=n.k, K=K, K_pad=K_pad, w_off=w_off, b_off=b_off, kind=kind, act=act,
                                 macs=n.h * n.w * n.c * n.k * n.k * cin_real, fused_next=True))
-            wlayout.append(dict(korder=12, wkey=(ta.wkey, tb.wkey), cin=n.c, cin_pad=n.c, cout=ta.c + tb.c, cout_pad=128, k=1, K=n.c, K_pad=n.c, w_off=w_off + 128 * K_pad,
+            wlayout.append(dict(korder=WL.TWIN_TAIL, wkey=(ta.wkey, tb.wkey), cin=n.c, cin_pad=n.c, cout=ta.c + tb.c, cout_pad=128, k=1, K=n.c, K_pad=n.c, w_off=w_off + 128 * K_pad,
                                 b_off=b_off + 128, kind=kind, act=act, macs=n.h * n.w * (ta.c + tb.c) * n.c, fused_prev=True))
             w_off += 128 * K_pad + 128 * n.c
             b_off += 256

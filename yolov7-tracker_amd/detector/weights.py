@@ -5,6 +5,7 @@ m(x + ia) * im), and packing into the [Cout_pad][K_pad] fp16 layout of the impli
 import numpy as np
 
 from .. import _lib
+from .layout import WeightLayout as WL
 import torch
 
 BN_EPS = 1e-3
@@ -189,13 +190,13 @@ def folded(w, sd):
 
 
 def panel_pack(blk, cin_pad, narrow=False):
-    """[Cout_pad][K_pad] block with k = (kh*3 + kw)*Cin + ci  ->  the patch kernel's PANEL order (csrc/y7t_conv_patch.hip, korder 2):
+    """[Cout_pad][K_pad] block with k = (kh*3 + kw)*Cin + ci  ->  the patch kernel's PANEL order (csrc/y7t_conv_patch.hip, WeightLayout.PATCH):
     [n-tile of BN rows][K-step = 32-channel chunk * 9 + tap][row][four 16-byte slots], slot s of row r holding channel octet
     s ^ ((r >> 2) & 3) of the chunk -- byte for byte the image the kernel's buffer->LDS DMA leaves in LDS, so each K-step's
     panel is one contiguous run of full cache lines.  BN = 128 when Cout_pad allows, else 64."""
     cout_pad, K = blk.shape
     assert K == 9 * cin_pad and cin_pad % 64 == 0
-    BN = 128 if cout_pad % 128 == 0 and not narrow else 64      # (narrow: korder 9)
+    BN = 128 if cout_pad % 128 == 0 and not narrow else 64      # (narrow: PATCH_N64)
     nc32 = cin_pad // 32
     a = blk.reshape(cout_pad // BN, BN, 9, nc32, 4, 8)           # [tile][row][tap][chunk][octet][8]
     a = a.transpose(0, 3, 2, 1, 4, 5)                            # [tile][chunk][tap][row][octet][8]
@@ -206,11 +207,11 @@ def panel_pack(blk, cin_pad, narrow=False):
 
 
 def panel_pack_linear(blk, narrow=False):
-    """[Cout_pad][K_pad] block of a 1x1 layer -> panel order of the 32-deep generic kernel (csrc/y7t_conv.hip, korder 3):
+    """[Cout_pad][K_pad] block of a 1x1 layer -> panel order of the 32-deep generic kernel (csrc/y7t_conv.hip, WeightLayout.PANEL_1X1):
     [n-tile of BN rows][K-step of 32 channels][row][four 16-byte slots], slot s of row r = channel octet s ^ ((r >> 2) & 3)."""
     cout_pad, K = blk.shape
     assert K % 32 == 0
-    BN = 128 if cout_pad % 128 == 0 and not narrow else 64      # (narrow: korder 10)
+    BN = 128 if cout_pad % 128 == 0 and not narrow else 64      # (narrow: PANEL_1X1_N64)
     a = blk.reshape(cout_pad // BN, BN, K // 32, 4, 8).transpose(0, 2, 1, 3, 4)      # [tile][kstep][row][octet][8]
     r = np.arange(BN)
     src = np.arange(4)[None, :] ^ ((r[:, None] >> 2) & 3)
@@ -219,7 +220,7 @@ def panel_pack_linear(blk, narrow=False):
 
 
 def panel_pack_p8(blk):
-    """[Cout_pad][K] block of a 1x1 layer (Cout_pad % 256 == 0, K % 64 == 0) -> the panel order of csrc/y7t_conv_p8.hip (korder 7):
+    """[Cout_pad][K] block of a 1x1 layer (Cout_pad % 256 == 0, K % 64 == 0) -> the panel order of csrc/y7t_conv_p8.hip (WeightLayout.P8):
     [channel tile of 256][K-tile of 64][half h][row r of 128][eight 16-byte slots] = per (tile, K-tile) one contiguous 32 KiB block that IS the LDS image of the two
     channel half-tiles: row r of half h holds channel tile * 256 + (r // 32) * 64 + h * 32 + r % 32 (a wave's 64 output channels are contiguous), slot s of row r holds
     channel octet s ^ ((r >> 1) & 7) of the K-tile (the swizzle of the kernel's fragment reads)."""
@@ -241,7 +242,7 @@ def s2_panel_width(cout_pad):
 
 
 def panel_pack_s2(blk, cin_pad):
-    """[Cout_pad][K_pad] block with k = (kh*3 + kw)*Cin + ci  ->  the STRIDE-2 patch kernel's panel order (csrc/y7t_conv_patch_s2.hip, korder 4):
+    """[Cout_pad][K_pad] block with k = (kh*3 + kw)*Cin + ci  ->  the STRIDE-2 patch kernel's panel order (csrc/y7t_conv_patch_s2.hip, WeightLayout.PATCH_S2):
     [n-tile of BN rows][K-step = 16-channel chunk * 9 + tap][row][two 16-byte slots], slot s of row r holding channel octet s ^ ((r >> 3) & 1)
     of the chunk -- the image the kernel's buffer->LDS DMA leaves in LDS.  BN = 256 when Cout_pad allows, else 128."""
     cout_pad, K = blk.shape
@@ -257,7 +258,7 @@ def panel_pack_s2(blk, cin_pad):
 
 
 def pack_ws(blk):
-    """[64][576] block of a 64 -> 64 3x3 layer with k = (kh*3 + kw)*64 + ci  ->  the register-fragment order of csrc/y7t_conv_ws.hip (korder 5): fragment
+    """[64][576] block of a 64 -> 64 3x3 layer with k = (kh*3 + kw)*64 + ci  ->  the register-fragment order of csrc/y7t_conv_ws.hip (WeightLayout.WS64): fragment
     f = (tap * 4 + ks) * 2 + i is 1 KiB = 64 lanes x 8 halves, lane l holding W[i*32 + l % 32][tap][ks*16 + 8*(l // 32) .. +7] -- the A operand of
     v_mfma_f32_32x32x16_f16 exactly as a lane keeps it, so that a wave loads a fragment with ONE 16-byte load per lane from consecutive addresses."""
     assert blk.shape == (64, 576)
@@ -267,7 +268,7 @@ def pack_ws(blk):
 
 
 def pack_ws_s2(blk):
-    """[128][576] block of the 64 -> 128 3x3 / stride 2 layer with k = (kh*3 + kw)*64 + ci  ->  the register-fragment order of csrc/y7t_conv_ws_s2.hip (korder 8):
+    """[128][576] block of the 64 -> 128 3x3 / stride 2 layer with k = (kh*3 + kw)*64 + ci  ->  the register-fragment order of csrc/y7t_conv_ws_s2.hip (WeightLayout.WS_S2):
     fragment f = (tap * 4 + ks) * 4 + q is 1 KiB = 64 lanes x 8 halves, lane l holding W[q*32 + l % 32][tap][ks*16 + 8*(l // 32) .. +7] (wave q keeps channels 32 q .. + 31)."""
     assert blk.shape == (128, 576)
     a = blk.reshape(4, 32, 9, 4, 2, 8)          # [q][l31][tap][ks][hi][8]
@@ -276,7 +277,7 @@ def pack_ws_s2(blk):
 
 
 def pack_ws_s2_tail(blk):
-    """[128][128] block of the twin 1x1 convolution fused behind the stride-2 layer (korder 11 ops; wlayout korder 12)  ->  its 8 x 4 A-fragments behind the 3x3 bank:
+    """[128][128] block of the twin 1x1 convolution fused behind the stride-2 layer (WS_S2_TWIN ops; wlayout entry TWIN_TAIL)  ->  its 8 x 4 A-fragments behind the 3x3 bank:
     fragment (ks, q) is 1 KiB, lane l holding W2[q*32 + l % 32][ks*16 + 8*(l // 32) .. +7]"""
     assert blk.shape == (128, 128)
     a = blk.reshape(4, 32, 8, 2, 8)             # [q][l31][ks][hi][8]
@@ -286,13 +287,31 @@ def pack_ws_s2_tail(blk):
 
 def pack_ws128(blk):
     """[Cout_pad][1152] block of a 128 -> 128 k 3x3 layer (Cout_pad a multiple of 128) with k = (kh*3 + kw)*128 + ci  ->  the register-fragment order of
-    csrc/y7t_conv_ws128.hip (korder 6): per 128-channel output tile n, fragment f = (n*72 + tap*8 + ks)*4 + q is 1 KiB = 64 lanes x 8 halves, lane l holding
+    csrc/y7t_conv_ws128.hip (WeightLayout.WS128): per 128-channel output tile n, fragment f = (n*72 + tap*8 + ks)*4 + q is 1 KiB = 64 lanes x 8 halves, lane l holding
     W[n*128 + q*32 + l % 32][tap][ks*16 + 8*(l // 32) .. +7]"""
     cp = blk.shape[0]
     assert blk.shape[1] == 1152 and cp % 128 == 0
     a = blk.reshape(cp // 128, 4, 32, 9, 8, 2, 8)      # [n][q][l31][tap][ks][hi][8]
     a = a.transpose(0, 3, 4, 1, 5, 2, 6)               # [n][tap][ks][q][hi][l31][8]   (lane = hi * 32 + l31)
     return np.ascontiguousarray(a).reshape(cp, 1152)
+
+
+# layout -> its packer: (the [Cout_pad][K_pad] block in TAP_MAJOR order -- LINE_MAJOR for that layout --, cin_pad) -> the block as the layout's kernel reads it
+PACKERS = {
+    WL.TAP_MAJOR: lambda blk, cin_pad: blk,
+    WL.LINE_MAJOR: lambda blk, cin_pad: blk,
+    WL.PATCH: lambda blk, cin_pad: panel_pack(blk, cin_pad),
+    WL.PATCH_N64: lambda blk, cin_pad: panel_pack(blk, cin_pad, narrow=True),
+    WL.PANEL_1X1: lambda blk, cin_pad: panel_pack_linear(blk),
+    WL.PANEL_1X1_N64: lambda blk, cin_pad: panel_pack_linear(blk, narrow=True),
+    WL.PATCH_S2: lambda blk, cin_pad: panel_pack_s2(blk, cin_pad),
+    WL.WS64: lambda blk, cin_pad: pack_ws(blk),
+    WL.WS128: lambda blk, cin_pad: pack_ws128(blk),
+    WL.P8: lambda blk, cin_pad: panel_pack_p8(blk),
+    WL.WS_S2: lambda blk, cin_pad: pack_ws_s2(blk),
+    WL.WS_S2_TWIN: lambda blk, cin_pad: pack_ws_s2(blk),      # (the op's first bank; its wlayout entries are WS_S2 and TWIN_TAIL)
+    WL.TWIN_TAIL: lambda blk, cin_pad: pack_ws_s2_tail(blk),
+}
 
 
 def pack(wlayout, sd, w_elems, b_elems):
@@ -306,26 +325,11 @@ def pack(wlayout, sd, w_elems, b_elems):
         assert W.shape == (cout, cin, k, k), (w["wkey"], W.shape, (cout, cin, k, k))
         Wt = np.zeros((cout, k, k, w["cin_pad"]), np.float64)
         Wt[..., :cin] = W.transpose(0, 2, 3, 1)
-        if w.get("korder") == 1:   # (cout, kh, kw, chunk, 64) -> (cout, kh, chunk, kw, 64)
+        if w["korder"] == WL.LINE_MAJOR:   # (cout, kh, kw, chunk, 64) -> (cout, kh, chunk, kw, 64)
             Wt = Wt.reshape(cout, k, k, w["cin_pad"] // 64, 64).transpose(0, 1, 3, 2, 4)
         blk = np.zeros((w["cout_pad"], w["K_pad"]), np.float16)
         blk[:cout, :w["K"]] = Wt.reshape(cout, -1).astype(np.float16)
-        if w.get("korder") in (2, 9):
-            blk = panel_pack(blk, w["cin_pad"], narrow=w["korder"] == 9)
-        elif w.get("korder") in (3, 10):
-            blk = panel_pack_linear(blk, narrow=w["korder"] == 10)
-        elif w.get("korder") == 4:
-            blk = panel_pack_s2(blk, w["cin_pad"])
-        elif w.get("korder") == 5:
-            blk = pack_ws(blk)
-        elif w.get("korder") == 6:
-            blk = pack_ws128(blk)
-        elif w.get("korder") == 7:
-            blk = panel_pack_p8(blk)
-        elif w.get("korder") == 8:
-            blk = pack_ws_s2(blk)
-        elif w.get("korder") == 12:
-            blk = pack_ws_s2_tail(blk)
+        blk = PACKERS[w["korder"]](blk, w["cin_pad"])
         wb[w["w_off"]:w["w_off"] + blk.size] = blk.reshape(-1)
         bb[w["b_off"]:w["b_off"] + cout] = b.astype(np.float32)
     return wb, bb
