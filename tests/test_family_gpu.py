@@ -234,7 +234,7 @@ NEW_CONV_CASES = new_conv_cases()
 @pytest.mark.parametrize("case", NEW_CONV_CASES, ids=["k%d-%dto%d-%dx%ds%d" % (layout_of(c[7])[0], c[3], c[4], c[5], c[5], c[6]) for c in NEW_CONV_CASES])
 def test_new_conv_shapes_match_torch_fp32(L, case):
     from tests.test_detector_gpu import test_conv_layer_matches_torch_fp32
-    test_conv_layer_matches_torch_fp32(L, case)
+    test_conv_layer_matches_torch_fp32(L, case, util.conv_dispatch_name(case))      # (the cases come out of the plans: the name from the dispatch rule restated in tests/util.py)
 
 
 def test_new_conv_shapes_cover_the_named_ones():

@@ -34,6 +34,69 @@ def layer_cout_pad(cout, layout):
     return (cout + rows - 1) // rows * rows
 
 
+def conv_dispatch_name(case):
+    """the kernel name the library must report for a single-layer case (B, H, W, Cin, Cout, k, s, act, in_ld, in_coff, out_ld, out_coff, out_f32) of
+    y7t_conv2d_nhwc_f16: csrc/y7t_conv.hip::conv_dispatch / launch_conv / launch_conv_ut, y7t_conv_patch.hip::y7t_conv_patch_try and the launchers of the layouts that
+    one kernel reads, restated from their text (no tile counter through this entry point: the statically partitioned forms; default switches).  For case lists that
+    are generated from plans; the hand-written names of tests/test_detector_gpu.py::CONV_CASES pin this restatement (tests/test_conv_ref_cpu.py)."""
+    from yolov7_tracker_amd.detector.layout import WeightLayout as WL, layout_of
+    B, H, W, Cin, Cout, k, s, act, in_ld, in_coff, out_ld, out_coff, out_f32 = case[:13]
+    lay, force = layout_of(act)
+    cout_pad = layer_cout_pad(Cout, lay)
+    p = k // 2
+    M = B * ((H + 2 * p - k) // s + 1) * ((W + 2 * p - k) // s + 1)
+    K_pad = (k * k * Cin + 63) // 64 * 64
+    if lay in (WL.WS_S2, WL.WS_S2_TWIN):
+        return "ws_s2<2,32>" + (" + 1x1" if lay == WL.WS_S2_TWIN else "")
+    one = {WL.P8: "p8<256,256,64> 1x1", WL.WS64: "ws64<16,16>", WL.WS128: "ws128<4,16>" if s == 1 else "ws128_s2<2,16>",
+           WL.PATCH_S2: "patch_s2<256>" if cout_pad % 256 == 0 else "patch_s2<128>"}
+    if lay in one:
+        return one[lay]
+    panel64 = lay in (WL.PATCH_N64, WL.PANEL_1X1_N64)
+
+    def igemm(BM, BN, BK, NST):
+        km1 = k == 1 and s == 1 and Cin % 64 == 0
+        tiles, nk = -(-M // BM) * (cout_pad // BN), K_pad // BK
+        S = 1
+        if tiles < 256 and nk >= 8:
+            S = max(1, min(-(-512 // tiles), nk // 4, 16))
+            while S > 1 and S * M * cout_pad * 4 > 128 << 20:
+                S -= 1
+            S = -(-nk // -(-nk // S))
+        return "igemm<%d,%d,%d,%d>%s%s" % (BM, BN, BK, NST, " 1x1" if km1 else "" if Cin % BK == 0 else " ragged-K", " splitK" if S > 1 else "")
+
+    if lay in (WL.PANEL_1X1, WL.PANEL_1X1_N64):
+        return igemm(128, 128, 32, 2) if cout_pad % 128 == 0 and not panel64 else igemm(128, 64, 32, 2)
+    is_patch = lay in (WL.PATCH, WL.PATCH_N64)
+    if k == 3 and s == 1 and Cin % 64 == 0 and not out_f32 and not (Cout % 8 or out_ld % 8 or out_coff % 8):      # y7t_conv_patch_try
+        pwide = cout_pad % 128 == 0 and not panel64
+        bn = 128 if pwide else 64
+        eff = lambda tw, th: (W * H) / float(-(-W // tw) * tw * -(-H // th) * th)
+        e16, e32 = eff(16, 16), eff(32, 8)
+        tw, th, e = (16, 16, e16) if e16 >= e32 else (32, 8, e32)
+        if force or is_patch or B * H * W * (cout_pad // bn) >= 256 * 256:
+            if W in (20, 40) and 1.0 > e:
+                return "patch_strip<%d,%d>" % (W, bn)
+            if force or is_patch or e >= 0.8:
+                ptiles = B * -(-H // th) * -(-W // tw)
+                if not pwide and (ptiles * (cout_pad // 64) >= 4 * 2048 or force):
+                    return "patch_mt<%d,%d,4>" % (tw, th)
+                return "patch<%d,%d,%d>" % (tw, th, bn)
+    assert not is_patch, "a PATCH layout on a layer the patch kernel cannot run"
+    wide = cout_pad % 128 == 0
+    if k == 1:
+        return igemm(128, 128, 32, 2) if wide else igemm(128, 64, 32, 2)
+    big256 = (M // 256) * (cout_pad // (128 if wide else 64)) >= 2048
+    if Cin <= 16 and not wide and big256:
+        return igemm(256, 64, 32, 2)
+    if s == 2 and big256:
+        return igemm(256, 128, 32, 2) if wide else igemm(256, 64, 32, 2)
+    tm = -(-M // 128)
+    if wide and not (tm * (cout_pad // 128) < 256 and tm * (cout_pad // 64) >= 256):
+        return igemm(128, 128, 64, 2)
+    return igemm(128, 64, 64, 2)
+
+
 def load_tracker_case(name):
     g = np.load(os.path.join(GOLDEN, "tracker_%s.npz" % name))
     counts = g["det_counts"]
