@@ -140,6 +140,7 @@ class TrackerNP:
         assert kind in ("sort", "bytetrack", "botsort", "deepsort")
         self.feature_fn = None            # deepsort: (N, 4) tlbr -> (N, D) appearance features (stands in for the ReID network)
         self.dot = np.dot                 # cal_cosine_distance's product (matching.py:178)
+        self.feature_budget = 100         # STrack's store_features_budget (basetrack.py:76); a test may shorten it to make the feature lists wrap
         self.kind, self.fmt = kind, kalman_format
         self.det_thresh = conf_thresh
         self.iou_thresh = iou_thresh
@@ -174,7 +175,7 @@ class TrackerNP:
         if det.features:                                  # basetrack.py:324-332, use_avg_of_feature=False (deepsort.py:111)
             f = det.features[0] / np.linalg.norm(det.features[0])
             t.features.append(f)
-            t.features = t.features[-100:]
+            t.features = t.features[-self.feature_budget:]
         t.state, t.activated, t.tsu = TRACKED, True, 0
 
     def _reactivate(self, t, det):
@@ -384,12 +385,14 @@ def dot_sequential(a, bt):
     return acc
 
 
-def run(kind, dets_per_frame, ids=None, warps=None, feature_fn=None, dot=None, **kw):
+def run(kind, dets_per_frame, ids=None, warps=None, feature_fn=None, dot=None, feature_budget=None, **kw):
     """-> per-frame list of (track_id, tlwh float64[4], cls, score), like ref_harness.run_reference_tracker."""
     trk = TrackerNP(kind, ids=ids if ids is not None else IdCounter(), **kw)
     trk.feature_fn = feature_fn
     if dot is not None:
         trk.dot = dot
+    if feature_budget is not None:
+        trk.feature_budget = feature_budget
     out = []
     for fi, det in enumerate(dets_per_frame):
         cur = trk.update_without_detection() if det is None else trk.update(det, None if warps is None else warps[fi])

@@ -82,6 +82,12 @@ def lib():
         L.hs_feat_init.argtypes = [vp] + [ci] * 4
         L.hs_deepsort_step.argtypes = [vp, vp, vp, ci, vp, vp, ci]
         L.hs_feat_status.argtypes = [vp]
+        L.hs_np_pairwise_sumsq.restype = ctypes.c_float
+        L.hs_np_pairwise_sumsq.argtypes = [vp, ci]
+        L.hs_blas_sdot_self.restype = ctypes.c_float
+        L.hs_blas_sdot_self.argtypes = [vp, ci]
+        L.hs_feat_store.argtypes = [vp, vp, ci, ci]
+        L.hs_feat_normalize.argtypes = [vp, ci, ci, vp]
         # StrongSORT
         L.hs_ss_feat_bytes.restype = sz
         L.hs_ss_feat_bytes.argtypes = [ci, ci, ci]
@@ -112,6 +118,35 @@ def pyset_difference(n, matched):
     c = lib().hs_pyset_difference(n, member.ctypes.data, len(set(matched)), out.ctypes.data)
     assert c >= 0
     return out[:c].tolist()
+
+
+def np_pairwise_sumsq(x):
+    """y7t_np_pairwise_sumsq of a float32 vector (np.linalg.norm(axis=1)'s sum, before the sqrt) -> np.float32"""
+    x = np.ascontiguousarray(x, np.float32)
+    return np.float32(lib().hs_np_pairwise_sumsq(x.ctypes.data, x.size))
+
+
+def blas_sdot_self(x):
+    """y7t_blas_sdot_self of a float32 vector (the 1-D np.linalg.norm's sum, before the sqrt) -> np.float32"""
+    x = np.ascontiguousarray(x, np.float32)
+    return np.float32(lib().hs_blas_sdot_self(x.ctypes.data, x.size))
+
+
+def feat_store(src, update):
+    """y7t_feat_store: the ring row a raw appearance vector becomes (update: STrack.update's f / norm(f) first)"""
+    src = np.ascontiguousarray(src, np.float32)
+    dst = np.empty_like(src)
+    lib().hs_feat_store(dst.ctypes.data, src.ctypes.data, src.size, int(bool(update)))
+    return dst
+
+
+def feat_normalize(feats):
+    """y7t_feat_normalize_dets: the (n, dim) detection features of a frame, every row divided by its norm"""
+    feats = np.ascontiguousarray(feats, np.float32)
+    out = np.empty_like(feats)
+    if len(feats):
+        lib().hs_feat_normalize(feats.ctypes.data, feats.shape[0], feats.shape[1], out.ctypes.data)
+    return out
 
 
 def lapjv(cost, limit, sap=False, literal=False):

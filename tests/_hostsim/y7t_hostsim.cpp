@@ -142,6 +142,21 @@ int hs_pyset_difference(int n, const int* member, int n_other, int* out) {
     free(tab);
     return st ? -1 : c;
 }
+// the appearance arithmetic on its own: the two sums of squares (numpy's pairwise add.reduce, OpenBLAS's sdot), one stored vector, a frame's normalised rows
+float hs_np_pairwise_sumsq(const float* x, int n) { return y7t_np_pairwise_sumsq(x, n); }
+float hs_blas_sdot_self(const float* x, int n) { return y7t_blas_sdot_self(x, n); }
+void hs_feat_store(float* dst, const float* src, int dim, int update) { y7t_feat_store(dst, src, dim, update); }
+void hs_feat_normalize(const float* feats, int n, int dim, float* out) {      // y7t_feat_normalize_dets into the caller's n x dim buffer
+    Y7TFeatHdr hdr;
+    memset(&hdr, 0, sizeof(hdr));
+    hdr.dim = dim; hdr.cap_d = n;
+    int* cm = (int*)malloc(sizeof(int) * (2 * (size_t)n + 2));
+    Y7TFeat f;
+    memset(&f, 0, sizeof(f));
+    f.h = &hdr; f.detn = out; f.cmin = cm; f.cmax = cm + n + 1;
+    y7t_feat_normalize_dets(hs_ex(), f, feats, n);
+    free(cm);
+}
 
 // ---- StrongSORT (y7t_track_strongsort.h): the plain forms of the frame's three launches (appearance distances, the step, the queued vector stores) ----
 size_t hs_ss_feat_bytes(int cap_t, int cap_d, int dim) { return y7t_ss_layout(cap_t, cap_d, dim).total; }

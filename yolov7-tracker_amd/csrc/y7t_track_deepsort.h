@@ -142,9 +142,11 @@ Y7T_FN int y7t_pyset_difference_list(int n, const int* unm, int n_unm, int n_oth
 //   * np.linalg.norm(mat, axis=1): x * x rounded to float32, then add.reduce's PAIRWISE sum (numpy/_core/src/umath/loops_utils.h.src:
 //     8 running sums for blocks <= 128, recursive halving above), sqrt;
 //   * np.dot(mat1, mat2.T) (sgemm): one sequential fused-multiply-add chain over k per output;
-//   * np.linalg.norm(vec) of a 1-D feature (STrack.update, basetrack.py:325) = sqrt(sdot(x, x)): OpenBLAS's SkylakeX sdot kernel --
-//     four 16-lane accumulators over 64 elements per step (FMA), folded 16 -> 8 lanes, summed ((a0 + a1) + a2) + a3, halves added,
-//     two horizontal adds.
+//   * np.linalg.norm(vec) of a 1-D feature (STrack.update, basetrack.py:325) = sqrt(sdot(x, x)): OpenBLAS's SkylakeX sdot kernel over the
+//     first n & -32 elements -- four 16-lane accumulators over 64 elements per step (FMA), folded 16 -> 8 lanes, summed
+//     ((a0 + a1) + a2) + a3, halves added, two horizontal adds -- and its driver (kernel/x86_64/sdot.c) for the n & 31 that remain: their
+//     float32 products summed into a DOUBLE, the kernel's float32 sum added in double, one rounding to float32.
+// tests/golden/np_norms.npz holds numpy's own bits of both norms at 18 widths; tests/test_deepsort_feat_cpu.py compares these restatements with them.
 // ---------------------------------------------------------------------------------------------
 Y7T_NOINL float y7t_np_pairwise_sumsq(const float* x, int n) {
     if (n < 8) {
@@ -175,6 +177,14 @@ Y7T_FN float y7t_fmaf(float a, float b, float c) {
 #endif
 }
 
+// the driver's tail: `kern` is the kernel's sum of the first n1 = n & -32 elements
+Y7T_FN float y7t_blas_sdot_tail(const float* x, int n1, int n, float kern) {
+    if (n1 == n) return kern;
+    double tail = 0.0;
+    for (int k = n1; k < n; ++k) { const float p = x[k] * x[k]; tail = tail + (double)p; }
+    return (float)(tail + (double)kern);
+}
+
 Y7T_FN float y7t_blas_sdot_self(const float* x, int n) {
     const int n1 = n & -32, n64 = n1 & ~63;
     float a5[4][16], a[4][8];
@@ -188,9 +198,8 @@ Y7T_FN float y7t_blas_sdot_self(const float* x, int n) {
     float sv[8], hv[4];
     for (int l = 0; l < 8; ++l) sv[l] = ((a[0][l] + a[1][l]) + a[2][l]) + a[3][l];
     for (int l = 0; l < 4; ++l) hv[l] = sv[l] + sv[l + 4];
-    float d = (hv[0] + hv[1]) + (hv[2] + hv[3]);
-    for (int k = n1; k < n; ++k) d = d + x[k] * x[k];
-    return d;
+    const float d = (hv[0] + hv[1]) + (hv[2] + hv[3]);
+    return y7t_blas_sdot_tail(x, n1, n, d);
 }
 
 #if Y7T_DEVICE
@@ -225,9 +234,8 @@ Y7T_FN float y7t_wave_sdot_self(const float* x, int n, int lane) {
     const float sv = ((a0 + a1) + a2) + a3;                                                     // sv[l & 7] on every lane
     const float hv = sv + __shfl(sv, (lane & 48) + (((l & 7) + 4) & 7), 64);                    // l & 7 < 4: sv[l] + sv[l + 4]
     const float h0 = __shfl(hv, 0, 64), h1 = __shfl(hv, 1, 64), h2 = __shfl(hv, 2, 64), h3 = __shfl(hv, 3, 64);
-    float d = (h0 + h1) + (h2 + h3);
-    for (int k = n1; k < n; ++k) d = d + x[k] * x[k];
-    return d;
+    const float d = (h0 + h1) + (h2 + h3);
+    return y7t_blas_sdot_tail(x, n1, n, d);      // (no wave width has a tail; every lane would walk it alike)
 }
 #endif
 

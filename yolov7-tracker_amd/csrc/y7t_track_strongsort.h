@@ -126,17 +126,9 @@ Y7T_FN float y7t_ss_mix(float prev, float f) {
     const float a = 0.9f * prev, b = 0.1f * f;
     return a + b;
 }
-// sdot(x, x) for any n: OpenBLAS's kernel takes the first n & -32 elements (y7t_blas_sdot_self), its driver (kernel/x86_64/sdot.c) sums the float32 products of the
-// remaining ones into a DOUBLE, adds the kernel's sum and rounds once.  (y7t_blas_sdot_self's own tail adds them in float32: DeepSORT's restatement, a few ulps off
-// for dimensions that are not a multiple of 32, left as it is.)
-Y7T_FN float y7t_ss_sdot_self(const float* x, int n) {
-    const int n1 = n & -32;
-    const float kern = n1 ? y7t_blas_sdot_self(x, n1) : 0.f;
-    if (n1 == n) return kern;
-    double tail = 0.0;
-    for (int k = n1; k < n; ++k) { const float p = x[k] * x[k]; tail = tail + (double)p; }
-    return (float)(tail + (double)kern);
-}
+// sdot(x, x) for any n: y7t_blas_sdot_self (y7t_track_deepsort.h) -- OpenBLAS's kernel over the first n & -32 elements and its driver's double-precision tail;
+// one restatement for both trackers.
+Y7T_FN float y7t_ss_sdot_self(const float* x, int n) { return y7t_blas_sdot_self(x, n); }
 Y7T_FN void y7t_ss_ema(float* vec, const float* raw, int dim) {
     const float nb = sqrtf(y7t_ss_sdot_self(raw, dim));
     for (int d = 0; d < dim; ++d) vec[d] = y7t_ss_mix(vec[d], raw[d] / nb);
