@@ -400,8 +400,9 @@ int y7t_det_forward_stem_u8(y7t_det* det, const void* frames_u8, int B, int H0, 
 int y7t_letterbox_layout_u8(const void* img, int B, int H0, int W0, int H, int W, int new_h, int new_w, int top, int left, int reorg,
                             void* out_f16, int ldout, y7t_stream stream);
 
-/* Detect.forward decode (models/yolo.py:39-57) + non_max_suppression (utils/general.py:607-695, multi_label=False,
- * agnostic=False) + scale_coords/clip/round (general.py:319-340, tracker/track.py:234-244), all on the device.
+/* Detect.forward decode (models/yolo.py:39-57) + non_max_suppression (utils/general.py:607-695; y7t_det_postprocess: classes=None,
+ * agnostic=False, multi_label=False -- the tracking path; y7t_det_postprocess_ex: all three through y7t_nms_opts; labels=() always)
+ * + scale_coords/clip/round (general.py:319-340, tracker/track.py:234-244), all on the device.
  * head[l]: NHWC fp32 output of the l-th Detect 1x1 conv, [B][ny][nx][na*no].  anchors: [nl][na][2] pixels (host).
  * letterbox: DEVICE [B][5] = gain, pad_w, pad_h, H0, W0.  dets: [B][max_det][6]; ndets: [B];
  * cand_count (may be NULL): [B] candidates above conf_thres (> cap == overflow, caller must check).
@@ -413,6 +414,32 @@ int y7t_det_postprocess(const float* const* head_host_array_of_dev_ptrs, const i
                         const float* anchors, int nl, int na, int no, int B, float conf_thres, float iou_thres, int max_det,
                         int max_nms, int cap, const float* letterbox, float* dets, int* ndets, int* keep_idx, int* cand_count,
                         void* workspace, size_t workspace_bytes, y7t_stream stream);
+
+/* The remaining arguments of non_max_suppression (general.py:607-608), by value: nothing is allocated, the call stays capturable.
+ *   multi_label    with nc > 1 every class j of a row with obj > conf_thres and sigmoid(cls_j) * obj > conf_thres is its own candidate
+ *                  (box, that score, j) (general.py:654-656); nc == 1 runs the best-class path (:624).  The candidates of a row share its cidx;
+ *                  cand_count counts (row, class) pairs, and a row's pairs are only written below cap.  Decode pass only: the fused Detect
+ *                  epilogues keep the best class alone, so head == NULL with multi_label is Y7T_E_STATE.  rows x nc >= 2^31 (the sort key's
+ *                  low word and the candidate counter hold row * nc + class): Y7T_E_ARG.
+ *   filter_classes != 0: `classes is not None` (:662-663) -- a candidate stays iff bit (c % 32) of class_mask[c / 32] is set for its class c.
+ *                  An all-zero mask is classes=[]; ids outside [0, nc) match nothing.  Applied in the rank sort, before the max_nms cut, on
+ *                  either candidate source; the candidate arrays and cand_count are NOT filtered (keep_idx addresses the unfiltered slots),
+ *                  so further calls on the same workspace with other options each give their own answer.  nc > 32 * Y7T_NMS_MASK_WORDS
+ *                  together with a filter: Y7T_E_ARG.
+ *   agnostic       the class offset cls * 4096 of the NMS is 0 (:677): one box per object whatever its class.
+ * Order of the walk: score descending, then anchor row ascending, then class ascending.  Refusals write nothing.
+ * opts == NULL (or all zero) is y7t_det_postprocess exactly: the same kernels, the same launches. */
+enum { Y7T_NMS_MASK_WORDS = 8 };
+typedef struct y7t_nms_opts {
+    int32_t agnostic;
+    int32_t multi_label;
+    int32_t filter_classes;
+    uint32_t class_mask[Y7T_NMS_MASK_WORDS];
+} y7t_nms_opts;
+int y7t_det_postprocess_ex(const float* const* head_host_array_of_dev_ptrs, const int* ny, const int* nx, const float* strides,
+                           const float* anchors, int nl, int na, int no, int B, float conf_thres, float iou_thres, int max_det,
+                           int max_nms, int cap, const float* letterbox, float* dets, int* ndets, int* keep_idx, int* cand_count,
+                           void* workspace, size_t workspace_bytes, y7t_stream stream, const y7t_nms_opts* opts);
 
 /* ---------------------------------------------------------------- ReID embedding (DeepSORT's appearance branch) ---- */
 /* DeepSORT.get_feature -> Extractor (tracker/deepsort.py:19-41, tracker/reid_models/deepsort_reid.py:112-153) with OSNet

@@ -1,6 +1,6 @@
 """Rank sort + kept-list NMS alone (y7t_det_postprocess on predecoded candidates) at ONE frame and at 40: HIP events around the post-processing of a fused forward
 whose Detect epilogues left ~2000 candidates per frame (the bench's configuration: conditioned weights, planted objectness, all four levels live).
-    python scripts/time_nms.py"""
+    python scripts/time_nms.py [batch ...]          # default: 1 40"""
 import os, sys, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -8,7 +8,7 @@ import bench
 from yolov7_tracker_amd import synth
 from yolov7_tracker_amd.detector import arch, model
 
-for B in (1, 40):
+for B in [int(v) for v in sys.argv[1:]] or (1, 40):
     frames_host = synth.make_frames(B, 80, 1280, seq_idx=0)
     sd = bench.conditioned_state_dict(types.SimpleNamespace(arch="yolov7-w6", img=1280), 10, frames_host)
     det = model.Detector(arch.yolov7_w6(10), sd, img_size=(1280, 1280), max_batch=B, seed=0)

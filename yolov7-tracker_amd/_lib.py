@@ -91,6 +91,8 @@ SIGNATURES = {
     "y7t_det_postprocess_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "y7t_det_postprocess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "y7t_det_postprocess_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "y7t_reid_create": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "y7t_reid_destroy": (c_int, [c_void_p]),
     "y7t_reid_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
@@ -156,6 +158,30 @@ def stream_ptr():
 def ptr(t):
     """device/host pointer of a torch tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+NMS_MASK_WORDS = 8      # Y7T_NMS_MASK_WORDS
+
+
+class NmsOpts(ctypes.Structure):
+    """y7t_nms_opts (include/y7t.h)"""
+    _fields_ = [("agnostic", ctypes.c_int32), ("multi_label", ctypes.c_int32), ("filter_classes", ctypes.c_int32),
+                ("class_mask", ctypes.c_uint32 * NMS_MASK_WORDS)]
+
+
+def nms_opts(classes=None, agnostic=False, multi_label=False):
+    """the y7t_nms_opts of non_max_suppression's (classes, agnostic, multi_label), or None for the defaults (the caller then takes y7t_det_postprocess itself).
+    classes: None, or an iterable of class ids ([] removes everything; an id no class has matches nothing, as `x[:, 5:6] == classes` does)"""
+    if classes is None and not agnostic and not multi_label:
+        return None
+    o = NmsOpts(int(bool(agnostic)), int(bool(multi_label)), int(classes is not None))
+    for c in (classes if classes is not None else ()):
+        if float(c) != int(c):
+            continue                     # (a class column holds integers: a fractional id equals none of them)
+        c = int(c)
+        if 0 <= c < 32 * NMS_MASK_WORDS:
+            o.class_mask[c >> 5] |= 1 << (c & 31)
+    return o
 
 
 def cu_masked_streams(reserved, total=None):

@@ -84,6 +84,11 @@ struct Y7TPostArgs {
     int* keep_idx;          // [B][max_det] candidate slot of each kept detection
     int* count_out;         // [B] number of candidates found (> cap means overflow) or null
     void* ws; size_t ws_bytes;
+    // y7t_nms_opts (include/y7t.h); all zero: the tracking path's chain, launch for launch
+    int agnostic;           // class offset 0 (general.py:677)
+    int multi_label;        // one candidate per (row, class) above conf_thres (general.py:654-656); decode pass only, no > 6
+    int filter_classes;     // keep the candidates whose class has its bit in class_mask (general.py:662-663)
+    uint32_t class_mask[8]; // Y7T_NMS_MASK_WORDS: bit c % 32 of word c / 32 = class c
 };
 size_t y7t_post_ws_bytes(int B, int cap, int max_nms);
 // the candidate arrays at the start of a postprocess workspace (shared with the fused Detect epilogue)

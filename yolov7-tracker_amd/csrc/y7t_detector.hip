@@ -243,6 +243,14 @@ extern "C" int y7t_det_postprocess(const float* const* head, const int* ny, cons
                                    int na, int no, int B, float conf_thres, float iou_thres, int max_det, int max_nms, int cap,
                                    const float* letterbox, float* dets, int* ndets, int* keep_idx, int* cand_count, void* ws, size_t ws_bytes,
                                    y7t_stream stream) {
+    return y7t_det_postprocess_ex(head, ny, nx, strides, anchors, nl, na, no, B, conf_thres, iou_thres, max_det, max_nms, cap, letterbox, dets, ndets, keep_idx,
+                                  cand_count, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int y7t_det_postprocess_ex(const float* const* head, const int* ny, const int* nx, const float* strides, const float* anchors, int nl,
+                                      int na, int no, int B, float conf_thres, float iou_thres, int max_det, int max_nms, int cap,
+                                      const float* letterbox, float* dets, int* ndets, int* keep_idx, int* cand_count, void* ws, size_t ws_bytes,
+                                      y7t_stream stream, const y7t_nms_opts* opts) {
     Y7T_ARG_CHECK(letterbox && dets && ndets && keep_idx && ws);
     Y7T_ARG_CHECK(head == nullptr || (ny && nx && strides && anchors));
     Y7T_ARG_CHECK(nl >= 1 && nl <= 4 && na >= 1 && na <= 3 && no >= 6 && B >= 1 && cap >= 64 && max_det >= 1 && max_nms >= 1);
@@ -256,6 +264,31 @@ extern "C" int y7t_det_postprocess(const float* const* head, const int* ny, cons
     a.max_det = max_det; a.max_nms = max_nms < cap ? max_nms : cap; a.cap = cap;
     a.letterbox_dev = letterbox; a.dets = dets; a.ndets = ndets; a.keep_idx = keep_idx; a.count_out = cand_count;
     a.ws = ws; a.ws_bytes = ws_bytes;
+    if (opts) {      // every refusal before the first launch: nothing is written
+        static_assert(sizeof(a.class_mask) == sizeof(opts->class_mask), "Y7TPostArgs::class_mask is y7t_nms_opts::class_mask");
+        const int nc = no - 5;
+        a.agnostic = opts->agnostic != 0;
+        a.multi_label = opts->multi_label != 0 && nc > 1;      // multi_label &= nc > 1 (general.py:624)
+        a.filter_classes = opts->filter_classes != 0;
+        if (a.multi_label && !head) {
+            y7t_set_error("postprocess: multi_label needs the per-class scores, which the fused Detect epilogues do not store (they keep the best class): "
+                          "run the forward without the fused decode and pass the head tensors");
+            return Y7T_E_STATE;
+        }
+        if (a.filter_classes && nc > 32 * Y7T_NMS_MASK_WORDS) {
+            y7t_set_error("postprocess: a class filter over nc = %d classes (the mask holds %d)", nc, 32 * Y7T_NMS_MASK_WORDS);
+            return Y7T_E_ARG;
+        }
+        if (a.multi_label) {
+            long long rows = 0;
+            for (int l = 0; l < nl; ++l) rows += (long long)na * ny[l] * nx[l];
+            if (rows * nc > 0x7fffffffll) {      // the rank sort's key carries row * nc + class in its 32 low bits, and count[b] (an int) can reach rows * nc
+                y7t_set_error("postprocess: multi_label over %lld rows x %d classes does not fit the sort key and the candidate counter", rows, nc);
+                return Y7T_E_ARG;
+            }
+        }
+        for (int w = 0; w < Y7T_NMS_MASK_WORDS; ++w) a.class_mask[w] = a.filter_classes ? opts->class_mask[w] : 0u;
+    }
     return y7t_post_run(a, (hipStream_t)stream);
 }
 

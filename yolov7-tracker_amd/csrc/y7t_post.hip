@@ -6,7 +6,8 @@
 //   * max-pool k x k (SPPCSPC's 5/9/13 as a 5-cascade, models/common.py:271-278; MP 2x2/s2, SP, common.py:30-45)
 //   * Detect decode (models/yolo.py:39-57) fused with the candidate filter of non_max_suppression
 //     (utils/general.py:607-665), rank sort by confidence, class-offset bitmask NMS with torchvision's greedy
-//     semantics (general.py:676-682), top-300, scale_coords + clip + round (general.py:319-340, tracker/track.py:234-244)
+//     semantics (general.py:676-682), top-300, scale_coords + clip + round (general.py:319-340, tracker/track.py:234-244);
+//     with y7t_nms_opts: the multi-label form of the decode pass (general.py:654-656), the class filter (:662-663) and the agnostic offset (:677) in the rank sort
 #include "y7t_common.h"
 #include <stdlib.h>
 #include "y7t_det.h"
@@ -409,7 +410,83 @@ __global__ void __launch_bounds__(256) k_decode_filter(const DecodeArgs a, int l
     }
 }
 
+// multi_label (general.py:654-656): `i, j = (x[:, 5:] > conf_thres).nonzero().T` -- every class of a row with obj > conf_thres whose obj * cls confidence passes the
+// threshold is a candidate of its own, with the row's box and the row's index in cidx.  A sibling of k_decode_filter, not a branch in its class loop.
+// A row that passes with k classes takes its k slots with ONE reservation, and the reservations of a wave go out as one atomic per image the wave touches (one, unless
+// the wave straddles two images): the lanes' k are summed by an inclusive scan over the wave, the first lane of the image adds the total to count[b] and every lane
+// takes base + (its prefix).  At the low thresholds multi_label is evaluated with (conf 0.001) nearly every lane of every wave passes, and they all add to the SAME
+// word -- count[b], one image at batch 1 -- where per-lane atomics of one address serialise; one add per wave is a 64th of that chain.
+// The loop is uniform over the workgroup (whole strips of 256 rows, `live` masks the tail), so the scan's cross-lane reads run with every lane active.
+// Slot order inside a row is class ascending; cap cuts a reservation that straddles it: the slots below cap are written, the others are not.
+__global__ void __launch_bounds__(256) k_decode_filter_ml(const DecodeArgs a, int level) {
+    const DecodeLevel L = a.lv[level];
+    const int per_img = a.na * L.ny * L.nx;
+    const long long tot = (long long)a.B * per_img;
+    const int nc = a.no - 5;
+    const int lane = threadIdx.x & 63;
+    for (long long t0 = blockIdx.x * (long long)blockDim.x; t0 < tot; t0 += (long long)gridDim.x * blockDim.x) {
+        const long long t = t0 + threadIdx.x;
+        const bool live = t < tot;
+        const int b = live ? (int)(t / per_img) : -1, r = live ? (int)(t - (long long)b * per_img) : 0;
+        const int x = r % L.nx, an = (r / L.nx) % a.na, y = r / (L.nx * a.na);
+        const float* p = L.p + ((((size_t)(live ? b : 0) * L.ny + y) * L.nx + x) * a.na + an) * a.no;
+        float obj = 0.f;
+        int k = 0;
+        if (live) {
+            obj = sigmoidf_(p[4]);
+            if (obj > a.conf_thres)                               // xc = prediction[..., 4] > conf_thres
+                for (int c = 0; c < nc; ++c) k += (sigmoidf_(p[5 + c]) * obj > a.conf_thres) ? 1 : 0;      // x[:, 5:] *= x[:, 4:5]; (x[:, 5:] > conf_thres)
+        }
+        int slot = 0;
+        unsigned long long pend = __ballot(k > 0);
+        while (pend) {                                            // (uniform: one round per image among the wave's passing rows)
+            const int src = __ffsll((long long)pend) - 1;
+            const int bb = __shfl(b, src);
+            const bool mine = k > 0 && b == bb;
+            int incl = mine ? k : 0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int v = __shfl_up(incl, d);
+                if (lane >= d) incl += v;
+            }
+            const int total = __shfl(incl, 63);
+            int base = 0;
+            if (lane == src) base = atomicAdd(a.count + bb, total);
+            base = __shfl(base, src);
+            if (mine) slot = base + incl - k;
+            pend &= ~__ballot(mine);
+        }
+        if (k == 0 || slot >= a.cap) continue;
+        const float sx = sigmoidf_(p[0]), sy = sigmoidf_(p[1]), sw = sigmoidf_(p[2]), sh = sigmoidf_(p[3]);
+        const float cx = (sx * 2.f - 0.5f + (float)x) * L.stride, cy = (sy * 2.f - 0.5f + (float)y) * L.stride;
+        const float w = (sw * 2.f) * (sw * 2.f) * L.aw[an], h = (sh * 2.f) * (sh * 2.f) * L.ah[an];
+        const float x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2;      // xywh2xyxy
+        const int row = L.row0 + (an * L.ny + y) * L.nx + x;
+        const int end = slot + k < a.cap ? slot + k : a.cap;
+        for (int c = 0; c < nc && slot < end; ++c) {              // the same expression as the count above: the same k classes, in class order
+            const float s = sigmoidf_(p[5 + c]) * obj;
+            if (!(s > a.conf_thres)) continue;
+            const size_t o = (size_t)b * a.cap + slot;
+            float* bo = a.cbox + o * 4;
+            bo[0] = x1; bo[1] = y1; bo[2] = x2; bo[3] = y2;
+            a.cscore[o] = s;
+            a.ccls[o] = (float)c;
+            a.cidx[o] = row;
+            ++slot;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ rank sort
+// what y7t_nms_opts adds to the rank sort, by value.  The candidate arrays are never filtered: a candidate whose class is not in the mask gets key 0 like an empty
+// slot -- it outranks nothing, takes no rank, and is not counted in nsorted -- so another call on the same candidates with another mask gives its own answer.
+struct SortOpts {
+    unsigned mask[8];     // class c passes iff bit c % 32 of mask[c / 32]
+    int filter;           // classes is not None
+    int agnostic;         // class offset 0 (general.py:677)
+    int nc_key;           // multi_label: the candidates of a row share cidx, the key's low word is row * nc_key + class; 0: the row alone
+};
+
 // rank by (score desc, row index asc); scatter class-offset boxes (x[:, :4] + cls*4096) into sorted order
 __global__ void __launch_bounds__(256) k_rank_sort(const float* __restrict__ cbox, const float* __restrict__ cscore, const float* __restrict__ ccls,
                                                    const int* __restrict__ cidx, const int* __restrict__ count, int cap, int max_nms,
@@ -451,6 +528,74 @@ __global__ void __launch_bounds__(256) k_rank_sort(const float* __restrict__ cbo
     }
     if (i < n && rank < max_nms) {
         const float off = ccls[(size_t)b * cap + i] * 4096.f;
+        const float* bo = cbox + ((size_t)b * cap + i) * 4;
+        float* so = sbox + ((size_t)b * mcap + rank) * 4;
+        so[0] = bo[0] + off; so[1] = bo[1] + off; so[2] = bo[2] + off; so[3] = bo[3] + off;
+        sorder[(size_t)b * mcap + rank] = i;
+    }
+}
+
+// k_rank_sort with y7t_nms_opts: the class mask, (row, class) keys, the agnostic offset.  A sibling, so that the tracking path's kernel above stays the code that was
+// measured; the ranking loop is the same.  What differs: key_of (a masked-out candidate is key 0; multi_label keys carry row * nc + class), nsorted -- the number of
+// candidates that PASSED the mask: block 0 of an image counts the non-zero keys it stages through LDS, every candidate's key passes through exactly one of its
+// threads -- and the scatter, which skips key 0 and leaves the class offset out when agnostic.
+__global__ void __launch_bounds__(256) k_rank_sort_opts(const float* __restrict__ cbox, const float* __restrict__ cscore, const float* __restrict__ ccls,
+                                                        const int* __restrict__ cidx, const int* __restrict__ count, int cap, int max_nms,
+                                                        float* __restrict__ sbox, int* __restrict__ sorder, int* __restrict__ nsorted, int mcap, const SortOpts so_) {
+    __shared__ unsigned long long sk[256];
+    __shared__ int s_passed;
+    const int b = blockIdx.y;
+    int n = count[b]; if (n > cap) n = cap;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0 && n == 0) nsorted[b] = 0;      // (an image without candidates: block 0 leaves below; with candidates it publishes the number that passed the mask at its end)
+    if (blockIdx.x * 256 >= n) return;
+    const float* sc = cscore + (size_t)b * cap;
+    const float* cl = ccls + (size_t)b * cap;
+    const int* ix = cidx + (size_t)b * cap;
+    const unsigned kmul = so_.nc_key ? (unsigned)so_.nc_key : 1u;
+    auto key_of = [&](int j) -> unsigned long long {
+        const float v = sc[j];
+        if (!(v > 0.f)) return 0ull;
+        unsigned low = (unsigned)ix[j];
+        if (so_.filter || so_.nc_key) {
+            const int c = (int)cl[j];
+            if (so_.filter) {
+                unsigned w = 0u;      // mask[c / 32] as a chain of selects: the mask stays in scalar registers (a divergent index would move it to scratch)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) w = (c >> 5) == q ? so_.mask[q] : w;
+                if (!((w >> (c & 31)) & 1u)) return 0ull;
+            }
+            low = low * kmul + (so_.nc_key ? (unsigned)c : 0u);
+        }
+        return ((unsigned long long)__builtin_bit_cast(unsigned, v) << 32) | (unsigned long long)(0xFFFFFFFFu - low);
+    };
+    const unsigned long long my_k = i < n ? key_of(i) : 0ull;
+    int rank = 0, passed = 0;
+    unsigned long long nxt = (int)threadIdx.x < n ? key_of(threadIdx.x) : 0ull;
+    for (int base = 0; base < n; base += 256) {
+        __syncthreads();
+        sk[threadIdx.x] = nxt;
+        passed += nxt != 0ull;
+        __syncthreads();
+        const int jn = base + 256 + threadIdx.x;
+        nxt = jn < n ? key_of(jn) : 0ull;
+        const int lim = (n - base) < 256 ? (n - base) : 256;
+        if (lim == 256) {
+#pragma unroll 8
+            for (int t = 0; t < 256; ++t) rank += sk[t] > my_k;
+        } else {
+            for (int t = 0; t < lim; ++t) rank += sk[t] > my_k;
+        }
+    }
+    if (blockIdx.x == 0) {      // (uniform over the workgroup)
+        if (threadIdx.x == 0) s_passed = 0;
+        __syncthreads();
+        if (passed) atomicAdd(&s_passed, passed);
+        __syncthreads();
+        if (threadIdx.x == 0) nsorted[b] = s_passed < max_nms ? s_passed : max_nms;
+    }
+    if (i < n && my_k != 0ull && rank < max_nms) {
+        const float off = so_.agnostic ? 0.f : cl[i] * 4096.f;
         const float* bo = cbox + ((size_t)b * cap + i) * 4;
         float* so = sbox + ((size_t)b * mcap + rank) * 4;
         so[0] = bo[0] + off; so[1] = bo[1] + off; so[2] = bo[2] + off; so[3] = bo[3] + off;
@@ -671,10 +816,19 @@ int y7t_post_run(const Y7TPostArgs& a, hipStream_t s) {
     for (int l = 0; l < a.nl && !a.predecoded; ++l) {
         const long long tot = (long long)B * a.na * a.ny[l] * a.nx[l];
         int blocks = (int)((tot + 255) / 256); if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(k_decode_filter, dim3(blocks), dim3(256), 0, s, d, l);
+        if (a.multi_label) hipLaunchKernelGGL(k_decode_filter_ml, dim3(blocks), dim3(256), 0, s, d, l);
+        else hipLaunchKernelGGL(k_decode_filter, dim3(blocks), dim3(256), 0, s, d, l);
         Y7T_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_rank_sort, dim3((cap + 255) / 256, B), dim3(256), 0, s, cbox, cscore, ccls, cidx, count, cap, a.max_nms, sbox, sorder, nsorted, (int)mcap);
+    if (a.agnostic || a.multi_label || a.filter_classes) {
+        SortOpts so;
+        for (int w = 0; w < 8; ++w) so.mask[w] = a.class_mask[w];
+        so.filter = a.filter_classes; so.agnostic = a.agnostic; so.nc_key = a.multi_label ? a.no - 5 : 0;
+        hipLaunchKernelGGL(k_rank_sort_opts, dim3((cap + 255) / 256, B), dim3(256), 0, s, cbox, cscore, ccls, cidx, count, cap, a.max_nms, sbox, sorder, nsorted,
+                           (int)mcap, so);
+    } else {
+        hipLaunchKernelGGL(k_rank_sort, dim3((cap + 255) / 256, B), dim3(256), 0, s, cbox, cscore, ccls, cidx, count, cap, a.max_nms, sbox, sorder, nsorted, (int)mcap);
+    }
     Y7T_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_nms_keep, dim3(B), dim3(256), (size_t)a.max_det * 6 * sizeof(float), s, sbox, nsorted, sorder, cbox, cscore, ccls, cap, (int)mcap,
                        a.iou_thres, a.max_det, lb, a.dets, a.ndets, a.keep_idx);

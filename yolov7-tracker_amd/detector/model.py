@@ -417,8 +417,9 @@ class Detector:
     def __call__(self, img, augment=False):
         return (self.forward(img),)
 
-    def postprocess(self, out, conf_thres=0.01, iou_thres=0.45, ori_shapes=None):
+    def postprocess(self, out, conf_thres=0.01, iou_thres=0.45, ori_shapes=None, classes=None, agnostic=False, multi_label=False):
         """decode + NMS + scale_coords + round on the device.  ori_shapes: list of (H0, W0) per image (None: no rescale).
+        classes / agnostic / multi_label: as in non_max_suppression (utils/general.py:607); multi_label needs a forward without fuse_decode.
         -> (dets (B, 300, 6) float32 device tensor, ndets (B,) int32 device tensor); asynchronous."""
         p, B = self.plan, out.B
         H, W = out.img_shape
@@ -437,13 +438,20 @@ class Detector:
             if abs(float(conf_thres) - float(out.fused)) > 1e-12:
                 raise ValueError("this forward fused the Detect decode with conf_thres=%g; post-processing it with %g needs a plain forward"
                                  % (out.fused, conf_thres))
+            if multi_label and p.det["no"] > 6:
+                raise ValueError("multi_label needs the per-class scores, which a fused forward does not store (its Detect epilogues keep the best class): "
+                                 "run the forward without fuse_decode")
             head_ptrs = None            # the candidates are already in ps.ws
         else:
             head_ptrs = out.staged[1] if getattr(out, "staged", None) is not None else p.head_ptrs
-        _lib.check(self._L.y7t_det_postprocess(head_ptrs, p.ny, p.nx, p.strides, p.anchors, len(p.heads), p.det["na"], p.det["no"], B,
-                                               float(conf_thres), float(iou_thres), MAX_DET, MAX_NMS, self.max_cand, _lib.ptr(p.lb),
-                                               _lib.ptr(ps.dets), _lib.ptr(ps.ndets), _lib.ptr(ps.keep), _lib.ptr(ps.cand), _lib.ptr(ps.ws),
-                                               ps.ws.numel(), _lib.stream_ptr()))
+        opts = _lib.nms_opts(classes, agnostic, multi_label)
+        args = (head_ptrs, p.ny, p.nx, p.strides, p.anchors, len(p.heads), p.det["na"], p.det["no"], B, float(conf_thres), float(iou_thres), MAX_DET, MAX_NMS,
+                self.max_cand, _lib.ptr(p.lb), _lib.ptr(ps.dets), _lib.ptr(ps.ndets), _lib.ptr(ps.keep), _lib.ptr(ps.cand), _lib.ptr(ps.ws), ps.ws.numel(),
+                _lib.stream_ptr())
+        if opts is None:
+            _lib.check(self._L.y7t_det_postprocess(*args))
+        else:
+            _lib.check(self._L.y7t_det_postprocess_ex(*args, ctypes.byref(opts)))
         return ps.dets, ps.ndets
 
     def candidate_arrays(self, pset=0, B=None):
@@ -512,15 +520,17 @@ class Detector:
 
 
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, labels=()):
-    """utils/general.py:607-695 for the arguments the tracking path uses (classes=None, agnostic=False, multi_label=False).
-    prediction: the HeadOutput returned by Detector.  -> list of (n, 6) tensors [xyxy, conf, cls], score-descending."""
+    """utils/general.py:607-695 on the device; `labels` (autolabelling apriori) is not implemented.
+    prediction: the HeadOutput returned by Detector.  classes: None or a list of class ids kept before the max_nms cut; agnostic: NMS across classes;
+    multi_label: one candidate per (anchor, class) above conf_thres -- it needs the per-class scores, i.e. a forward without fuse_decode (ValueError otherwise).
+    -> list of (n, 6) tensors [xyxy, conf, cls], score-descending (equal scores: anchor row, then class, ascending)."""
     if not isinstance(prediction, HeadOutput):
         raise TypeError("non_max_suppression expects the detector's HeadOutput (the decoded tensor is only materialised on request: "
                         "HeadOutput.decoded())")
-    if classes is not None or agnostic or multi_label or labels:
-        raise NotImplementedError("only the tracking path's NMS arguments are implemented")
+    if labels:
+        raise NotImplementedError("labels (autolabelling apriori boxes) are not implemented")
     det = prediction.det
-    dets, nd = det.postprocess(prediction, conf_thres, iou_thres, None)
+    dets, nd = det.postprocess(prediction, conf_thres, iou_thres, None, classes=classes, agnostic=agnostic, multi_label=multi_label)
     nd = nd.cpu().numpy()
     det.check_overflow()
     out = []

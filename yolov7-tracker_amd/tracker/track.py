@@ -37,9 +37,10 @@ timer = Timer()
 seq_fps = []
 
 
-def post_process_v7(out, img_size, ori_img_size, conf_thres=0.01, all_images=False):
-    """track.py:234-244 (the reference keeps image 0 of the batch; all_images=True returns the list for every image)"""
-    res = non_max_suppression(out, conf_thres=conf_thres)
+def post_process_v7(out, img_size, ori_img_size, conf_thres=0.01, all_images=False, classes=None, agnostic=False):
+    """track.py:234-244 (the reference keeps image 0 of the batch; all_images=True returns the list for every image).
+    classes / agnostic (extension): non_max_suppression's arguments of the same names, as detect.py:79 passes --classes / --agnostic-nms"""
+    res = non_max_suppression(out, conf_thres=conf_thres, classes=classes, agnostic=agnostic)
     for o in res:
         o[:, :4] = scale_coords(img_size, o[:, :4], ori_img_size, ratio_pad=None).round()
     return res if all_images else res[0]
@@ -145,7 +146,7 @@ def main(opts, cfgs):
                     head, lb_size = model.forward_frames(imgs0, img_size=opts.img_size, fuse_decode=0.01)
                 else:
                     head, lb_size = model.forward(imgs.cuda(), fuse_decode=0.01), imgs.shape[2:]
-                outs = post_process_v7(head, img_size=lb_size, ori_img_size=imgs0.shape[1:], all_images=True)
+                outs = post_process_v7(head, img_size=lb_size, ori_img_size=imgs0.shape[1:], all_images=True, classes=opts.classes, agnostic=opts.agnostic_nms)
             for k in range(nb):
                 if k:
                     timer.tic()
@@ -250,6 +251,9 @@ def build_parser():
     parser.add_argument('--synthetic_seqs', type=int, default=1)
     parser.add_argument('--results_root', type=str, default='./tracker/results')
     parser.add_argument('--yolo_root', type=str, default='./', help="(extension) where ./<dataset>/test.txt of --data_format yolo lives (the reference: the working directory)")
+    # the NMS arguments of the reference's detect.py:166-167 (non_max_suppression applies them before its max_nms / max_det cuts)
+    parser.add_argument('--classes', nargs='+', type=int, default=None, help='(extension) filter by class: --classes 0, or --classes 0 2 3')
+    parser.add_argument('--agnostic_nms', action='store_true', help='(extension) class-agnostic NMS')
     return parser
 
 
