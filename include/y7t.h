@@ -167,6 +167,30 @@ int y7t_ecc_align(const void* tmpl_plane, const void* img_plane, int h, int w, i
 int y7t_ecc_iteration_sums_f64(const void* tmpl_plane, const void* img_plane, int h, int w, double theta, double tx, double ty, void* workspace,
                                double* sums_out21_f64, y7t_stream stream);
 
+/* Camera-motion ESTIMATION from features: GMC.applyFeaures of the reference (tracker/botsort.py:111-235: FAST corners, ORB descriptors, Hamming 2-NN matching, three
+ * filters, estimateAffinePartial2D with RANSAC) as a specification of our own in exact arithmetic -- DESIGN.md section 4 "GMC / features" states it and what is not
+ * claimed against OpenCV.  A STATE holds the keypoints and descriptors of one frame in DEVICE memory (16-byte aligned, y7t_orb_state_bytes(max_keypoints) bytes):
+ * a 32-byte header of ints {n, corners found, truncated, h, w}, max_keypoints descriptors of 32 bytes, max_keypoints keypoints {x, y} (ints, row-major order).
+ * y7t_orb_workspace_bytes: bytes of DEVICE workspace (16-byte aligned, no initialisation) that an extraction and an estimate on h x w planes need.
+ * y7t_orb_extract_u8: bgr = (H, W, 3) uint8 frame (device); dets = n_dets rows of 6 float32 as y7t_tracker_step takes them (device; tlbr first, full-resolution
+ *   pixels; n_dets == 0: no boxes), whose boxes are masked out as botsort.py:129-132 does -> state_out for the plane of (H / downscale) x (W / downscale) pixels,
+ *   both sides in 63 .. 8192; at most max_keypoints (1 .. 65536) keypoints, the first in row-major order (the header's `truncated` tells).  Seven launches.
+ * y7t_orb_estimate: warp_out6_f64 (6 doubles, device, row-major 2x3 [[a, -b, tx], [b, a, ty]], translation in full-resolution pixels) = the similarity from the
+ *   previous frame's coordinates to the current one's, the identity unless the flag is 0; status_out6_f64 (6 doubles, device) = {n_prev, n_cur, good matches,
+ *   inliers, Y7T_ORB_* flag, truncated (bit 0 current, bit 1 previous state)}.  h, w, downscale, max_keypoints: as the two states were extracted.  Four launches;
+ *   nothing is read back, the counts stay in device memory; the same inputs give the same bits on every run.
+ * y7t_orb_tap_layout (tests): the byte offsets in the workspace of {plane, FAST scores, kept corners, smoothed plane (h x w uint8 each), row counts, row offsets
+ *   (h ints each), moments (max_keypoints x {m10, m01} ints), best-two matches (x {j1, d1, j2, d2} ints), good matches (x {px, py, cx, cy} ints), the estimate's
+ *   header (ints {good, flag, survivors of the first two filters, winning hypothesis, inliers}), inlier counts of the 2000 hypotheses (ints)} and the total. */
+enum { Y7T_ORB_STATUS_OK = 0, Y7T_ORB_STATUS_NO_MATCHES = 1, Y7T_ORB_STATUS_NOT_ENOUGH = 2, Y7T_ORB_STATUS_NO_MODEL = 3 };
+int y7t_orb_workspace_bytes(int h, int w, int max_keypoints, size_t* out);
+int y7t_orb_state_bytes(int max_keypoints, size_t* out);
+int y7t_orb_extract_u8(const uint8_t* bgr, int H, int W, int downscale, const float* dets, int n_dets, int max_keypoints, void* workspace, void* state_out,
+                       y7t_stream stream);
+int y7t_orb_estimate(const void* prev_state, const void* cur_state, int h, int w, int downscale, int max_keypoints, void* workspace, double* warp_out6_f64,
+                     double* status_out6_f64, y7t_stream stream);
+int y7t_orb_tap_layout(int h, int w, int max_keypoints, size_t* offsets12);
+
 /* C-BIoU (tracker/c_biou_tracker.py:212-353, tracker kind Y7T_TRACKER_C_BIOU; the Kalman kind of y7t_tracker_init is ignored): no motion model, three
  * IoU associations of buffered boxes.  Same pool blob, same layout and the same entry points as SORT / ByteTrack: y7t_tracker_step, y7t_tracker_step_frames,
  * y7t_tracker_step_batch (a batch may mix C-BIoU pools with the others).  A slot's `cov` storage holds the track's last 6 boxes, its two motion states and

@@ -75,6 +75,11 @@ SIGNATURES = {
     "y7t_ecc_workspace_bytes": (c_int, [c_int, c_int, c_void_p]),
     "y7t_ecc_align": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "y7t_ecc_iteration_sums_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "y7t_orb_workspace_bytes": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "y7t_orb_state_bytes": (c_int, [c_int, c_void_p]),
+    "y7t_orb_extract_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "y7t_orb_estimate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y7t_orb_tap_layout": (c_int, [c_int, c_int, c_int, c_void_p]),
     "y7t_tracker_layout": (c_int, [c_int, c_int, c_void_p, c_int]),
     "y7t_tracker_field_name": (ctypes.c_char_p, [c_int]),
     "y7t_det_create": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),

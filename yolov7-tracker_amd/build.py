@@ -23,7 +23,8 @@ OBJ_ABLATE = os.path.join(HERE, "build_ablate")
 LIB_ABLATE = os.path.join(LIBDIR, "liby7t_ablate.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-# -ffp-contract=off: the float64 tracker arithmetic must round like the plain-C oracle
+# -ffp-contract=off: the float64 tracker arithmetic must round like the plain-C oracle; y7t_ecc.hip and y7t_orb.hip (every .hip of csrc/ is a source) are compared
+# bit for bit with g++ builds of their headers and rely on it too
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(os.path.dirname(HERE), "include")]
 # per-file overrides (the conv kernels want contraction: fp32 accumulate of fp16 products)

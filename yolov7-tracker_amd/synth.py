@@ -240,6 +240,69 @@ def make_camera_frames(n_frames=8, size=1280, seq_idx=0, rot=0.004, shift=1.5):
     return np.stack(frames), warps
 
 
+# ---- frames with corners (the input of the feature-based estimate, GMC('features')): the sinusoid scene is too smooth for FAST at threshold 20 ----
+def corner_scene(x, y, extent, seq_idx=0, per_kilopixel=3.0, sides=(6.0, 28.0)):
+    """-> (..., 3) float64 BGR levels at the (real-valued) scene coordinates x, y: camera_background with a seeded set of rotated rectangles of random grey levels
+    painted over it in order, their centres spread over extent = (H, W) and a margin around it, `per_kilopixel` of them per 1000 square pixels, half-sides drawn
+    from sides / 2.  A point is inside a rectangle by an analytic test at its own coordinates, so a frame under any warp is EVALUATED, never interpolated."""
+    H, W = float(extent[0]), float(extent[1])
+    rng = np.random.default_rng(BASE_SEED + 7700 + seq_idx)
+    margin = 0.06 * max(H, W)
+    n = max(4, int(round(per_kilopixel * (H + 2 * margin) * (W + 2 * margin) / 1000.0)))
+    cx, cy = rng.uniform(-margin, W + margin, n), rng.uniform(-margin, H + margin, n)
+    a, b = rng.uniform(sides[0] / 2, sides[1] / 2, n), rng.uniform(sides[0] / 2, sides[1] / 2, n)
+    phi = rng.uniform(0.0, np.pi, n)
+    grey = rng.uniform(20.0, 235.0, n)
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    out = camera_background(x, y, seq_idx)
+    # a pixel grid under an affine pose (every caller's): a rectangle is tested only in a window of rows and columns that contains it -- the same levels, sooner
+    inv = None
+    if x.ndim == 2 and x.shape[0] > 1 and x.shape[1] > 1:
+        R, C = x.shape[0] - 1, x.shape[1] - 1
+        o = np.array([x[0, 0], y[0, 0]])
+        M = np.array([[(x[0, C] - o[0]) / C, (x[R, 0] - o[0]) / R], [(y[0, C] - o[1]) / C, (y[R, 0] - o[1]) / R]])      # scene = M (col, row) + o
+        if abs(np.linalg.det(M)) > 1e-9 and np.allclose(M @ [C, R] + o, [x[R, C], y[R, C]], rtol=0, atol=1e-6):
+            inv = np.linalg.inv(M)
+    for k in range(n):
+        xs, ys, dst = x, y, out
+        if inv is not None:
+            c, r = inv @ (np.array([cx[k], cy[k]]) - o)
+            reach = np.hypot(a[k], b[k]) * np.abs(inv).sum(1) + 2.0
+            c0, c1, r0, r1 = int(max(0, c - reach[0])), int(min(x.shape[1], c + reach[0] + 1)), int(max(0, r - reach[1])), int(min(x.shape[0], r + reach[1] + 1))
+            if c0 >= c1 or r0 >= r1:
+                continue
+            xs, ys, dst = x[r0:r1, c0:c1], y[r0:r1, c0:c1], out[r0:r1, c0:c1]
+        dx, dy = xs - cx[k], ys - cy[k]
+        inside = (np.abs(dx * np.cos(phi[k]) + dy * np.sin(phi[k])) <= a[k]) & (np.abs(dy * np.cos(phi[k]) - dx * np.sin(phi[k])) <= b[k])
+        dst[inside] = grey[k]
+    return out
+
+
+def make_corner_frames(n_frames=8, size=1280, seq_idx=0, rot=0.004, shift=1.5, steps=None, **scene):
+    """make_camera_frames over corner_scene: -> (frames uint8 (n_frames, H, W, 3) BGR, warps float64 (n_frames, 2, 3)), warps[t] the PLANTED motion from frame
+    t - 1 to frame t in full-resolution pixels, warps[0] the identity.  steps: the (theta, tx, ty) of frames 1 .. n_frames - 1, instead of the seeded draw."""
+    H, W = (size, size) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    rng = np.random.default_rng(BASE_SEED + 7800 + seq_idx)
+    pose = np.eye(3)                                                             # frame pixel -> scene
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    frames, warps = [], np.zeros((n_frames, 2, 3))
+    for t in range(n_frames):
+        if t == 0:
+            step = np.eye(3)
+        elif steps is not None:
+            step = np.vstack([euclidean_warp(*steps[t - 1]), [0.0, 0.0, 1.0]])
+        else:
+            th = float(np.clip(rng.normal(0.0, rot), -2 * rot, 2 * rot))
+            tr = np.clip(rng.normal(0.0, shift, 2), -2 * shift, 2 * shift)
+            step = np.vstack([euclidean_warp(th, tr[0], tr[1]), [0.0, 0.0, 1.0]])
+        warps[t] = step[:2]
+        pose = pose @ np.linalg.inv(step)                                        # pose_t = pose_{t-1} W_t^-1
+        sx = pose[0, 0] * xs + pose[0, 1] * ys + pose[0, 2]
+        sy = pose[1, 0] * xs + pose[1, 1] * ys + pose[1, 2]
+        frames.append(np.clip(np.floor(corner_scene(sx, sy, (H, W), seq_idx, **scene) + 0.5), 0, 255).astype(np.uint8))
+    return np.stack(frames), warps
+
+
 # ---- the Deep Hungarian Net of DeepMOT (/root/reference/tracker/deepmot.py:10-140, class Munkrs) ----
 def dhn_tensor_shapes():
     """-> [(name, shape)]: the 38 tensors of Munkrs(element_dim=1, hidden_dim=256, target_size=1, bidirectional=True).state_dict(), in its order

@@ -11,8 +11,8 @@ App = 0.5 * cosine distance of the track's smoothed vector and the detection's, 
 pass.  Features enter at `get_feature(tlbrs, ori_img) -> (N, D)` (botsort.py:291-311: the DeepSORT Net on 128 x 64 crops; tracker/appearance.py) for the
 detections with score >= conf_thresh.
 
-The camera-motion ESTIMATION (`GMC`, botsort.py:13-248) is tracker/gmc.py for method 'ecc' (findTransformECC as HIP kernels); ORB / SIFT matching and the
-GMC files stay out of scope.  The 2x3 warp of a frame is an input: `update(dets, img, warp=H)` or `tracker.gmc = callable(raw_frame, detections) -> H`, e.g. `GMC('ecc').apply_device`, whose (6,) float64
+The camera-motion ESTIMATION (`GMC`, botsort.py:13-248) is tracker/gmc.py for method 'ecc' (findTransformECC as HIP kernels) and for method 'features' (applyFeaures, botsort.py:111-235,
+under a specification of our own); OpenCV's own ORB / SIFT and the GMC files stay out of scope.  The 2x3 warp of a frame is an input: `update(dets, img, warp=H)` or `tracker.gmc = callable(raw_frame, detections) -> H`, e.g. `GMC('ecc').apply_device`, whose (6,) float64
 DEVICE tensor goes to the step without a host copy.  `tracker.gmc` is None by default, as before."""
 import numpy as np
 import torch

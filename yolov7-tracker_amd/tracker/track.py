@@ -7,7 +7,7 @@ device-resident SORT / ByteTrack trackers.
 
 Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / arch name for state-dict checkpoints),
 --nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch,
---gmc {none,ecc} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
+--gmc {none,ecc,features} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
 --botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
 """
 import argparse
@@ -114,7 +114,7 @@ def main(opts, cfgs):
         print(f'--------------tracking seq {seq}--------------')
         if synthetic:
             loader = tracker_dataloader.SyntheticLoader(opts.synthetic_frames, opts.synthetic_objs, opts.img_size, si,
-                                                        device_preprocess=opts.device_preprocess, moving_camera=opts.gmc != 'none')
+                                                        device_preprocess=opts.device_preprocess, moving_camera='corners' if opts.gmc == 'features' else opts.gmc != 'none')
         else:
             # track.py:126: the sequence folder ('origin') or the path file every sequence is filtered out of ('yolo')
             path = os.path.join(DATA_ROOT, seq) if opts.data_format == 'origin' else os.path.join(getattr(opts, 'yolo_root', './'), opts.dataset, 'test.txt')
@@ -125,9 +125,9 @@ def main(opts, cfgs):
         data_loader = torch.utils.data.DataLoader(loader, batch_size=max(1, opts.batch))
         # (extension) --botsort_reid: BoTSORT's use_apperance_model, which the reference hard-codes to False (botsort.py:276)
         tracker = TRACKER_DICT[opts.tracker](opts, frame_rate=30, gamma=opts.gamma, **({'use_apperance_model': True} if botsort_reid else {}))
-        if opts.gmc == 'ecc':      # (extension) estimate the camera motion on the device; one estimator per sequence, like the reference's per-tracker GMC
+        if opts.gmc in ('ecc', 'features'):      # (extension) estimate the camera motion on the device; one estimator per sequence, like the reference's per-tracker GMC
             from .gmc import GMC
-            estimator = GMC('ecc', faithful=bool(opts.gmc_faithful))
+            estimator = GMC(opts.gmc, faithful=bool(opts.gmc_faithful))
             if opts.tracker == 'strongsort':
                 tracker.ECC = estimator
             else:
@@ -229,8 +229,9 @@ def build_parser():
     parser.add_argument('--kalman_format', type=str, default='default', help='use what kind of Kalman, default, naive, strongsort or bot-sort like')
     parser.add_argument('--batch', type=int, default=1, help='(extension) frames per detector forward; the tracker still steps frame by frame')
     parser.add_argument('--device_preprocess', action='store_true', help='(extension) letterbox raw frames on the GPU instead of in the loader')
-    parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc'],
-                        help='(extension) camera-motion estimate for strongsort / botsort: ecc = findTransformECC on the device (tracker/gmc.py)')
+    parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc', 'features'],
+                        help='(extension) camera-motion estimate for strongsort / botsort on the device (tracker/gmc.py): ecc = findTransformECC, '
+                             'features = FAST corners, rotated BRIEF, Hamming matching and RANSAC (the applyFeaures path the reference runs as orb)')
     parser.add_argument('--botsort_reid', action='store_true',
                         help="(extension) --tracker botsort with its appearance branch (use_apperance_model, off in the reference): IoU-gated cosine fusion with "
                              "--reid_model_path features")

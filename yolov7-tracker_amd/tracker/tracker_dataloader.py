@@ -114,7 +114,9 @@ class SyntheticLoader(torch.utils.data.Dataset):
     def __init__(self, n_frames, n_obj, size, seq_idx, device_preprocess=False, moving_camera=False):
         from .. import synth
         self.device_preprocess = device_preprocess
-        if moving_camera:      # a textured scene under a moving camera (synth.make_camera_frames): what a camera-motion estimate needs to see
+        if moving_camera == 'corners':      # ... with corners (synth.make_corner_frames): what the feature-based estimate needs to see
+            self.frames, self.warps = synth.make_corner_frames(n_frames, size, seq_idx)
+        elif moving_camera:      # a textured scene under a moving camera (synth.make_camera_frames): what a camera-motion estimate needs to see
             self.frames, self.warps = synth.make_camera_frames(n_frames, size, seq_idx)
         else:
             self.frames = synth.make_frames(n_frames, n_obj, size, seq_idx)
