@@ -22,10 +22,10 @@ _SO_ECC = os.path.join(_HERE, "liby7t_hostsim_ecc.so")
 FAST_BYTES = 131072
 
 
-def _build(so, src, deps, defs=(), force=False):
-    """compile tests/_hostsim/<src> into <so> when it is older than the source or one of the csrc headers `deps`"""
+def _build(so, src, defs=(), force=False):
+    """compile tests/_hostsim/<src> into <so> when it is older than the source or any header of csrc/ (a hand-kept list would miss a new one)"""
     src = os.path.join(_HERE, src)
-    deps = [src] + [os.path.join(_CSRC, h) for h in deps]
+    deps = [src] + [os.path.join(_CSRC, h) for h in os.listdir(_CSRC) if h.endswith(".h")]
     if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"] + list(defs) + ["-o", so, src])
     return so
@@ -37,14 +37,13 @@ def reset_fast_bytes():
 
 
 def build_ecc(force=False):
-    return _build(_SO_ECC, "y7t_hostsim_ecc.cpp", ["y7t_ecc.h"], force=force)
+    return _build(_SO_ECC, "y7t_hostsim_ecc.cpp", force=force)
 
 
 def build(force=False):
     """both libraries -> the path of the tracker programs'"""
     build_ecc(force)
-    _build(_SO, "y7t_hostsim.cpp", ["y7t_track_core.h", "y7t_track_step.h", "y7t_track_cbiou.h", "y7t_track_deepsort.h", "y7t_track_strongsort.h", "y7t_track_deepmot.h"],
-           _DEFS, force)
+    _build(_SO, "y7t_hostsim.cpp", _DEFS, force)
     reset_fast_bytes()
     return _SO
 

@@ -12,8 +12,7 @@ _lib = None
 
 
 def build(force=False):
-    return hs._build(_SO, "y7t_hostsim_botsort_reid.cpp", ["y7t_track_core.h", "y7t_track_step.h", "y7t_track_cbiou.h", "y7t_track_deepsort.h", "y7t_track_strongsort.h",
-                                                          "y7t_track_botsort_reid.h"], force=force)
+    return hs._build(_SO, "y7t_hostsim_botsort_reid.cpp", force=force)
 
 
 def lib():

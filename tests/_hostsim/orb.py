@@ -12,7 +12,7 @@ _lib = None
 
 
 def build_orb(force=False):
-    return _build(_SO_ORB, "y7t_hostsim_orb.cpp", ["y7t_orb.h", "y7t_orb_pattern.h", "y7t_ecc.h"], force=force)
+    return _build(_SO_ORB, "y7t_hostsim_orb.cpp", force=force)
 
 
 def lib():

@@ -3,7 +3,7 @@
 //
 // Restates /root/reference/tracker/botsort.py:313-493 (BoTSORT.update with use_apperance_model = True), tracker/matching.py:84-103 (embedding_distance, metric
 // 'cosine'), :165-178 (cal_cosine_distance), tracker/basetrack.py:296-339 (STrack.re_activate / update: the float32 moving average of the normalised features,
-// y7t_ss_ema of y7t_track_strongsort.h -- the same code), tracker/botsort.py:250-269 (multi_gmc).
+// y7t_ss_store_pending of y7t_track_strongsort.h -- StrongSORT's store, the same code), tracker/botsort.py:250-269 (multi_gmc).
 //
 // The fused cost of the first (0.9) and the unconfirmed (0.7) association is
 //     App = 0.5 * (1 - cos);  App[IoU_dist > theta_iou] = 1;  App[App > theta_emb] = 1;  cost = min(IoU_dist, App)
@@ -20,17 +20,20 @@
 //   * re_activate keeps the vector, update runs the float32 moving average.
 #pragma once
 #include "y7t_track_step.h"
-#include "y7t_track_strongsort.h"      // Y7TSsHdr / Y7TSs, y7t_ss_queue*, y7t_ss_store_pending (the float32 moving-average store), Y7T_NO_CONTRACT
+#include "y7t_track_strongsort.h"      // Y7TSsHdr / Y7TSs and y7t_ss_store_pending: the one-vector store with its float32 moving average is StrongSORT's, on this state's memory
+#include "y7t_track_pend.h"            // the queue of vectors to store
+#include "y7t_np_arith.h"        // numpy's float64 row norms and dot products, Y7T_NO_CONTRACT
 
 // (Y7T_BOTSORT_REID = 8: y7t_track_core.h)
 
 // feature state of one tracker: caller-owned device memory next to the track-pool blob.  The header BEGINS with StrongSORT's (the status word at byte 20, the
-// pending-store counter: y7t_ss_queue and y7t_ss_store_pending run on it as they are); its spare words carry this program's own values:
+// pending-store counter: the queue of y7t_track_pend.h and y7t_ss_store_pending run on it as they are); its spare words carry this program's own values:
 //   ss.pad1 = the frame's count of cosines evaluated, ss.gamma = theta_iou, ss.pad2 = theta_emb
 struct Y7TBrHdr { Y7TSsHdr ss; int n_emb /* evaluated pairs of the frame that theta_emb sent to 1 */, hcap, h_nb /* columns of the association the table holds */, pad; };
 #define Y7T_BR_NDOTS(h) ((h)->ss.pad1)
 #define Y7T_BR_THETA_IOU(h) ((h)->ss.gamma)
 #define Y7T_BR_THETA_EMB(h) ((h)->ss.pad2)
+static_assert(sizeof(Y7TBrHdr) == sizeof(Y7TSsHdr) + 4 * 4, "the feature-state header of BoT-SORT with ReID: n_dots at byte 28, theta_iou at 32, theta_emb at 40, its four own ints from 48");
 #define Y7T_BR_PPD 2      // pending stores per detection of the capacity: a detection left after the first association may update an unconfirmed track AND start a track
 enum { Y7T_BR_ERR_VEC = 4 /* a zero-norm or non-finite appearance vector: the frame was not stepped */, Y7T_BR_ERR_PAIRS = 32 /* more pairs at or under theta_iou than the table holds */ };
 struct Y7TBrLayout { size_t vec, pend, tn, dn, hkey, hlist, hval, total; };
@@ -74,107 +77,14 @@ Y7T_FN Y7TBr y7t_br_bind(void* blob) {
 Y7T_FN void y7t_br_init(const Y7TExec& ex, void* blob, int cap_t, int cap_d, int dim, double theta_iou, double theta_emb) {
     Y7TBrHdr* h = (Y7TBrHdr*)blob;
     if (ex.tid == 0) {
-        h->ss.magic = 0x59374252; h->ss.dim = dim; h->ss.one = 1; h->ss.cap_t = cap_t; h->ss.cap_d = cap_d; h->ss.status = 0; h->ss.n_pend = 0;
+        h->ss.magic = 0x59374252; h->ss.dim = dim; h->ss.budget = 1; h->ss.cap_t = cap_t; h->ss.cap_d = cap_d; h->ss.status = 0; h->ss.n_pend = 0;
         Y7T_BR_NDOTS(h) = 0; Y7T_BR_THETA_IOU(h) = theta_iou; Y7T_BR_THETA_EMB(h) = theta_emb;
         h->n_emb = 0; h->hcap = y7t_br_hcap(cap_t, cap_d); h->h_nb = 0; h->pad = 0;
     }
     y7t_sync(ex);
 }
 
-// ---------------------------------------------------------------------------------------------
-// The float64 arithmetic of 1. - cal_cosine_distance(mat1, mat2) as numpy evaluates it, pinned in the text itself:
-//   * mat / np.linalg.norm(mat, axis=1, keepdims=True): sqrt(np.add.reduce(x * x, axis=1)) -- the products are exact (float32 values), the reduction is numpy's
-//     PAIRWISE sum: blocks of at most 128 elements, eight interleaved accumulators a block combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the block's tail added one
-//     by one, a longer run halved (the left half rounded down to a multiple of 8) and the halves' sums added; then one division per element;
-//   * np.dot(mat1, mat2.T): dgemm.  What OpenBLAS's dgemm does depends on the shapes (its small-matrix kernels, gemv for a single row or column, 256-deep k blocks for
-//     large ones), so no one chain is numpy's; this program takes ONE sequential FMA chain over k = 0 .. dim-1 per pair, which meets np.dot to a few units of
-//     the last place of 1 (DESIGN.md section 4 records the largest difference measured, and the goldens keep both thresholds that far from every pair).
-// ---------------------------------------------------------------------------------------------
-template <class LeafFn>
-Y7T_FN double y7t_br_pairwise(int n, LeafFn leaf /* (offset, count <= 128) -> that block's sum */) {
-    int so[20], sn[20], sd[20], sp = 1, vd[20], vp = 0;
-    double vv[20];
-    so[0] = 0; sn[0] = n; sd[0] = 0;
-    while (sp > 0) {      // depth-first, left to right; two finished neighbours of one depth are their parent's halves
-        --sp;
-        const int o = so[sp], m = sn[sp], d = sd[sp];
-        if (m > 128) {
-            int n2 = m / 2;
-            n2 -= n2 % 8;
-            so[sp] = o + n2; sn[sp] = m - n2; sd[sp] = d + 1; ++sp;
-            so[sp] = o; sn[sp] = n2; sd[sp] = d + 1; ++sp;
-            continue;
-        }
-        double v = leaf(o, m);
-        int dd = d;
-        while (vp > 0 && vd[vp - 1] == dd) { v = vv[vp - 1] + v; --vp; --dd; }
-        vv[vp] = v; vd[vp] = dd; ++vp;
-    }
-    return vv[0];
-}
-Y7T_FN double y7t_br_sq(float x) { return (double)x * (double)x; }      // (exact: 24-bit factors)
-Y7T_FN double y7t_br_leaf(const float* x, int o, int m) {
-    double res = 0.0;
-    int i = 0;
-    if (m >= 8) {
-        double r[8];
-        for (int k = 0; k < 8; ++k) r[k] = y7t_br_sq(x[o + k]);
-        for (i = 8; i < m - (m % 8); i += 8)
-            for (int k = 0; k < 8; ++k) r[k] = r[k] + y7t_br_sq(x[o + i + k]);
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    }
-    for (; i < m; ++i) res = res + y7t_br_sq(x[o + i]);
-    return res;
-}
-Y7T_FN double y7t_br_norm(const float* x, int dim) { return sqrt(y7t_br_pairwise(dim, [&](int o, int m) { return y7t_br_leaf(x, o, m); })); }
-Y7T_FN bool y7t_br_norm_ok(double nrm) { return nrm > 0.0 && nrm < HUGE_VAL; }      // (false for NaN: an element that is not finite makes the sum so)
-// out[k] = x[k] / |x| -> is the row usable (a zero or non-finite norm gives the reference NaN costs, which it hands to lapjv)
-Y7T_FN bool y7t_br_normalize(const float* x, int dim, double* out) {
-    const double nrm = y7t_br_norm(x, dim);
-    for (int k = 0; k < dim; ++k) out[k] = (double)x[k] / nrm;
-    return y7t_br_norm_ok(nrm);
-}
-#if Y7T_DEVICE
-// the same by one wave: lanes 0..7 own a block's eight accumulators, every lane leaves with the block's sum; the divisions a lane per element
-Y7T_FN bool y7t_br_normalize_wave(const float* x, int dim, double* out, int lane) {
-    const double sum = y7t_br_pairwise(dim, [&](int o, int m) {
-        double res = 0.0;
-        int i = 0;
-        if (m >= 8) {
-            const int k = lane & 7;
-            double r = y7t_br_sq(x[o + k]);
-            for (i = 8; i < m - (m % 8); i += 8) r = r + y7t_br_sq(x[o + i + k]);
-            const double r0 = __shfl(r, 0, 64), r1 = __shfl(r, 1, 64), r2 = __shfl(r, 2, 64), r3 = __shfl(r, 3, 64);
-            const double r4 = __shfl(r, 4, 64), r5 = __shfl(r, 5, 64), r6 = __shfl(r, 6, 64), r7 = __shfl(r, 7, 64);
-            res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        }
-        for (; i < m; ++i) res = res + y7t_br_sq(x[o + i]);
-        return res;
-    });
-    const double nrm = sqrt(sum);
-    for (int k = lane; k < dim; k += 64) out[k] = (double)x[k] / nrm;
-    return y7t_br_norm_ok(nrm);
-}
-#endif
-// np.dot of two normalised rows: one chain, the contraction stated (fma), whatever the build's -ffp-contract says
-Y7T_FN double y7t_br_dotstep(double s, double a, double b) { return __builtin_fma(a, b, s); }
-Y7T_FN double y7t_br_dot(const double* a, const double* b, int dim) {
-    double s = 0.0;
-    int k = 0;
-#if Y7T_DEVICE
-    if ((dim & 1) == 0 && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0) {      // 16-byte loads, a 128-byte line of each row at a time: the same chain
-        for (; k + 16 <= dim; k += 16) {
-            double2 av[8], bv[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { av[q] = *(const double2*)(a + k + 2 * q); bv[q] = *(const double2*)(b + k + 2 * q); }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { s = y7t_br_dotstep(s, av[q].x, bv[q].x); s = y7t_br_dotstep(s, av[q].y, bv[q].y); }
-        }
-    }
-#endif
-    for (; k < dim; ++k) s = y7t_br_dotstep(s, a[k], b[k]);
-    return s;
-}
+// 1. - cal_cosine_distance(mat1, mat2) in float64: y7t_np_arith.h -- the rows divided by their np.linalg.norm (y7t_np_normalize_f64), np.dot as one FMA chain per pair (y7t_np_dot_f64)
 // 0.5 * (1. - dot): a rounded difference, an exact halving
 Y7T_FN double y7t_br_half(double dot) {
     Y7T_NO_CONTRACT
@@ -188,11 +98,12 @@ Y7T_FN double y7t_br_gate(double iou_d, double half, double theta_iou, double th
     if (app > theta_emb) app = 1.0;
     return (iou_d <= app || iou_d != iou_d) ? iou_d : app;
 }
-// the cosine of two float32 rows on its own (tests): norm[] holds 2 * dim doubles
+// np.linalg.norm of one float32 row, and the cosine of two, on their own (tests): norm[] holds 2 * dim doubles
+Y7T_FN double y7t_br_norm(const float* x, int dim) { return y7t_np_norm_f64(x, dim); }
 Y7T_FN double y7t_br_cosine(const float* u, const float* v, int dim, double* norm) {
-    y7t_br_normalize(u, dim, norm);
-    y7t_br_normalize(v, dim, norm + dim);
-    return y7t_br_dot(norm, norm + dim, dim);
+    y7t_np_normalize_f64(u, dim, norm);
+    y7t_np_normalize_f64(v, dim, norm + dim);
+    return y7t_np_dot_f64(norm, norm + dim, dim);
 }
 
 // is detection row j one the reference extracts a feature for (botsort.py:339: score >= det_thresh, compared in float32)?
@@ -225,10 +136,10 @@ Y7T_FN void y7t_br_prepare(const Y7TExec& ex, const Y7TTrk& s, const Y7TBr& f, c
             src = det_feats + (size_t)j * dim; dst = f.dn + (size_t)j * dim;
         }
 #if Y7T_DEVICE
-        const bool ok = y7t_br_normalize_wave(src, dim, dst, lane);
+        const bool ok = y7t_np_wave_normalize_f64(src, dim, dst, lane);
         if (!ok && lane == 0) atomicOr(&f.h->ss.status, Y7T_BR_ERR_VEC);
 #else
-        if (!y7t_br_normalize(src, dim, dst)) f.h->ss.status |= Y7T_BR_ERR_VEC;
+        if (!y7t_np_normalize_f64(src, dim, dst)) f.h->ss.status |= Y7T_BR_ERR_VEC;
 #endif
     }
 }
@@ -300,7 +211,7 @@ Y7T_FN void y7t_br_cosines(const Y7TExec& ex, const Y7TTrk& s, const Y7TBr& f, i
     for (int k = ex.tid; k < cnt; k += ex.nt) {
         const int e = f.hlist[k], key = f.hkey[e];
         const int i = key / nb, j = key - i * nb;
-        const double half = y7t_br_half(y7t_br_dot(f.tn + (size_t)slots[i] * dim, f.dn + (size_t)drows[j] * dim, dim));
+        const double half = y7t_br_half(y7t_np_dot_f64(f.tn + (size_t)slots[i] * dim, f.dn + (size_t)drows[j] * dim, dim));
         f.hval[e] = half;
         gated += half > theta_emb ? 1 : 0;
     }
@@ -382,7 +293,7 @@ Y7T_FN void y7t_tracker_step_botsort_reid(const Y7TExec& ex, void* blob, void* f
     if (cfg.tracker != Y7T_BOTSORT_REID || n < 0 || f.h->ss.cap_t < cfg.cap_t || f.h->ss.cap_d < cfg.cap_d || (f.h->ss.status & Y7T_BR_ERR_VEC)) {
         if (ex.tid == 0) {
             if (cfg.tracker != Y7T_BOTSORT_REID || n < 0) h->status |= Y7T_ERR_KIND;
-            else if (!(f.h->ss.status & Y7T_BR_ERR_VEC)) f.h->ss.status |= Y7T_SS_ERR_CAP;
+            else if (!(f.h->ss.status & Y7T_BR_ERR_VEC)) f.h->ss.status |= Y7T_PEND_ERR_CAP;
             else f.h->ss.n_pend = 0;      // (the store launch behind the step finds nothing queued)
             if (out_count) *out_count = 0;
         }
@@ -453,7 +364,7 @@ Y7T_FN void y7t_tracker_step_botsort_reid(const Y7TExec& ex, void* blob, void* f
         else y7t_assoc_br(ex, s, f, nA, nD, th, la, ld);
         Y7T_PROF(h, 3 + 2 * ph);
         y7t_apply_matches(ex, s, la, nA, ld, dets, mode, na, nr);
-        if (ph != 1) y7t_ss_queue_updates<Y7T_BR_PPD>(ex, s, f.ss, la, nA, ld);      // (ph 1: det.has_feature is False -- the track keeps its vector)
+        if (ph != 1) y7t_pend_queue_updates<Y7T_BR_PPD>(ex, s, y7t_pend_of(f.ss), la, nA, ld);      // (ph 1: det.has_feature is False -- the track keeps its vector)
         if (ph == 0) {
             n_left = y7t_compact(ex, n_hi, [&](int j) { return s.ycol[j] < 0; }, s.tmpa, 0);
             for (int k = ex.tid; k < n_left; k += ex.nt) s.left[k] = s.dhi[s.tmpa[k]];
@@ -508,7 +419,7 @@ Y7T_FN void y7t_tracker_step_botsort_reid(const Y7TExec& ex, void* blob, void* f
         }
         y7t_sync(ex);
         // STrack(..., feature=f): features = [f] (the raw vector, basetrack.py:97-103): whatever the slot's previous occupant left is overwritten
-        y7t_ss_queue<Y7T_BR_PPD>(ex, f.ss, made, 0, [&](int k, int& sl, int& row) {
+        y7t_pend_queue<Y7T_BR_PPD>(ex, y7t_pend_of(f.ss), made, 0, [&](int k, int& sl, int& row) {
             sl = s.tmpb[k];
             row = s.left[s.tmpa[k]];
             return true;

@@ -14,6 +14,7 @@
 //   * where the pool or D_high is empty the network is skipped and the (empty) ecu matrix is solved: nothing matches.
 #pragma once
 #include "y7t_track_step.h"
+#include "y7t_np_arith.h"      // Y7T_NO_CONTRACT
 
 // (Y7T_DEEPMOT = 7: y7t_track_core.h)
 enum { Y7T_ERR_DHN_CAP = 32 /* the frame's h x w matrix exceeds the DHN object's workspace */, Y7T_ERR_DHN = 64 /* the network's forward gave up (a bounded spin ran out) */ };
@@ -22,12 +23,6 @@ enum { Y7T_ERR_DHN_CAP = 32 /* the frame's h x w matrix exceeds the DHN object's
 struct Y7TDmFrame { int magic, n, n_pool, n_hi, n_lo, n_unc, net, pad; };      // net: 1 = the network runs on n_pool x n_hi
 #define Y7T_DM_MAGIC 0x59374d31
 
-#if Y7T_DEVICE
-#define Y7T_DM_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define Y7T_DM_NO_CONTRACT
-#endif
-
 // matching.ecu_iou_distance's image term: float((h**2 + w**2)**0.5) of Python ints
 Y7T_FN double y7t_dm_norm_factor(int img_h, int img_w) { return sqrt((double)((long long)img_h * img_h + (long long)img_w * img_w)); }
 
@@ -35,7 +30,7 @@ Y7T_FN double y7t_dm_norm_factor(int img_h, int img_w) { return sqrt((double)((l
 // b: the detection's float32 tlwh.  det_cx = b[0] + 0.5 * b[2] in FLOAT32 (a float32 array and a Python scalar), trk_cx in float64; their difference in float64
 // (a float32 array minus a float64 scalar), squared, summed, sqrt; 1 - exp(-5 d / norm); 0.5 * (ecu + iou)
 Y7T_FN double y7t_dm_ecu_iou(const double* t, const float* b, double iou_d, double norm) {
-    Y7T_DM_NO_CONTRACT
+    Y7T_NO_CONTRACT
     const float hw = 0.5f * b[2], hh = 0.5f * b[3];
     const float dcx = b[0] + hw, dcy = b[1] + hh;
     const double tw = 0.5 * t[2], th = 0.5 * t[3];

@@ -13,12 +13,15 @@
 //     list applied to the unfiltered pool).
 #pragma once
 #include "y7t_track_step.h"
+#include "y7t_track_pend.h"      // the header's first words, the queue of vectors to store
+#include "y7t_np_arith.h"        // the float32 norms and products as numpy / OpenBLAS evaluate them
 
 // (Y7T_DEEPSORT = 3: y7t_track_core.h)
 #define Y7T_PYSET_CAP 8192      // table entries of the emulated CPython set (enough for 1228 unmatched tracks)
 
 // feature state of one DeepSORT tracker: caller-owned device memory next to the track-pool blob
-struct Y7TFeatHdr { int magic, dim, budget, cap_t, cap_d, status, n_pend, pad1; };
+struct Y7TFeatHdr : Y7TPendHdr { int pad1; };      // (status bit 8: the emulated CPython set outgrew its table)
+static_assert(sizeof(Y7TFeatHdr) == 28 + 4, "DeepSORT's feature-state header: the shared words, pad1 at byte 28");
 struct Y7TFeatLayout { size_t ring, nfeat, fpos, app, detn, pend, cmin, cmax, casc_tr, casc_det, u0, tomatch, tmpd, pyset, total; };
 struct Y7TFeat {
     Y7TFeatHdr* h;
@@ -27,8 +30,8 @@ struct Y7TFeat {
     int *nfeat, *fpos;  // [cap_t] stored features, next write position
     float* app;         // [cap_t][cap_d]         nearest_embedding_distance(slot, detection row) of this frame
     float* detn;        // [cap_d][dim]           this frame's detection features, normalised (cal_cosine_distance's mat2)
-    int* pend;          // [cap_d][3]             appearance vectors this frame's step decided to store: (slot, detection row, 1 = update / 0 = new track);
-                        //                        written out after the step by y7t_feat_store_pending (grid-wide: a wave per vector)
+    int* pend;          // [cap_d][3]             appearance vectors this frame's step decided to store: (slot, detection row, 1 = update / 0 = new track), the queue of
+                        //                        y7t_track_pend.h; written out after the step by y7t_feat_store_pending (grid-wide: a wave per vector)
     int *cmin, *cmax;   // [cap_d]                youngest / oldest time_since_update among the live slots whose nearest-embedding distance to the detection
                         //                        passes the appearance test (<= 0.15): reset by y7t_feat_normalize_dets, filled with the distances
     int *casc_tr, *casc_det, *u0;   // [cap_t]    cascade matches in match order (pool index, position in the detection list); unmatched pool indices
@@ -136,112 +139,9 @@ Y7T_FN int y7t_pyset_difference_list(int n, const int* unm, int n_unm, int n_oth
     return cnt;
 }
 
-// ---------------------------------------------------------------------------------------------
-// float32 arithmetic of the reference's appearance cost, as numpy 2.2 / OpenBLAS 0.3.29 (AVX-512 kernels) evaluate it in the environment
-// the golden sequences were recorded in -- the costs of similar objects differ by a few float32 ulps, and the assignment follows them:
-//   * np.linalg.norm(mat, axis=1): x * x rounded to float32, then add.reduce's PAIRWISE sum (numpy/_core/src/umath/loops_utils.h.src:
-//     8 running sums for blocks <= 128, recursive halving above), sqrt;
-//   * np.dot(mat1, mat2.T) (sgemm): one sequential fused-multiply-add chain over k per output;
-//   * np.linalg.norm(vec) of a 1-D feature (STrack.update, basetrack.py:325) = sqrt(sdot(x, x)): OpenBLAS's SkylakeX sdot kernel over the
-//     first n & -32 elements -- four 16-lane accumulators over 64 elements per step (FMA), folded 16 -> 8 lanes, summed
-//     ((a0 + a1) + a2) + a3, halves added, two horizontal adds -- and its driver (kernel/x86_64/sdot.c) for the n & 31 that remain: their
-//     float32 products summed into a DOUBLE, the kernel's float32 sum added in double, one rounding to float32.
-// tests/golden/np_norms.npz holds numpy's own bits of both norms at 18 widths; tests/test_deepsort_feat_cpu.py compares these restatements with them.
-// ---------------------------------------------------------------------------------------------
-Y7T_NOINL float y7t_np_pairwise_sumsq(const float* x, int n) {
-    if (n < 8) {
-        float r = 0.f;
-        for (int i = 0; i < n; ++i) r = r + x[i] * x[i];
-        return r;
-    }
-    if (n <= 128) {
-        float r[8];
-        for (int j = 0; j < 8; ++j) r[j] = x[j] * x[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] = r[j] + x[i + j] * x[i + j];
-        float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res = res + x[i] * x[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return y7t_np_pairwise_sumsq(x, n2) + y7t_np_pairwise_sumsq(x + n2, n - n2);
-}
-
-Y7T_FN float y7t_fmaf(float a, float b, float c) {
-#if Y7T_DEVICE
-    return __builtin_fmaf(a, b, c);
-#else
-    return fmaf(a, b, c);
-#endif
-}
-
-// the driver's tail: `kern` is the kernel's sum of the first n1 = n & -32 elements
-Y7T_FN float y7t_blas_sdot_tail(const float* x, int n1, int n, float kern) {
-    if (n1 == n) return kern;
-    double tail = 0.0;
-    for (int k = n1; k < n; ++k) { const float p = x[k] * x[k]; tail = tail + (double)p; }
-    return (float)(tail + (double)kern);
-}
-
-Y7T_FN float y7t_blas_sdot_self(const float* x, int n) {
-    const int n1 = n & -32, n64 = n1 & ~63;
-    float a5[4][16], a[4][8];
-    for (int v = 0; v < 4; ++v) for (int l = 0; l < 16; ++l) a5[v][l] = 0.f;
-    int i = 0;
-    for (; i < n64; i += 64)
-        for (int v = 0; v < 4; ++v) for (int l = 0; l < 16; ++l) { const float t = x[i + 16 * v + l]; a5[v][l] = y7t_fmaf(t, t, a5[v][l]); }
-    for (int v = 0; v < 4; ++v) for (int l = 0; l < 8; ++l) a[v][l] = a5[v][l] + a5[v][l + 8];
-    for (; i < n1; i += 32)
-        for (int v = 0; v < 4; ++v) for (int l = 0; l < 8; ++l) { const float t = x[i + 8 * v + l]; a[v][l] = y7t_fmaf(t, t, a[v][l]); }
-    float sv[8], hv[4];
-    for (int l = 0; l < 8; ++l) sv[l] = ((a[0][l] + a[1][l]) + a[2][l]) + a[3][l];
-    for (int l = 0; l < 4; ++l) hv[l] = sv[l] + sv[l + 4];
-    const float d = (hv[0] + hv[1]) + (hv[2] + hv[3]);
-    return y7t_blas_sdot_tail(x, n1, n, d);
-}
-
-#if Y7T_DEVICE
-// The same sums with the 64 lanes of a wave sharing one vector (every lane calls; every lane gets the result) -- bit-identical to the serial forms:
-// each partial sum is built from the same operands in the same order, only by different lanes.
-Y7T_FN bool y7t_dim_wave_ok(int dim) { return dim == 128 || dim == 256 || dim == 512 || dim == 1024; }
-
-// y7t_np_pairwise_sumsq of the vector x[i] / div (div = 1: x itself): lane (block, j) owns running sum j of its 128-element block
-Y7T_FN float y7t_wave_pairwise_sumsq(const float* x, int dim, float div, int lane) {
-    const int nblk = dim >> 7, blk = lane >> 3, j = lane & 7;
-    float r = 0.f;
-    if (blk < nblk) {
-        const float* xb = x + blk * 128;
-        const float t0 = xb[j] / div;
-        r = t0 * t0;
-        for (int i = 8; i < 128; i += 8) { const float t = xb[i + j] / div; r = r + t * t; }
-    }
-    r = r + __shfl_xor(r, 1, 64); r = r + __shfl_xor(r, 2, 64); r = r + __shfl_xor(r, 4, 64);      // ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7))
-    for (int m = 1; m < nblk; m <<= 1) r = r + __shfl_xor(r, 8 * m, 64);                          // the recursive halving over blocks
-    return __shfl(r, 0, 64);
-}
-
-// y7t_blas_sdot_self: lane 16 v + l owns accumulator (v, l)
-Y7T_FN float y7t_wave_sdot_self(const float* x, int n, int lane) {
-    const int n1 = n & -32, n64 = n1 & ~63;
-    const int v = lane >> 4, l = lane & 15;
-    float a5 = 0.f;
-    for (int i = 0; i < n64; i += 64) { const float t = x[i + lane]; a5 = y7t_fmaf(t, t, a5); }
-    float a = a5 + __shfl(a5, (lane + 8) & 63, 64);                                             // meaningful on l < 8
-    if (n1 > n64 && l < 8) { const float t = x[n64 + 8 * v + l]; a = y7t_fmaf(t, t, a); }
-    const float a0 = __shfl(a, l & 7, 64), a1 = __shfl(a, 16 + (l & 7), 64), a2 = __shfl(a, 32 + (l & 7), 64), a3 = __shfl(a, 48 + (l & 7), 64);
-    const float sv = ((a0 + a1) + a2) + a3;                                                     // sv[l & 7] on every lane
-    const float hv = sv + __shfl(sv, (lane & 48) + (((l & 7) + 4) & 7), 64);                    // l & 7 < 4: sv[l] + sv[l + 4]
-    const float h0 = __shfl(hv, 0, 64), h1 = __shfl(hv, 1, 64), h2 = __shfl(hv, 2, 64), h3 = __shfl(hv, 3, 64);
-    const float d = (h0 + h1) + (h2 + h3);
-    return y7t_blas_sdot_tail(x, n1, n, d);      // (no wave width has a tail; every lane would walk it alike)
-}
-#endif
-
 // What STrack keeps of an appearance vector, in the form the distance uses it.  STrack stores the raw vector at creation (basetrack.py:97-103) and
 // f / np.linalg.norm(f) on every update (basetrack.py:324-332, 1-D norm = sqrt(sdot)); nearest_embedding_distance then divides every stored row by
-// its np.linalg.norm(axis=1) (pairwise sum) again.  Both divisions happen here, once, when the vector is stored.  Serial (one thread).
+// its np.linalg.norm(axis=1) (pairwise sum) again (y7t_np_arith.h: both norms).  Both divisions happen here, once, when the vector is stored.  Serial (one thread).
 Y7T_FN void y7t_feat_store(float* dst, const float* src, int dim, int update) {
     const float nb = update ? sqrtf(y7t_blas_sdot_self(src, dim)) : 1.0f;
     for (int d = 0; d < dim; ++d) dst[d] = src[d] / nb;
@@ -249,24 +149,10 @@ Y7T_FN void y7t_feat_store(float* dst, const float* src, int dim, int update) {
     for (int d = 0; d < dim; ++d) dst[d] = dst[d] / na;
 }
 
-// Queue the vectors a step decides to store; y7t_feat_store_pending writes them after the step (nothing in the step reads the ring: this frame's
-// distances were taken before it).  A detection row is stored at most once per frame and a slot receives at most one vector.
-template <class PairFn>
-Y7T_FN void y7t_feat_store_many(const Y7TExec& ex, const Y7TFeat& f, int count, int update, PairFn pair /* (i, slot&, detection row&) -> bool */) {
-    for (int i = ex.tid; i < count; i += ex.nt) {
-        int sl, row;
-        if (!pair(i, sl, row)) continue;
-        const int k = Y7T_FETCH_ADD(&f.h->n_pend, 1);
-        if (k < f.h->cap_d) { f.pend[3 * k] = sl; f.pend[3 * k + 1] = row; f.pend[3 * k + 2] = update; }
-        else f.h->status |= 16;
-    }
-    y7t_sync(ex);
-}
-
-// write the queued vectors (ex may span a whole grid: on the device a wave per vector); resets the queue
+// write the queued vectors (ex may span a whole grid: on the device a wave per vector); the next step zeroes the queue
 Y7T_FN void y7t_feat_store_pending(const Y7TExec& ex, const Y7TFeat& f, const float* det_feats) {
     const int dim = f.h->dim, budget = f.h->budget;
-    const int count = f.h->n_pend < f.h->cap_d ? f.h->n_pend : f.h->cap_d;
+    const int count = y7t_pend_count<1>(y7t_pend_of(f));
 #if Y7T_DEVICE
     if (y7t_dim_wave_ok(dim) && (ex.nt & 63) == 0) {
         const int lane = ex.tid & 63;
@@ -275,8 +161,8 @@ Y7T_FN void y7t_feat_store_pending(const Y7TExec& ex, const Y7TFeat& f, const fl
             const float* b = det_feats + (size_t)f.pend[3 * i + 1] * dim;
             const int pos = update ? f.fpos[sl] : 0;
             float* dst = f.ring + ((size_t)sl * budget + pos) * dim;
-            const float nb = update ? sqrtf(y7t_wave_sdot_self(b, dim, lane)) : 1.0f;
-            const float na = sqrtf(y7t_wave_pairwise_sumsq(b, dim, nb, lane));
+            const float nb = update ? sqrtf(y7t_blas_wave_sdot_self(b, dim, lane)) : 1.0f;
+            const float na = sqrtf(y7t_np_wave_pairwise_sumsq(b, dim, nb, lane));
             for (int d = lane; d < dim; d += 64) dst[d] = (b[d] / nb) / na;
             if (lane == 0) {
                 if (update) { f.fpos[sl] = (pos + 1 == budget) ? 0 : pos + 1; if (f.nfeat[sl] < budget) f.nfeat[sl] += 1; }
@@ -304,7 +190,7 @@ Y7T_FN void y7t_feat_normalize_dets(const Y7TExec& ex, const Y7TFeat& f, const f
         const int lane = ex.tid & 63;
         for (int j = ex.tid >> 6; j < n; j += ex.nt >> 6) {
             const float* b = det_feats + (size_t)j * dim;
-            const float nb = sqrtf(y7t_wave_pairwise_sumsq(b, dim, 1.0f, lane));
+            const float nb = sqrtf(y7t_np_wave_pairwise_sumsq(b, dim, 1.0f, lane));
             float* o = f.detn + (size_t)j * dim;
             for (int d = lane; d < dim; d += 64) o[d] = b[d] / nb;
         }
@@ -342,33 +228,6 @@ Y7T_FN void y7t_embed_slot(const Y7TExec& ex, const Y7TFeat& f, int slot, int n,
         row[j] = best;
         if ((double)best <= 0.15) { Y7T_ATOMIC_MIN_I(f.cmin + j, tsu); Y7T_ATOMIC_MAX(f.cmax + j, tsu); }
     }
-    y7t_sync(ex);
-}
-
-// STrack.update's feature bookkeeping (basetrack.py:324-332, use_avg_of_feature = False) for the rows of `tracks` that apply_matches
-// UPDATED (tmpa[i] == 1): features.append(f / np.linalg.norm(f)); features = features[-budget:]
-Y7T_FN void y7t_ds_append_features(const Y7TExec& ex, const Y7TTrk& s, const Y7TFeat& f, const int* tracks, int na, const int* dets,
-                                   const float* det_feats) {
-    y7t_feat_store_many(ex, f, na, 1, [&](int i, int& sl, int& row) {
-        if (s.xrow[i] < 0 || s.tmpa[i] != 1) return false;
-        sl = tracks[i];
-        row = dets[s.xrow[i]];
-        return true;
-    });
-}
-
-// linear_assignment(cost, thresh) on a cost matrix already in s.cost (na x nb, row stride nb) -> s.xrow / s.ycol
-Y7T_FN void y7t_assign_on_cost(const Y7TExec& ex, const Y7TTrk& s, int na, int nb, double thresh, bool literal = false) {
-    Y7TLap L;
-    L.nr = na; L.nc = nb; L.ld = nb; L.n = na + nb; L.half = thresh / 2.0; L.prof = nullptr;
-    const size_t ws = y7t_al(y7t_lap_ws_bytes(L.n));
-    void* lapws = s.lapws;
-    if (ex.fast && ws <= ex.fast_bytes) lapws = ex.fast;
-    L.c = s.cost;
-    y7t_lap_bind(L, lapws, L.n);
-    if (literal || y7t_lap_solve_sap(ex, L)) y7t_lap_solve_literal(ex, L);      // ties: lapjv's own order decides
-    for (int i = ex.tid; i < na; i += ex.nt) s.xrow[i] = (L.x[i] >= nb) ? -1 : L.x[i];
-    for (int j = ex.tid; j < nb; j += ex.nt) s.ycol[j] = (L.y[j] >= na) ? -1 : L.y[j];
     y7t_sync(ex);
 }
 
@@ -566,7 +425,7 @@ Y7T_FN void y7t_tracker_step_deepsort(const Y7TExec& ex, void* blob, void* fblob
     y7t_sync(ex);
     int na, nr;
     y7t_apply_matches(ex, s, s.rem, nm, s.dhi, dets, 0, na, nr);
-    y7t_ds_append_features(ex, s, f, s.rem, nm, s.dhi, det_feats);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.rem, nm, s.dhi);      // STrack.update, use_avg_of_feature = False: features.append(f / np.linalg.norm(f)); features = features[-budget:]
     Y7T_PROF(h, 4);
     // ---- Step 3: IoU association of the still-Tracked leftovers (in u0 order) with the leftover detections, thresh 0.5 ----
     const int n_t0 = y7t_compact(ex, n_u0, [&](int k) { return s.state[s.pool[f.u0[k]]] == Y7T_TRACKED; }, s.tmpa, 0);
@@ -578,7 +437,7 @@ Y7T_FN void y7t_tracker_step_deepsort(const Y7TExec& ex, void* blob, void* fblob
     y7t_sync(ex);
     y7t_assoc(ex, s, n_t0, n_to, 0.5);
     y7t_apply_matches(ex, s, s.rem, n_t0, s.left, dets, 0, na, nr);
-    y7t_ds_append_features(ex, s, f, s.rem, n_t0, s.left, det_feats);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.rem, n_t0, s.left);
     Y7T_PROF(h, 5);
     // u_det1 (detection rows), in column order
     const int n_d1 = y7t_compact(ex, n_to, [&](int c) { return s.ycol[c] < 0; }, s.tmpb, 0);
@@ -599,7 +458,7 @@ Y7T_FN void y7t_tracker_step_deepsort(const Y7TExec& ex, void* blob, void* fblob
     y7t_sync(ex);
     y7t_assoc(ex, s, n_unc, n_d1, 0.9);
     y7t_apply_matches(ex, s, s.unconf, n_unc, s.dlo, dets, 2, na, nr);
-    y7t_ds_append_features(ex, s, f, s.unconf, n_unc, s.dlo, det_feats);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.unconf, n_unc, s.dlo);
     Y7T_PROF(h, 6);
     {
         const int n_rm = y7t_compact(ex, n_unc, [&](int i) { return s.xrow[i] < 0; }, s.tmpa, 0);
@@ -644,7 +503,7 @@ Y7T_FN void y7t_tracker_step_deepsort(const Y7TExec& ex, void* blob, void* fblob
         }
         y7t_sync(ex);
         // STrack(..., feature=f): features = [f] (the raw vector, basetrack.py:97-103)
-        y7t_feat_store_many(ex, f, made, 0, [&](int k, int& sl, int& row) {
+        y7t_pend_queue(ex, y7t_pend_of(f), made, 0, [&](int k, int& sl, int& row) {
             sl = s.tmpb[k];
             row = s.dlo[s.tmpa[k]];
             return true;

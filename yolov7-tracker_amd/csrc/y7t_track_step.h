@@ -819,6 +819,20 @@ Y7T_FN void y7t_assoc(const Y7TExec& ex, const Y7TTrk& s, int na, int nb, double
     y7t_sync(ex);
 }
 
+// linear_assignment(cost, thresh) on a cost matrix already in s.cost (na x nb, row stride nb) -> s.xrow / s.ycol
+Y7T_FN void y7t_assign_on_cost(const Y7TExec& ex, const Y7TTrk& s, int na, int nb, double thresh, bool literal = false) {
+    Y7TLap L;
+    L.nr = na; L.nc = nb; L.ld = nb; L.n = na + nb; L.half = thresh / 2.0; L.prof = nullptr;
+    const size_t ws = y7t_al(y7t_lap_ws_bytes(L.n));
+    void* lapws = s.lapws;
+    if (ex.fast && ws <= ex.fast_bytes) lapws = ex.fast;
+    L.c = s.cost;
+    y7t_lap_bind(L, lapws, L.n);
+    if (literal || y7t_lap_solve_sap(ex, L)) y7t_lap_solve_literal(ex, L);      // ties: lapjv's own order decides
+    for (int i = ex.tid; i < na; i += ex.nt) s.xrow[i] = (L.x[i] >= nb) ? -1 : L.x[i];
+    for (int j = ex.tid; j < nb; j += ex.nt) s.ycol[j] = (L.y[j] >= na) ? -1 : L.y[j];
+    y7t_sync(ex);
+}
 
 // gather tlbr of listed pool tracks
 Y7T_FN void y7t_gather_track_tlbr(const Y7TExec& ex, const Y7TTrk& s, const int* list, int n) {

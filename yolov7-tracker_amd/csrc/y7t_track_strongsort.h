@@ -14,23 +14,23 @@
 //     the first update mixes that raw vector with a normalised one.
 #pragma once
 #include "y7t_track_step.h"
-#include "y7t_track_deepsort.h"      // y7t_blas_sdot_self (np.linalg.norm of a float32 vector), y7t_assign_on_cost
+#include "y7t_track_pend.h"      // the header's first words, the queue of vectors to store
+#include "y7t_np_arith.h"        // scipy's cdist, OpenBLAS's sdot, the float32 mix, Y7T_NO_CONTRACT
 
 // (Y7T_STRONGSORT = 6: y7t_track_core.h)
 #ifndef Y7T_SS_STAT
 #define Y7T_SS_STAT(k) do { } while (0)      // (the CPU test build counts which solver path a fused association took)
 #endif
 
-// feature state of one StrongSORT tracker: caller-owned device memory next to the track-pool blob.  The first six words are laid out as in Y7TFeatHdr
-// (the status word at byte 20)
-struct Y7TSsHdr { int magic, dim, one, cap_t, cap_d, status, n_pend, pad1; double gamma; double pad2; };
-enum { Y7T_SS_ERR_CAP = 2 /* the feature state is smaller than the pool it is stepped with */, Y7T_SS_ERR_PEND = 16 /* more queued vectors than detections */ };
+// feature state of one StrongSORT tracker: caller-owned device memory next to the track-pool blob
+struct Y7TSsHdr : Y7TPendHdr { int pad1; double gamma; double pad2; };
+static_assert(sizeof(Y7TSsHdr) == 28 + 4 + 8 + 8, "StrongSORT's feature-state header: the shared words, pad1 at byte 28, gamma at 32, pad2 at 40");
 struct Y7TSsLayout { size_t vec, app, pend, total; };
 struct Y7TSs {
     Y7TSsHdr* h;
     float* vec;         // [cap_t][dim]      STrack.features[-1] of the slot's track: the raw vector of its first detection, later the smoothed one
     double* app;        // [cap_t][cap_d]    embedding_distance(slot, detection row) of this frame (rows: the slots of the tracked / lost lists; columns: rows above det_thresh)
-    int* pend;          // [cap_d][3]        vectors this frame's step decided to store: (slot, detection row, 1 = update (moving average) / 0 = new track (raw copy))
+    int* pend;          // [cap_d][3]        vectors this frame's step decided to store: (slot, detection row, 1 = update (moving average) / 0 = new track (raw copy)): the queue of y7t_track_pend.h
 };
 
 Y7T_HD Y7TSsLayout y7t_ss_layout(int cap_t, int cap_d, int dim) {
@@ -55,34 +55,8 @@ Y7T_FN Y7TSs y7t_ss_bind(void* blob) {
 
 Y7T_FN void y7t_ss_init(const Y7TExec& ex, void* blob, int cap_t, int cap_d, int dim, double gamma) {
     Y7TSsHdr* h = (Y7TSsHdr*)blob;
-    if (ex.tid == 0) { h->magic = 0x59375331; h->dim = dim; h->one = 1; h->cap_t = cap_t; h->cap_d = cap_d; h->status = 0; h->n_pend = 0; h->pad1 = 0; h->gamma = gamma; h->pad2 = 0.0; }
+    if (ex.tid == 0) { h->magic = 0x59375331; h->dim = dim; h->budget = 1; h->cap_t = cap_t; h->cap_d = cap_d; h->status = 0; h->n_pend = 0; h->pad1 = 0; h->gamma = gamma; h->pad2 = 0.0; }
     y7t_sync(ex);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The float64 arithmetic of matching.embedding_distance(..., 'euclidean') as scipy 1.15 evaluates it: per pair ONE sequential chain over
-// k = 0 .. dim-1 of d = u[k] - v[k]; s += d * d (the product rounded before the sum: no FMA), then sqrt, then np.maximum(0.0, .).  Both operands
-// are float32 values cast to float64 (the casts are exact).  Contraction is switched off in the text itself, so no compiler flag decides the rounding.
-// ---------------------------------------------------------------------------------------------
-#if Y7T_DEVICE
-#define Y7T_NO_CONTRACT _Pragma("clang fp contract(off)")      // (hipcc contracts a * b + c by default; the library's build switches that off for this file as well)
-#else
-#define Y7T_NO_CONTRACT                                        // (the CPU build is compiled with -ffp-contract=off)
-#endif
-Y7T_FN double y7t_ss_sqstep(double s, float u, float v) {
-    Y7T_NO_CONTRACT
-    const double d = (double)u - (double)v;
-    const double p = d * d;
-    return s + p;
-}
-Y7T_FN double y7t_ss_root(double s) {
-    const double d = sqrt(s);      // (correctly rounded on the device as on the host)
-    return d > 0.0 ? d : (d != d ? d : 0.0);      // np.maximum(0.0, d): NaN passes
-}
-Y7T_FN double y7t_ss_dist(const float* u, const float* v, int dim) {
-    double s = 0.0;
-    for (int k = 0; k < dim; ++k) s = y7t_ss_sqstep(s, u[k], v[k]);
-    return y7t_ss_root(s);
 }
 
 // Dist_mat = self.gamma * IoU_dist + (1. - self.gamma) * Apperance_dist (strongsort.py:152): two rounded products and one sum
@@ -96,7 +70,10 @@ Y7T_FN double y7t_ss_fuse(double gamma, double iou_d, double app_d) {
 // is detection row j one the reference extracts a feature for (strongsort.py:110: conf > det_thresh, compared in float32)?  Every other row of det_feats is never read
 Y7T_FN bool y7t_ss_row_used(const float* dets, int j, float det_t) { return dets[6 * (size_t)j + 4] > det_t; }
 
-// the slot behind rank r of the frame's appearance rows: the tracked list, then the lost list (a slot in both lists is computed twice, to the same value)
+// matching.embedding_distance(..., 'euclidean') of one pair: scipy's cdist (y7t_np_arith.h)
+Y7T_FN double y7t_ss_dist(const float* u, const float* v, int dim) { return y7t_scipy_euclidean(u, v, dim); }
+
+// the slot behind rank r of a frame's appearance rows: the tracked list, then the lost list (a slot in both lists is computed twice, to the same value)
 Y7T_FN int y7t_ss_live_slot(const Y7TTrk& s, int n_tracked, int r) { return r < n_tracked ? s.tracked[r] : s.lost[r - n_tracked]; }
 
 // Plain form of the frame's appearance matrix (a lane per pair): every slot of the tracked / lost lists x every detection row above det_thresh.
@@ -115,60 +92,32 @@ Y7T_FN void y7t_ss_appearance_plain(const Y7TExec& ex, const Y7TTrk& s, const Y7
     }
 }
 
-// ---------------------------------------------------------------------------------------------
+// The one-vector store: vec[cap_t][dim] holds STrack.features[-1] of the slot's track -- the raw vector of its first detection, later the smoothed one.
 // STrack.update's feature bookkeeping (basetrack.py:324-332, use_avg_of_feature = True), all float32 as numpy evaluates it:
 //   f = raw / np.linalg.norm(raw);  smooth = 0.9 * features[-1] + (1 - 0.9) * f;  smooth /= np.linalg.norm(smooth)
-// the scalars round to float32(0.9) / float32(0.1), the products and the sum are three separate roundings, np.linalg.norm of a float32 vector
-// is sqrt(sdot(x, x)) (y7t_ss_sdot_self).  In place on the slot's vector.  Serial (one thread).
-// ---------------------------------------------------------------------------------------------
-Y7T_FN float y7t_ss_mix(float prev, float f) {
-    Y7T_NO_CONTRACT
-    const float a = 0.9f * prev, b = 0.1f * f;
-    return a + b;
-}
-// sdot(x, x) for any n: y7t_blas_sdot_self (y7t_track_deepsort.h) -- OpenBLAS's kernel over the first n & -32 elements and its driver's double-precision tail;
-// one restatement for both trackers.
-Y7T_FN float y7t_ss_sdot_self(const float* x, int n) { return y7t_blas_sdot_self(x, n); }
+// (y7t_np_mix_f32; np.linalg.norm of a float32 vector is sqrt(sdot(x, x)): y7t_blas_sdot_self).  In place on the slot's vector.  Serial (one thread).
 Y7T_FN void y7t_ss_ema(float* vec, const float* raw, int dim) {
-    const float nb = sqrtf(y7t_ss_sdot_self(raw, dim));
-    for (int d = 0; d < dim; ++d) vec[d] = y7t_ss_mix(vec[d], raw[d] / nb);
-    const float ns = sqrtf(y7t_ss_sdot_self(vec, dim));
+    const float nb = sqrtf(y7t_blas_sdot_self(raw, dim));
+    for (int d = 0; d < dim; ++d) vec[d] = y7t_np_mix_f32(vec[d], raw[d] / nb);
+    const float ns = sqrtf(y7t_blas_sdot_self(vec, dim));
     for (int d = 0; d < dim; ++d) vec[d] = vec[d] / ns;
 }
 
-#if Y7T_DEVICE
-// the fold of y7t_wave_sdot_self for n % 64 == 0, the lanes' own sums a5 (lane l: elements l, l + 64, ... in order) already in registers
-Y7T_FN float y7t_ss_wave_sdot_fold(float a5, int lane) {
-    const int l = lane & 15;
-    const float a = a5 + __shfl(a5, (lane + 8) & 63, 64);
-    const float a0 = __shfl(a, l & 7, 64), a1 = __shfl(a, 16 + (l & 7), 64), a2 = __shfl(a, 32 + (l & 7), 64), a3 = __shfl(a, 48 + (l & 7), 64);
-    const float sv = ((a0 + a1) + a2) + a3;
-    const float hv = sv + __shfl(sv, (lane & 48) + (((l & 7) + 4) & 7), 64);
-    const float h0 = __shfl(hv, 0, 64), h1 = __shfl(hv, 1, 64), h2 = __shfl(hv, 2, 64), h3 = __shfl(hv, 3, 64);
-    return (h0 + h1) + (h2 + h3);
-}
-#endif
-
-// write the queued vectors (ex may span a whole grid: on the device a wave per vector); resets nothing -- the next step zeroes the queue.  A detection row is
-// stored at most once per frame and a slot receives at most one vector, so the entries are independent.
-// PPD: the queue holds PPD entries per detection of the capacity (y7t_track_botsort_reid.h: two)
-template <int PPD>
-Y7T_FN int y7t_ss_pend_cap(const Y7TSs& f) {
-    if constexpr (PPD == 1) return f.h->cap_d;
-    else return PPD * f.h->cap_d;
-}
+// write the queued vectors (ex may span a whole grid: on the device a wave per vector): the moving average for an update, the raw copy for a new track.  The
+// entries are independent (see y7t_pend_queue).
 template <int PPD = 1>
 Y7T_FN void y7t_ss_store_pending(const Y7TExec& ex, const Y7TSs& f, const float* det_feats) {
-    const int dim = f.h->dim;
-    const int count = f.h->n_pend < y7t_ss_pend_cap<PPD>(f) ? f.h->n_pend : y7t_ss_pend_cap<PPD>(f);
+    const Y7TPend q = y7t_pend_of(f);
+    const int dim = q.h->dim;
+    const int count = y7t_pend_count<PPD>(q);
 #if Y7T_DEVICE
     if (y7t_dim_wave_ok(dim) && (ex.nt & 63) == 0) {      // 128 / 256 / 512 / 1024: a lane owns elements lane, lane + 64, ... (at most 16) in registers
         const int lane = ex.tid & 63, nc = dim >> 6;
         for (int i = ex.tid >> 6; i < count; i += ex.nt >> 6) {          // wave-uniform
-            const int sl = f.pend[3 * i], update = f.pend[3 * i + 2];
-            const float* b = det_feats + (size_t)f.pend[3 * i + 1] * dim;
+            const int sl = q.pend[3 * i], update = q.pend[3 * i + 2];
+            const float* b = det_feats + (size_t)q.pend[3 * i + 1] * dim;
             float* dst = f.vec + (size_t)sl * dim;
-            if (sl < 0 || sl >= f.h->cap_t) continue;
+            if (sl < 0 || sl >= q.h->cap_t) continue;
             float raw[16], sm[16];
             float a5 = 0.f;
 #pragma unroll
@@ -178,11 +127,11 @@ Y7T_FN void y7t_ss_store_pending(const Y7TExec& ex, const Y7TSs& f, const float*
                 for (int c = 0; c < 16; ++c) if (c < nc) dst[lane + 64 * c] = raw[c];
                 continue;
             }
-            const float nb = sqrtf(y7t_ss_wave_sdot_fold(a5, lane));
+            const float nb = sqrtf(y7t_blas_wave_sdot_fold(y7t_blas_wave_sdot_halve(a5, lane), lane));
             a5 = 0.f;
 #pragma unroll
-            for (int c = 0; c < 16; ++c) if (c < nc) { sm[c] = y7t_ss_mix(dst[lane + 64 * c], raw[c] / nb); a5 = y7t_fmaf(sm[c], sm[c], a5); }
-            const float ns = sqrtf(y7t_ss_wave_sdot_fold(a5, lane));
+            for (int c = 0; c < 16; ++c) if (c < nc) { sm[c] = y7t_np_mix_f32(dst[lane + 64 * c], raw[c] / nb); a5 = y7t_fmaf(sm[c], sm[c], a5); }
+            const float ns = sqrtf(y7t_blas_wave_sdot_fold(y7t_blas_wave_sdot_halve(a5, lane), lane));
 #pragma unroll
             for (int c = 0; c < 16; ++c) if (c < nc) dst[lane + 64 * c] = sm[c] / ns;
         }
@@ -190,36 +139,13 @@ Y7T_FN void y7t_ss_store_pending(const Y7TExec& ex, const Y7TSs& f, const float*
     }
 #endif
     for (int i = ex.tid; i < count; i += ex.nt) {
-        const int sl = f.pend[3 * i], update = f.pend[3 * i + 2];
-        if (sl < 0 || sl >= f.h->cap_t) continue;
-        const float* b = det_feats + (size_t)f.pend[3 * i + 1] * dim;
+        const int sl = q.pend[3 * i], update = q.pend[3 * i + 2];
+        if (sl < 0 || sl >= q.h->cap_t) continue;
+        const float* b = det_feats + (size_t)q.pend[3 * i + 1] * dim;
         float* dst = f.vec + (size_t)sl * dim;
         if (update) y7t_ss_ema(dst, b, dim);
         else for (int d = 0; d < dim; ++d) dst[d] = b[d];
     }
-}
-
-// queue the vectors a step decides to store (nothing in the step reads the vectors: this frame's distances were taken before it)
-template <int PPD = 1, class PairFn>
-Y7T_FN void y7t_ss_queue(const Y7TExec& ex, const Y7TSs& f, int count, int update, PairFn pair /* (i, slot&, detection row&) -> bool */) {
-    for (int i = ex.tid; i < count; i += ex.nt) {
-        int sl, row;
-        if (!pair(i, sl, row)) continue;
-        const int k = Y7T_FETCH_ADD(&f.h->n_pend, 1);
-        if (k < y7t_ss_pend_cap<PPD>(f)) { f.pend[3 * k] = sl; f.pend[3 * k + 1] = row; f.pend[3 * k + 2] = update; }
-        else f.h->status |= Y7T_SS_ERR_PEND;
-    }
-    y7t_sync(ex);
-}
-// ... for the rows of `tracks` that apply_matches UPDATED (tmpa[i] == 1; re_activate keeps the vector)
-template <int PPD = 1>
-Y7T_FN void y7t_ss_queue_updates(const Y7TExec& ex, const Y7TTrk& s, const Y7TSs& f, const int* tracks, int na, const int* dets) {
-    y7t_ss_queue<PPD>(ex, f, na, 1, [&](int i, int& sl, int& row) {
-        if (s.xrow[i] < 0 || s.tmpa[i] != 1) return false;
-        sl = tracks[i];
-        row = dets[s.xrow[i]];
-        return true;
-    });
 }
 
 // the fused pair: a box with the slot / detection row that names its entry of the appearance matrix (y7t_pairs contexts).  No geometry: boxes apart
@@ -317,7 +243,7 @@ Y7T_FN void y7t_tracker_step_strongsort(const Y7TExec& ex, void* blob, void* fbl
     const int kf = cfg.kf;
     if (cfg.tracker != Y7T_STRONGSORT || (!predict_only && (f.h->cap_t < cfg.cap_t || f.h->cap_d < cfg.cap_d))) {      // not this program's pool / a feature state too small for it: refuse, loudly
         if (ex.tid == 0) {
-            if (cfg.tracker != Y7T_STRONGSORT) h->status |= Y7T_ERR_KIND; else f.h->status |= Y7T_SS_ERR_CAP;
+            if (cfg.tracker != Y7T_STRONGSORT) h->status |= Y7T_ERR_KIND; else f.h->status |= Y7T_PEND_ERR_CAP;
             if (out_count) *out_count = 0;
         }
         return;
@@ -387,7 +313,7 @@ Y7T_FN void y7t_tracker_step_strongsort(const Y7TExec& ex, void* blob, void* fbl
     y7t_assoc_ss(ex, s, n_pool, n_hi, 0.7, s.pool, s.dhi, gamma, app, app_ld);
     Y7T_PROF(h, 3);
     y7t_apply_matches(ex, s, s.pool, n_pool, s.dhi, dets, 0, na, nr);
-    y7t_ss_queue_updates(ex, s, f, s.pool, n_pool, s.dhi);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.pool, n_pool, s.dhi);
     // ---- Step 3: the still-Tracked leftovers (u_tracks0) x the leftover detections, IoU at 0.5 ----
     const int n_left = y7t_compact(ex, n_hi, [&](int j) { return s.ycol[j] < 0; }, s.tmpb, 0);
     for (int k = ex.tid; k < n_left; k += ex.nt) s.left[k] = s.dhi[s.tmpb[k]];
@@ -401,7 +327,7 @@ Y7T_FN void y7t_tracker_step_strongsort(const Y7TExec& ex, void* blob, void* fbl
     Y7T_PROF(h, 4);
     y7t_assoc(ex, s, n_t0, n_left, 0.5);
     y7t_apply_matches(ex, s, s.rem, n_t0, s.left, dets, 0, na, nr);
-    y7t_ss_queue_updates(ex, s, f, s.rem, n_t0, s.left);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.rem, n_t0, s.left);
     Y7T_PROF(h, 5);
     // u_det1 (detection rows), in column order
     const int n_d1 = y7t_compact(ex, n_left, [&](int c) { return s.ycol[c] < 0; }, s.tmpb, 0);
@@ -423,7 +349,7 @@ Y7T_FN void y7t_tracker_step_strongsort(const Y7TExec& ex, void* blob, void* fbl
     Y7T_PROF(h, 6);
     y7t_assoc_ss(ex, s, n_unc, n_d1, 0.7, s.unconf, s.dlo, gamma, app, app_ld);
     y7t_apply_matches(ex, s, s.unconf, n_unc, s.dlo, dets, 2, na, nr);
-    y7t_ss_queue_updates(ex, s, f, s.unconf, n_unc, s.dlo);
+    y7t_pend_queue_updates(ex, s, y7t_pend_of(f), s.unconf, n_unc, s.dlo);
     Y7T_PROF(h, 7);
     {
         const int n_rm = y7t_compact(ex, n_unc, [&](int i) { return s.xrow[i] < 0; }, s.tmpa, 0);
@@ -468,7 +394,7 @@ Y7T_FN void y7t_tracker_step_strongsort(const Y7TExec& ex, void* blob, void* fbl
         }
         y7t_sync(ex);
         // STrack(..., feature=f): features = [f] (the raw vector, basetrack.py:97-103): whatever the slot's previous occupant left is overwritten
-        y7t_ss_queue(ex, f, made, 0, [&](int k, int& sl, int& row) {
+        y7t_pend_queue(ex, y7t_pend_of(f), made, 0, [&](int k, int& sl, int& row) {
             sl = s.tmpb[k];
             row = s.dlo[s.tmpa[k]];
             return true;

@@ -373,7 +373,7 @@ __global__ void k_ss_init(void* fblob, int cap_t, int cap_d, int dim, double gam
 // matching.embedding_distance(tracks, detections, 'euclidean') for every slot of the tracked / lost lists (confirmed and unconfirmed alike: the unconfirmed association
 // reads the same matrix) against every detection row above det_thresh, tiled like k_embed_dist: a workgroup takes 32 list entries x 64 detections, 32-deep k chunks of
 // both operands in LDS, 2 x 4 pairs per thread, the next chunk's global loads issued before the current chunk's arithmetic.  Every pair's sum is the sequential float64
-// chain over k = 0 .. dim-1 of y7t_ss_dist (= scipy's cdist), so the distances -- and the assignments that follow them -- are bit-identical to the plain form; only the
+// chain over k = 0 .. dim-1 of y7t_scipy_euclidean (= scipy's cdist, y7t_np_arith.h), so the distances -- and the assignments that follow them -- are bit-identical to the plain form; only the
 // order in which DIFFERENT pairs advance changes.  The grid is (workers, detection tiles): a worker walks the groups of 32 list entries whose number is its blockIdx.x
 // modulo the worker count (the lists' lengths are only known on the device).  The rows are the LISTS, not the state column: a lost track that aged out last frame is
 // Removed but still in the lost list for this frame's association (basetrack's sub_stracks runs before removed_stracks.extend), and its row takes part in the solve.
@@ -438,8 +438,8 @@ __global__ void __launch_bounds__(256) k_ss_appearance(void* blob, void* fblob, 
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float b = sB[tx + 16 * c][k];
-                    acc[0][c] = y7t_ss_sqstep(acc[0][c], a0, b);
-                    acc[1][c] = y7t_ss_sqstep(acc[1][c], a1, b);
+                    acc[0][c] = y7t_scipy_sqstep(acc[0][c], a0, b);
+                    acc[1][c] = y7t_scipy_sqstep(acc[1][c], a1, b);
                 }
             }
         }
@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(256) k_ss_appearance(void* blob, void* fblob, 
             const int sl = s_slot[2 * ty + r];
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (sl >= 0 && s_use[tx + 16 * c]) f.app[(size_t)sl * ld + j0 + tx + 16 * c] = y7t_ss_root(acc[r][c]);
+                if (sl >= 0 && s_use[tx + 16 * c]) f.app[(size_t)sl * ld + j0 + tx + 16 * c] = y7t_scipy_root(acc[r][c]);
         }
     }
 }
@@ -927,6 +927,23 @@ extern "C" int y7t_tracker_step_frames(void* state, const float* const* dets, co
     }
 }
 
+// The host part of a frame that the appearance trackers' entry points share (DeepSORT, StrongSORT, BoT-SORT with ReID; each checks its own arguments first, in the
+// order it always did): the thread count, the pool's kind (`refuse`: 0, or what the entry point returns for another tracker's pool), then FAMILY's step between the frame's
+// appearance launches (`before`) and its store launch (`after`) -- a frame without detections takes neither.  warp: the step's camera-motion argument, where it has one.
+template <class FAMILY, class Refuse, class Before, class After, class... W>
+static int step_appearance(void* state, void* feat_state, const float* dets, int n, const float* det_feats, double* out_rows, int out_cap, int* out_count, int threads,
+                           y7t_stream stream, Refuse refuse /* (const PoolInfo&) */, Before before /* (const PoolInfo&) */, After after, W... warp) {
+    const int nt = step_threads(threads, n);
+    Y7T_ARG_CHECK(nt > 0);
+    const PoolInfo pool = pool_info(state);
+    if (int e = refuse(pool)) return e;
+    if (n > 0) { if (int e = before(pool)) return e; }
+    const unsigned fb = step_fast_bytes(n);
+    if (int e = launch_step<FAMILY>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, warp...)) return e;
+    if (n > 0) { if (int e = after()) return e; }
+    return 0;
+}
+
 extern "C" size_t y7t_deepsort_feature_bytes(int cap_t, int cap_d, int feat_dim, int budget) {
     if (cap_t <= 0 || cap_d <= 0 || feat_dim <= 0 || budget <= 0) return 0;
     return y7t_feat_layout(cap_t, cap_d, feat_dim, budget).total;
@@ -945,25 +962,22 @@ extern "C" int y7t_tracker_step_deepsort(void* state, void* feat_state, int cap_
     Y7T_ARG_CHECK(state && feat_state && out_rows && out_count && out_cap >= 0 && cap_tracks > 0 && n >= 0);
     Y7T_ARG_CHECK(n == 0 || (dets && det_feats));
     Y7T_ARG_CHECK(cap_tracks <= 64 * Y7T_EMBED_WORKERS);      // (k_embed_dist: a workgroup owns at most 64 live slots)
-    const int nt = step_threads(threads, n);
-    Y7T_ARG_CHECK(nt > 0);
-    const int kind = pool_info(state).kind;
-    if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT || kind == Y7T_BOTSORT_REID)      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
-        return refuse_pool("y7t_tracker_step_deepsort", state, out_count, stream, "this pool was initialised as %s -- it steps through y7t_tracker_step",
-                           kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : kind == Y7T_BOTSORT_REID ? "BoT-SORT with ReID (y7t_tracker_step_botsort_reid)" : "StrongSORT (y7t_tracker_step_strongsort)");
-    if (n > 0) {
-        hipLaunchKernelGGL(k_ds_normalize, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats, n);      // a wave per detection
-        Y7T_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_embed_dist, dim3(cap_tracks < Y7T_EMBED_WORKERS ? cap_tracks : Y7T_EMBED_WORKERS, (n + 63) / 64), dim3(256), 0, S(stream), state, feat_state, n);
-        Y7T_LAUNCH_CHECK();
-    }
-    const unsigned fb = step_fast_bytes(n);
-    if (int e = launch_step<StepDeepsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb)) return e;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_ds_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);
-        Y7T_LAUNCH_CHECK();
-    }
-    return 0;
+    return step_appearance<StepDeepsort>(state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, threads, stream,
+        [&](const PoolInfo& pool) -> int {
+            const int kind = pool.kind;
+            if (kind == Y7T_C_BIOU || kind == Y7T_UAVMOT || kind == Y7T_STRONGSORT || kind == Y7T_DEEPMOT || kind == Y7T_BOTSORT_REID)      // no appearance rings: the pool's status says Y7T_ERR_KIND, nothing is stepped
+                return refuse_pool("y7t_tracker_step_deepsort", state, out_count, stream, "this pool was initialised as %s -- it steps through y7t_tracker_step",
+                                   kind == Y7T_C_BIOU ? "C-BIoU" : kind == Y7T_UAVMOT ? "UAVMOT" : kind == Y7T_DEEPMOT ? "DeepMOT (y7t_tracker_step_deepmot)" : kind == Y7T_BOTSORT_REID ? "BoT-SORT with ReID (y7t_tracker_step_botsort_reid)" : "StrongSORT (y7t_tracker_step_strongsort)");
+            return 0;
+        },
+        [&](const PoolInfo&) -> int {
+            hipLaunchKernelGGL(k_ds_normalize, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats, n);      // a wave per detection
+            Y7T_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_embed_dist, dim3(cap_tracks < Y7T_EMBED_WORKERS ? cap_tracks : Y7T_EMBED_WORKERS, (n + 63) / 64), dim3(256), 0, S(stream), state, feat_state, n);
+            Y7T_LAUNCH_CHECK();
+            return 0;
+        },
+        [&]() -> int { hipLaunchKernelGGL(k_ds_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats); Y7T_LAUNCH_CHECK(); return 0; });
 }
 
 extern "C" size_t y7t_strongsort_feature_bytes(int cap_t, int cap_d, int feat_dim) {
@@ -983,24 +997,18 @@ extern "C" int y7t_tracker_step_strongsort(void* state, void* feat_state, const 
                                            int* out_count, int threads, const double* gmc_warp, y7t_stream stream) {
     Y7T_ARG_CHECK(state && feat_state && out_rows && out_count && out_cap >= 0 && n >= 0);
     Y7T_ARG_CHECK(n == 0 || (dets && det_feats));
-    const int nt = step_threads(threads, n);
-    Y7T_ARG_CHECK(nt > 0);
-    const PoolInfo pool = pool_info(state);
-    if (pool.kind != Y7T_STRONGSORT)      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
-        return refuse_pool("y7t_tracker_step_strongsort", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as StrongSORT (tracker kind %d)", pool.kind);
-    if (n > 0) {
-        const int groups = (pool.cap_t + 31) / 32;
-        const int vec_ok = (((uintptr_t)feat_state | (uintptr_t)det_feats) & 15) == 0;
-        hipLaunchKernelGGL(k_ss_appearance, dim3(groups < Y7T_SS_WORKERS ? groups : Y7T_SS_WORKERS, (n + 63) / 64), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n, vec_ok);
-        Y7T_LAUNCH_CHECK();
-    }
-    const unsigned fb = step_fast_bytes(n);
-    if (int e = launch_step<StepStrongsort>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, gmc_warp)) return e;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_ss_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most one per detection)
-        Y7T_LAUNCH_CHECK();
-    }
-    return 0;
+    return step_appearance<StepStrongsort>(state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, threads, stream,
+        [&](const PoolInfo& pool) -> int {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+            return pool.kind == Y7T_STRONGSORT ? 0 : refuse_pool("y7t_tracker_step_strongsort", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as StrongSORT (tracker kind %d)", pool.kind);
+        },
+        [&](const PoolInfo& pool) -> int {
+            const int groups = (pool.cap_t + 31) / 32;
+            const int vec_ok = (((uintptr_t)feat_state | (uintptr_t)det_feats) & 15) == 0;
+            hipLaunchKernelGGL(k_ss_appearance, dim3(groups < Y7T_SS_WORKERS ? groups : Y7T_SS_WORKERS, (n + 63) / 64), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n, vec_ok);
+            Y7T_LAUNCH_CHECK();
+            return 0;
+        },
+        [&]() -> int { hipLaunchKernelGGL(k_ss_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats); Y7T_LAUNCH_CHECK(); return 0; }, gmc_warp);      // a wave per queued vector (at most one per detection)
 }
 
 extern "C" size_t y7t_botsort_reid_feature_bytes(int cap_t, int cap_d, int feat_dim) {
@@ -1022,23 +1030,17 @@ extern "C" int y7t_tracker_step_botsort_reid(void* state, void* feat_state, cons
                                              int* out_count, int threads, const double* gmc_warp, y7t_stream stream) {
     Y7T_ARG_CHECK(state && feat_state && out_rows && out_count && out_cap >= 0 && n >= 0);
     Y7T_ARG_CHECK(n == 0 || (dets && det_feats));
-    const int nt = step_threads(threads, n);
-    Y7T_ARG_CHECK(nt > 0);
-    const PoolInfo pool = pool_info(state);
-    if (pool.kind != Y7T_BOTSORT_REID)      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
-        return refuse_pool("y7t_tracker_step_botsort_reid", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as BoT-SORT with its appearance branch (tracker kind %d)", pool.kind);
-    if (n > 0) {   // a wave per row: the live slots (at most cap_tracks) and the frame's detections; a frame without detections takes no cosine
-        const int rows = pool.cap_t + n, blocks = (rows + 3) / 4;
-        hipLaunchKernelGGL(k_br_prepare, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n);
-        Y7T_LAUNCH_CHECK();
-    }
-    const unsigned fb = step_fast_bytes(n);
-    if (int e = launch_step<StepBotsortReid>(1, nt, kFastBytes + Y7T_LDS_HDR, fb + Y7T_LDS_HDR, stream, state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, fb, gmc_warp)) return e;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_br_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats);      // a wave per queued vector (at most two per detection)
-        Y7T_LAUNCH_CHECK();
-    }
-    return 0;
+    return step_appearance<StepBotsortReid>(state, feat_state, dets, n, det_feats, out_rows, out_cap, out_count, threads, stream,
+        [&](const PoolInfo& pool) -> int {      // another tracker's pool: its status says Y7T_ERR_KIND, nothing is stepped (a blob that was never initialised is not touched)
+            return pool.kind == Y7T_BOTSORT_REID ? 0 : refuse_pool("y7t_tracker_step_botsort_reid", pool.kind >= 0 ? state : nullptr, out_count, stream, "this pool was not initialised as BoT-SORT with its appearance branch (tracker kind %d)", pool.kind);
+        },
+        [&](const PoolInfo& pool) -> int {   // a wave per row: the live slots (at most cap_tracks) and the frame's detections; a frame without detections takes no cosine
+            const int rows = pool.cap_t + n, blocks = (rows + 3) / 4;
+            hipLaunchKernelGGL(k_br_prepare, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, S(stream), state, feat_state, dets, det_feats, n);
+            Y7T_LAUNCH_CHECK();
+            return 0;
+        },
+        [&]() -> int { hipLaunchKernelGGL(k_br_store, dim3((n + 3) / 4), dim3(256), 0, S(stream), feat_state, det_feats); Y7T_LAUNCH_CHECK(); return 0; }, gmc_warp);      // a wave per queued vector (at most two per detection)
 }
 
 // DeepMOT.update for one frame: the front program, the Deep Hungarian Net on the pool x high-detection matrix it wrote (skipped where either side is empty), the back

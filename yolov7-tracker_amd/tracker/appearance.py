@@ -120,7 +120,7 @@ class AppearanceTracker(BaseTracker):
         return feats_dev.to(device="cuda", dtype=torch.float32).contiguous()
 
     def _feature_status(self):
-        return int(self._feat[20:24].view(torch.int32).item())           # Y7TFeatHdr.status / Y7TSsHdr.status
+        return int(self._feat[20:24].view(torch.int32).item())           # Y7TPendHdr.status: every feature state's header derives from it (csrc/y7t_track_pend.h)
 
     def _step(self, d, n, feats, warp, out):
         """the tracker's library call for one frame: d (n, 6) and feats (>= n, D) float32 device tensors, warp a (6,) float64 device tensor or None,
