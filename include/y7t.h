@@ -305,6 +305,35 @@ int y7t_dhn_forward_f32(void* dhn, const float* D, int h, int w, float* out, y7t
 int y7t_tracker_step_deepmot(void* state, void* dhn, const float* dets, int n, int img_h, int img_w, double* out_rows, int out_cap, int* out_count, int threads,
                              y7t_stream stream);
 
+/* AFLink (tracker/reid_models/AFLink.py: class PostLinker, the appearance-free link model of StrongSORT++; the reference ships the network and never calls it):
+ * after a sequence, tracklets that a missed detection or an occlusion split into two ids are joined again from their (frame, x, y) rows alone.
+ *
+ * The AFLINK OBJECT is caller-owned device memory of y7t_aflink_weight_bytes() + y7t_aflink_workspace_bytes(max_tracklets, max_rows, max_pairs) bytes at a
+ * 256-byte aligned address.  Capacities: 1 <= max_tracklets <= 32768, max_rows >= 1 (the table stays the caller's: nothing is kept per row today), 1 <= max_pairs
+ * <= 2^24.  The workspace holds the activations of one chunk of min(max_pairs, 2048) pairs (72 KiB a pair: 144 MiB at most) and two integers a tracklet.
+ * y7t_aflink_init: `weights` = the y7t_aflink_num_weights() = 1075266 float32 values of the float tensors of PostLinker().state_dict() in its order (the
+ *   num_batches_tracked entries left out), packed, in host or device memory (INTEGRATION.md lists the offsets).  Synchronous.  y7t_aflink_release: the object's
+ *   memory is about to be freed.
+ * y7t_aflink_score_pairs_f32: scores[p] = softmax(PostLinker(x1[p], x2[p]))[1] in eval mode for x1, x2 (P x 30 x 3 float32, device; columns frame, x, y as the pair
+ *   transform leaves them), any P >= 0.  fp32 throughout; no atomics, bit-identical from call to call.  Asynchronous.
+ * y7t_aflink_candidates: the whole device side of AFLink.link.  rows: [frame, x, y] float64 rows of n_tracklets tracklets, each a run sorted by frame; row_offsets:
+ *   n_tracklets + 1 int32 (device).  Every ordered pair (i, j), i != j, with thrT0 <= first_frame(j) - last_frame(i) < thrT1 and not thrS < the distance of i's
+ *   last and j's first position (float64) is a candidate; candidates are compacted in row-major (i, j) order into pairs_out (max_pairs x 2 int32), transformed
+ *   (former: last 30 rows, zero rows in front; latter: first 30, zero rows behind; per column min / max over the 60 rows, (x - (max + min) / 2) / ((max - min) / 2
+ *   + 1e-5) in float64, cast to float32) and scored into scores_out (max_pairs float32).  x1_out / x2_out (max_pairs x 90 float32) receive the transformed blocks, or
+ *   NULL.  count_out (int32): the number of candidates; status_out (int32): bit 0 = more candidates than max_pairs -- the first max_pairs are listed and scored and
+ *   the caller must not use them as the whole list.  Everything stays on the device: asynchronous, no read-back.
+ * Errors: Y7T_E_ARG (a null pointer, a misaligned or too small object, a capacity out of range), Y7T_E_STATE (an address y7t_aflink_init never saw),
+ * Y7T_E_CAPACITY (n_tracklets > max_tracklets). */
+size_t y7t_aflink_num_weights(void);
+size_t y7t_aflink_weight_bytes(void);
+size_t y7t_aflink_workspace_bytes(int max_tracklets, int max_rows, int max_pairs);
+int y7t_aflink_init(void* obj, size_t bytes, const float* weights, int max_tracklets, int max_rows, int max_pairs, y7t_stream stream);
+int y7t_aflink_release(void* obj);
+int y7t_aflink_score_pairs_f32(void* obj, const float* x1, const float* x2, int P, float* scores, y7t_stream stream);
+int y7t_aflink_candidates(void* obj, const double* rows, const int* row_offsets, int n_tracklets, double thrT0, double thrT1, double thrS, int* pairs_out,
+                          float* x1_out, float* x2_out, float* scores_out, int* count_out, int* status_out, y7t_stream stream);
+
 /* byte offsets of the arrays inside a state blob, for host-side views (tracked_stracks, lost_stracks, ...).
  * names/offsets: see y7t_tracker_field_name(i); returns the number of fields. */
 int y7t_tracker_layout(int cap_tracks, int cap_dets, int64_t* offsets, int max_fields);

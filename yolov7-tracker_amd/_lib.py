@@ -70,6 +70,14 @@ SIGNATURES = {
     "y7t_dhn_release": (c_int, [c_void_p]),
     "y7t_dhn_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "y7t_tracker_step_deepmot": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "y7t_aflink_num_weights": (c_size_t, []),
+    "y7t_aflink_weight_bytes": (c_size_t, []),
+    "y7t_aflink_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "y7t_aflink_init": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "y7t_aflink_release": (c_int, [c_void_p]),
+    "y7t_aflink_score_pairs_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "y7t_aflink_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "y7t_kf_multi_gmc_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "y7t_ecc_prepare_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "y7t_ecc_workspace_bytes": (c_int, [c_int, c_int, c_void_p]),

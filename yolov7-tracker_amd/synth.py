@@ -330,3 +330,122 @@ def make_dhn_weights(seed=0, scale=1.0):
         bound = float(scale) / np.sqrt(float(fan))
         out[name] = rng.uniform(-bound, bound, size=shape).astype(np.float32)
     return out
+
+
+# ---- AFLink, the appearance-free link model of StrongSORT++ (the reference's tracker/reid_models/AFLink.py, class PostLinker) ----
+def aflink_tensor_shapes():
+    """-> [(name, shape)]: the 74 float tensors of PostLinker().state_dict(), in its order, without the num_batches_tracked entries (1,075,266 values): two temporal
+    modules of four blocks (a (7,1) convolution and the BatchNorms bnf, bnx, bny of the three columns), two fusion blocks ((1,3) convolution, BatchNorm), a classifier"""
+    out = []
+    for mod in ("TemporalModule_1", "TemporalModule_2"):
+        for k, (cin, cout) in enumerate(((1, 32), (32, 64), (64, 128), (128, 256))):
+            out.append(("%s.%d.conv.weight" % (mod, k), (cout, cin, 7, 1)))
+            for bn in ("bnf", "bnx", "bny"):
+                out += [("%s.%d.%s.%s" % (mod, k, bn, t), (cout,)) for t in ("weight", "bias", "running_mean", "running_var")]
+    for mod in ("FusionBlock_1", "FusionBlock_2"):
+        out.append((mod + ".conv.weight", (256, 256, 1, 3)))
+        out += [("%s.bn.%s" % (mod, t), (256,)) for t in ("weight", "bias", "running_mean", "running_var")]
+    out += [("classifier.fc1.weight", (128, 512)), ("classifier.fc1.bias", (128,)), ("classifier.fc2.weight", (2, 128)), ("classifier.fc2.bias", (2,))]
+    return out
+
+
+def aflink_transform(former, latter):
+    """the pair transform (DESIGN.md section 4 "AFLink"): former, latter (n, 3) float64 [frame, x, y] -> two (30, 3) float32 blocks"""
+    a, b = np.zeros((30, 3)), np.zeros((30, 3))
+    fa, lb = np.asarray(former, np.float64)[-30:], np.asarray(latter, np.float64)[:30]
+    a[30 - len(fa):] = fa
+    b[:len(lb)] = lb
+    both = np.concatenate([a, b], 0)
+    mn, mx = both.min(0), both.max(0)
+    sub, div = (mx + mn) / 2, (mx - mn) / 2 + 1e-5
+    return ((a - sub) / div).astype(np.float32), ((b - sub) / div).astype(np.float32)
+
+
+AFLINK_PAIR_LENGTHS = (1, 2, 29, 30, 31, 60)
+
+
+def make_aflink_tracklet_pairs(n=256, seed=0):
+    """seeded synthetic (former, latter) tracklet pairs, [frame, x, y] float64 rows: lengths among 1, 2, 29, 30, 31, 60, gaps 0..29, the latter either the same
+    object moving on or another object nearby; pair 0 is a single-row pair and pair 1 has a constant x column"""
+    rng = np.random.RandomState(1000 + int(seed))
+    out = []
+    for k in range(n):
+        la, lb = (1, 1) if k == 0 else (AFLINK_PAIR_LENGTHS[rng.randint(6)], AFLINK_PAIR_LENGTHS[rng.randint(6)])
+        gap = int(rng.randint(0, 30))
+        f0 = int(rng.randint(1, 500))
+        pos, vel = rng.uniform(50, 1200, 2), rng.uniform(-6, 6, 2)
+        fa = np.arange(f0, f0 + la, dtype=np.float64)
+        fb = np.arange(f0 + la - 1 + gap, f0 + la - 1 + gap + lb, dtype=np.float64)
+        pa = pos + (fa - f0)[:, None] * vel + rng.normal(0, 1.0, (la, 2))
+        if rng.rand() < 0.5:
+            pb = pos + (fb - f0)[:, None] * vel + rng.normal(0, 1.0, (lb, 2))
+        else:
+            pb = pa[-1] + rng.uniform(-60, 60, 2) + (fb - fb[0])[:, None] * rng.uniform(-6, 6, 2) + rng.normal(0, 1.0, (lb, 2))
+        if k == 1:
+            pa[:, 0] = 640.0
+            pb[:, 0] = 640.0
+        out.append((np.column_stack([fa, pa]), np.column_stack([fb, pb])))
+    return out
+
+
+def make_aflink_pairs(n=256, seed=0):
+    """-> x1, x2 (n, 30, 3) float32: make_aflink_tracklet_pairs through aflink_transform"""
+    blocks = [aflink_transform(a, b) for a, b in make_aflink_tracklet_pairs(n, seed)]
+    return np.stack([x[0] for x in blocks]), np.stack([x[1] for x in blocks])
+
+
+def aflink_forward_np(weights, x1, x2, dtype=np.float64):
+    """PostLinker.forward in eval mode from the tensors by name, NumPy: x1, x2 (P, 30, 3) -> the two logits (P, 2)"""
+    w = {k: np.asarray(v, dtype) for k, v in weights.items()}
+
+    def bn(x, p):
+        return (x - w[p + ".running_mean"]) / np.sqrt(w[p + ".running_var"] + dtype(1e-5)) * w[p + ".weight"] + w[p + ".bias"]
+
+    feats = []
+    for b, x in ((1, x1), (2, x2)):
+        h = np.asarray(x, dtype)[..., None]                                   # [P][rows][3][channels]
+        for k in range(4):
+            p = "TemporalModule_%d.%d" % (b, k)
+            cw = w[p + ".conv.weight"][:, :, :, 0]                            # [cout][cin][7]
+            rows = h.shape[1] - 6
+            y = sum(h[:, t:t + rows] @ cw[:, :, t].T for t in range(7))
+            y = np.stack([bn(y[:, :, c], "%s.%s" % (p, name)) for c, name in enumerate(("bnf", "bnx", "bny"))], 2)
+            h = np.maximum(y, 0)
+        fw = w["FusionBlock_%d.conv.weight" % b][:, :, 0, :]                   # [cout][cin][3]
+        y = sum(h[:, :, c] @ fw[:, :, c].T for c in range(3))
+        feats.append(np.maximum(bn(y, "FusionBlock_%d.bn" % b), 0).mean(1))
+    v = np.concatenate(feats, 1)
+    hid = np.maximum(v @ w["classifier.fc1.weight"].T + w["classifier.fc1.bias"], 0)
+    return hid @ w["classifier.fc2.weight"].T + w["classifier.fc2.bias"]
+
+
+def make_aflink_weights(seed=0, gain=1.5, accept=0.15):
+    """seeded weights of PostLinker (no AFLink_epoch20.pth ships with the reference) -> {name: float32 array} in state_dict() order.  One
+    numpy.random.RandomState(seed), tensor by tensor: convolution and linear weights He-normal (std sqrt(2 / fan_in)) times `gain`; BatchNorm weight and running_var
+    uniform(0.8, 1.2), bias and running_mean normal(0, 0.1), different for bnf, bnx, bny; fc1.bias zero; fc2.bias = [0, b] with b (rounded to 1e-3) such that about
+    `accept` of make_aflink_pairs(256, seed) score above 0.95.  PyTorch's own initialisation makes the score constant (0.48); gain 1.5 spreads it over 0..1."""
+    key = (int(seed), float(gain), float(accept))
+    if key in _AFLINK_WEIGHTS:      # (the calibration evaluates the network 256 times: once per process and recipe)
+        return {k: v.copy() for k, v in _AFLINK_WEIGHTS[key].items()}
+    rng = np.random.RandomState(int(seed))
+    out = {}
+    for name, shape in aflink_tensor_shapes():
+        if name.endswith("conv.weight") or name in ("classifier.fc1.weight", "classifier.fc2.weight"):
+            fan = int(np.prod(shape[1:]))
+            out[name] = (rng.standard_normal(shape) * (float(gain) * np.sqrt(2.0 / fan))).astype(np.float32)
+        elif name.startswith("classifier"):
+            out[name] = np.zeros(shape, np.float32)
+        elif name.endswith((".weight", ".running_var")):
+            out[name] = rng.uniform(0.8, 1.2, shape).astype(np.float32)
+        else:
+            out[name] = rng.normal(0.0, 0.1, shape).astype(np.float32)
+    x1, x2 = make_aflink_pairs(256, seed)
+    lg = aflink_forward_np(out, x1, x2)
+    # score > 0.95  <=>  l1 + b - l0 > log(19)
+    b = np.log(19.0) - np.quantile(lg[:, 1] - lg[:, 0], 1.0 - float(accept))
+    out["classifier.fc2.bias"] = np.array([0.0, np.round(b, 3)], np.float32)
+    _AFLINK_WEIGHTS[key] = {k: v.copy() for k, v in out.items()}
+    return out
+
+
+_AFLINK_WEIGHTS = {}

@@ -97,6 +97,10 @@ def main(opts, cfgs):
         raise ValueError("--botsort_reid: the appearance branch belongs to --tracker botsort (tracker %r has none to switch)" % (opts.tracker,))
     if opts.gmc != 'none' and opts.tracker not in ('strongsort', 'botsort'):
         raise ValueError("--gmc %s: only strongsort and botsort compensate camera motion (tracker %r does not)" % (opts.gmc, opts.tracker))
+    aflink_weights = None
+    if getattr(opts, 'aflink', None):
+        from .aflink import load_aflink_weights
+        aflink_weights = load_aflink_weights(opts.aflink)
     img_size = opts.img_size[0] if isinstance(opts.img_size, (list, tuple)) else opts.img_size
     model = attempt_load(opts.model_path, cfg=opts.model_cfg, nc=opts.nc, img_size=img_size, max_batch=max(1, opts.batch))
     stride = int(model.stride.max())
@@ -114,7 +118,8 @@ def main(opts, cfgs):
         print(f'--------------tracking seq {seq}--------------')
         if synthetic:
             loader = tracker_dataloader.SyntheticLoader(opts.synthetic_frames, opts.synthetic_objs, opts.img_size, si,
-                                                        device_preprocess=opts.device_preprocess, moving_camera='corners' if opts.gmc == 'features' else opts.gmc != 'none')
+                                                        device_preprocess=opts.device_preprocess, moving_camera='corners' if opts.gmc == 'features' else opts.gmc != 'none',
+                                                        miss=getattr(opts, 'synthetic_miss', None))
         else:
             # track.py:126: the sequence folder ('origin') or the path file every sequence is filtered out of ('yolo')
             path = os.path.join(DATA_ROOT, seq) if opts.data_format == 'origin' else os.path.join(getattr(opts, 'yolo_root', './'), opts.dataset, 'test.txt')
@@ -171,6 +176,9 @@ def main(opts, cfgs):
                 frame_id += 1
         seq_fps.append(i / timer.total_time)   # track.py:181 (sic: last index, not the frame count)
         timer.clear()
+        if aflink_weights is not None:      # (extension) --aflink: the rows that would have been written, linked; the file and TrackEval see the linked ids
+            from . import aflink
+            results = aflink.link_results(aflink_weights, results, max_pairs=opts.aflink_max_pairs)
         save_results(opts.results_root, folder_name, seq, results)
     print(f'average fps: {np.mean(seq_fps)}')
     if opts.track_eval and (synthetic or cfgs.get('TRACK_EVAL')):
@@ -250,7 +258,12 @@ def build_parser():
     parser.add_argument('--synthetic_frames', type=int, default=100)
     parser.add_argument('--synthetic_objs', type=int, default=80)
     parser.add_argument('--synthetic_seqs', type=int, default=1)
+    parser.add_argument('--synthetic_miss', type=float, default=None, help="--dataset synthetic: the scene detections' miss rate (default: the generator's 0.10)")
     parser.add_argument('--results_root', type=str, default='./tracker/results')
+    parser.add_argument('--aflink', type=str, default=None,
+                        help="(extension) link fragmented tracklets after each sequence with AFLink (tracker/aflink.py): a PostLinker state dict file, or "
+                             "random:aflink[:seed[:gain]]; default off")
+    parser.add_argument('--aflink_max_pairs', type=int, default=65536, help='(extension) --aflink: capacity of the candidate pair list')
     parser.add_argument('--yolo_root', type=str, default='./', help="(extension) where ./<dataset>/test.txt of --data_format yolo lives (the reference: the working directory)")
     # the NMS arguments of the reference's detect.py:166-167 (non_max_suppression applies them before its max_nms / max_det cuts)
     parser.add_argument('--classes', nargs='+', type=int, default=None, help='(extension) filter by class: --classes 0, or --classes 0 2 3')

@@ -111,7 +111,7 @@ class SyntheticLoader(torch.utils.data.Dataset):
     """seeded synthetic sequence: frames rendered by synth.make_frames, plus the scene's detections (used as the
     tracker's input with --synthetic_dets, since random detector weights do not detect anything meaningful)."""
 
-    def __init__(self, n_frames, n_obj, size, seq_idx, device_preprocess=False, moving_camera=False):
+    def __init__(self, n_frames, n_obj, size, seq_idx, device_preprocess=False, moving_camera=False, miss=None):
         from .. import synth
         self.device_preprocess = device_preprocess
         if moving_camera == 'corners':      # ... with corners (synth.make_corner_frames): what the feature-based estimate needs to see
@@ -120,7 +120,7 @@ class SyntheticLoader(torch.utils.data.Dataset):
             self.frames, self.warps = synth.make_camera_frames(n_frames, size, seq_idx)
         else:
             self.frames = synth.make_frames(n_frames, n_obj, size, seq_idx)
-        self.dets = synth.make_detections(n_frames, n_obj, size, seq_idx)
+        self.dets = synth.make_detections(n_frames, n_obj, size, seq_idx, **({} if miss is None else {'miss': float(miss)}))
 
     def __getitem__(self, i):
         ori = self.frames[i]
