@@ -17,7 +17,7 @@ def build(defs=()):
     tag = "".join(c for c in "".join(defs) if c.isalnum()) or "default"
     bdir = os.path.join(_HERE, "build_" + tag)
     so = os.path.join(bdir, "libconvsim.so")
-    srcs = [os.path.join(_CSRC, f) for f in ("y7t_conv.hip", "y7t_conv_common.h", "y7t_det.h", "y7t_common.h", "y7t_conv_patch.hip", "y7t_conv_patch_s2.hip", "y7t_conv_ws.hip", "y7t_conv_p8.hip", "y7t_conv_ws_s2.hip", "y7t_conv_ws128.hip")]
+    srcs = [os.path.join(_CSRC, f) for f in ("y7t_conv.hip", "y7t_conv_common.h", "y7t_det.h", "y7t_common.h", "y7t_conv_patch.hip", "y7t_conv_patch_s2.hip", "y7t_conv_ws.hip", "y7t_conv_p8.hip", "y7t_conv_ws_s2.hip", "y7t_conv_ws128.hip", "y7t_decode.h")]
     deps = srcs + [os.path.join(_HERE, "runtime.inc"), os.path.join(_HERE, "fake", "hip", "hip_runtime.h"), os.path.abspath(__file__)]
     if os.path.exists(so) and os.path.getmtime(so) >= max(os.path.getmtime(d) for d in deps):
         return so

@@ -1,4 +1,4 @@
-"""y7t_det_postprocess_ex through the C ABI: non_max_suppression's `classes`, `agnostic` and `multi_label` on the device (k_decode_filter_ml, k_rank_sort_opts and the
+"""y7t_det_postprocess_ex through the C ABI: non_max_suppression's `classes`, `agnostic` and `multi_label` on the device (k_decode_filter_ml, k_rank_sort<true> and the
 unchanged k_nms_keep of csrc/y7t_post.hip), in the pattern of tests/test_postprocess_gpu.py -- planted candidates, sentinel-filled outputs, the bytes behind the
 workspace checked -- against the restatement of tests/nms_opts_ref.py.  Comparisons on planted candidates are exact: ndets, the kept slots, all six columns, nothing
 written past ndets.  tests/test_nms_opts_scenes.py shows on the CPU that every scene has the property its case is about."""

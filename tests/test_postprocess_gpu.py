@@ -181,6 +181,52 @@ def test_detector_empty_image_after_a_full_one_fused_forward():
     assert n1[lo] == 0 and n1[hi] >= 1
 
 
+def test_candidate_arrays_follow_the_workspace_layout(L):
+    """Detector.candidate_arrays restates in Python the first five offsets of y7t_post_ws (csrc/y7t_post.hip), the one C function that lays a workspace out.  B = 3 with
+    max_cand = 100: 4800 / 1200 / 12 bytes per array, none a multiple of 256, so every array starts at a rounded offset and a slip in any of them shows.  All head
+    logits at -20 except five planted rows (box logits 0: sigmoid exactly 0.5, so the float32 box is cell centre +- anchor / 2 without a rounding to argue about):
+    three in image 0, none in image 1, two in the last image.  The views show exactly those rows, counts and boxes; and the workspace size is the closed form written out at the end: nine 256-rounded arrays plus 256 bytes."""
+    from yolov7_tracker_amd.detector import arch, model
+    B, cap, conf = 3, 100, 0.25
+    det = model.Detector(arch.ARCHS["yolov7-tiny"](10), None, img_size=(128, 192), max_batch=B, max_cand=cap, seed=0)
+    out = det(torch.rand((B, 3, 128, 192), generator=torch.Generator().manual_seed(13)))[0]
+    p, na, no = det.plan, det.plan.det["na"], det.plan.det["no"]
+    planted = {0: [(0, 5, 7, 1, 3), (1, 0, 11, 2, 0), (2, 3, 5, 0, 9)], 1: [], 2: [(0, 15, 23, 2, 4), (2, 0, 0, 1, 7)]}      # image: (level, y, x, anchor, class)
+    want = {}
+    for l, hd in enumerate(p.heads):
+        t = det.head_tensor(l, B)
+        h = np.full((B, hd["ny"], hd["nx"], na, no), -20.0, np.float32)
+        row0 = sum(na * f["ny"] * f["nx"] for f in p.heads[:l])
+        for b, cells in planted.items():
+            for (ll, y, x, an, c) in cells:
+                if ll != l:
+                    continue
+                h[b, y, x, an, :4], h[b, y, x, an, 4], h[b, y, x, an, 5 + c] = 0.0, 8.0, 8.0
+                st, aw, ah = np.float32(hd["stride"]), np.float32(det.spec["anchors"][l][2 * an]), np.float32(det.spec["anchors"][l][2 * an + 1])
+                cx, cy = (np.float32(0.5) + np.float32(x)) * st, (np.float32(0.5) + np.float32(y)) * st
+                want[(b, row0 + (an * hd["ny"] + y) * hd["nx"] + x)] = (np.array([cx - aw / 2, cy - ah / 2, cx + aw / 2, cy + ah / 2], np.float32), c)
+        t.copy_(torch.from_numpy(h.reshape(t.shape)))
+    det.postprocess(out, conf, 0.45, None)
+    torch.cuda.synchronize()
+    for views in (det.candidate_arrays(out.pset, B=B), det.candidate_arrays(out.pset)):      # (the default batch is the one postprocess just ran)
+        cbox, cscore, ccls, cidx, count = [v.cpu().numpy() for v in views]
+        assert cbox.shape == (B, cap, 4) and cidx.shape == (B, cap) and count.tolist() == [len(planted[b]) for b in range(B)]
+        for b in range(B):
+            n = int(count[b])
+            assert sorted(cidx[b, :n].tolist()) == sorted(r for (bb, r) in want if bb == b)
+            for j in range(n):
+                wbox, wcls = want[(b, int(cidx[b, j]))]
+                np.testing.assert_array_equal(cbox[b, j], wbox, err_msg="image %d slot %d" % (b, j))
+                assert int(ccls[b, j]) == wcls and 0.99 < cscore[b, j] < 1.0
+    assert det.plan.post[out.pset].cand.cpu().numpy().tolist() == [3, 0, 2]
+    rup = lambda n: (n + 255) // 256 * 256
+    for max_nms in (30000, 30):      # mcap = min(cap, max_nms): the cap, then max_nms
+        mcap = min(cap, max_nms)
+        closed = (rup(B * cap * 16) + rup(B * cap * 4) + rup(B * cap * 4) + rup(B * cap * 4) + rup(B * 4) + rup(B * 4) + rup(B * mcap * 16) + rup(B * mcap * 4) +
+                  rup(B * 5 * 4) + 256)
+        assert int(L.y7t_det_postprocess_workspace_bytes(B, cap, max_nms)) == closed
+
+
 @pytest.mark.parametrize("max_det", [1, 2, 63, 64, 65, 300])
 def test_max_det_cut(L, max_det):
     """case 3: the output is the first max_det of the uncut keep list -- cuts in the middle of a wave's keep loop (63, 65), at its end (64) and in a later sort chunk (300)"""

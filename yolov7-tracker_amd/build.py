@@ -31,10 +31,11 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # -fno-slp-vectorize: the SLP vectoriser pairs the epilogues' fp32 multiplies / adds into v_pk_mul_f32 / v_pk_add_f32, and ONE packed-fp32 instruction holds the matrix
 # pipe off for ~9 ns -- from either wave of a SIMD -- where two plain fp32 instructions per MFMA cost nothing (scripts/ubench/issue_classes.hip, profiles/r03_issue_classes.txt)
 _CONV = ["-ffp-contract=fast", "-fno-slp-vectorize"]
-# y7t_conv.hip: fast-honor-pragmas.  Under plain `fast` the backend fuses ANY multiply with a following add / subtract, flagged or not, so `#pragma clang fp contract(off)`
-# around the fused Detect decode could not keep expf's expansion (x * log2e - rndne(x * log2e), expanded behind the front end) from becoming one fma: one candidate in four
-# differed from k_decode_filter (y7t_post.hip, contraction off) in the last bit of score or box.  Honouring the pragma, the two Detect-decode instances gain ten instructions
-# each; the other 21 functions of the file compile to the same instructions and resource numbers (profiles/conv_forms_margins.txt)
+# y7t_conv.hip: fast-honor-pragmas.  Its Detect epilogue and the decode kernels of y7t_post.hip (contraction off) run the SAME functions, csrc/y7t_decode.h, whose bodies
+# carry `#pragma clang fp contract(off)`.  Under plain `fast` the backend fuses ANY multiply with a following add / subtract, flagged or not, so the pragma could not keep
+# expf's expansion (x * log2e - rndne(x * log2e), expanded behind the front end) from becoming one fma: one candidate in four differed between the two files in the last
+# bit of score or box.  Honouring the pragma costs the two Detect-decode instances ten instructions each; the other 21 functions of the file compiled to the same
+# instructions and resource numbers (profiles/conv_forms_margins.txt)
 _CONV_IGEMM = ["-ffp-contract=fast-honor-pragmas", "-fno-slp-vectorize"]
 FILE_FLAGS = {"y7t_conv.hip": _CONV_IGEMM, "y7t_conv_patch.hip": _CONV, "y7t_conv_patch_s2.hip": _CONV, "y7t_stem.hip": ["-fno-slp-vectorize"],
               "y7t_conv_ws.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_ws128.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_p8.hip": _CONV, "y7t_conv_ws_s2.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_post.hip": []}

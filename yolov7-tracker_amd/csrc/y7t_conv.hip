@@ -20,7 +20,7 @@
 // Concat elimination: input and output are channel SLICES of wider NHWC buffers (ldin/cin_off, ldout/cout_off),
 //             so producers write straight into their slot of a concat buffer and consumers read slices.
 #include "y7t_common.h"
-#include "y7t_det.h"
+#include "y7t_decode.h"
 #include <stdlib.h>
 
 #include "y7t_conv_common.h"
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 || BM * BN >= 256 * 256 ? 1 
         __syncthreads();
         // Slots: a workgroup reserves ONE block per image with a single global atomic (every candidate bumping count[b] itself
         // serialised ~200 same-address atomics per workgroup in L2: 470 us on the 40x40 level); ranks inside the block come from LDS atomics.
-        const int HoWo2 = q.ny * q.nx, nc = q.no - 5;
+        const int HoWo2 = q.lv.ny * q.lv.nx, nc = q.no - 5;
         int* lcount = (int*)(smem + BM * LD * 4);        // [BM] candidates of image b0 + i found by this workgroup
         int* lbase = lcount + BM;                        // [BM] first slot of that block
         const int b0 = m0 / HoWo2;
@@ -290,49 +290,40 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 || BM * BN >= 256 * 256 ? 1 
         float t_box[MAXT][4], t_score[MAXT], t_cls[MAXT];
 #pragma unroll
         for (int it = 0; it < MAXT; ++it) {
-#pragma clang fp contract(off)      // the decode below must round like k_decode_filter (y7t_post.hip is built without contraction): bit-equal candidates
             t_img[it] = -1;
             const int t = tid + it * 256;
             if (t >= BM * q.na) continue;
             const int pix = t / q.na, an = t - pix * q.na;
             const int m = m0 + pix;
             if (m >= p.M) continue;
-            const float* v = tile + pix * LD + an * q.no;
-            const float obj = 1.0f / (1.0f + expf(-v[4]));
-            if (!(obj > q.conf_thres)) continue;                  // xc = prediction[..., 4] > conf_thres
-            float best = -1.f; int bj = 0;
-            for (int c = 0; c < nc; ++c) {                        // x[:, 5:] *= x[:, 4:5]; conf, j = x[:, 5:].max(1)
-                const float sc = (1.0f / (1.0f + expf(-v[5 + c]))) * obj;
-                if (sc > best) { best = sc; bj = c; }
-            }
-            if (!(best > q.conf_thres)) continue;
-            const int b = m / HoWo2, rem = m - b * HoWo2, y = rem / q.nx, x = rem - y * q.nx;
-            const float sx = 1.0f / (1.0f + expf(-v[0])), sy = 1.0f / (1.0f + expf(-v[1]));
-            const float sw = 1.0f / (1.0f + expf(-v[2])), sh = 1.0f / (1.0f + expf(-v[3]));
-            const float cx = (sx * 2.f - 0.5f + (float)x) * q.stride, cy = (sy * 2.f - 0.5f + (float)y) * q.stride;
-            const float w = (sw * 2.f) * (sw * 2.f) * q.aw[an], h = (sh * 2.f) * (sh * 2.f) * q.ah[an];
-            t_box[it][0] = cx - w / 2; t_box[it][1] = cy - h / 2; t_box[it][2] = cx + w / 2; t_box[it][3] = cy + h / 2;   // xywh2xyxy
-            t_score[it] = best; t_cls[it] = (float)bj;
-            t_cidx[it] = q.row0 + (an * q.ny + y) * q.nx + x;
+            const float* v = tile + pix * LD + an * q.no;      // the row arithmetic: y7t_decode.h, shared with k_decode_filter -- bit-equal candidates
+            const float obj = y7t_sigmoid(v[4]);
+            if (!y7t_conf_passes(obj, q.c.conf_thres)) continue;
+            const Y7TBest best = y7t_best_class(v, nc, obj);
+            if (!y7t_conf_passes(best.conf, q.c.conf_thres)) continue;
+            const int b = m / HoWo2, rem = m - b * HoWo2, y = rem / q.lv.nx, x = rem - y * q.lv.nx;
+            y7t_decode_box(v, x, y, an, q.lv, t_box[it]);
+            t_score[it] = best.conf; t_cls[it] = (float)best.cls;
+            t_cidx[it] = y7t_anchor_row(q.lv, an, y, x);
             t_img[it] = b - b0;
             t_rank[it] = atomicAdd(lcount + (b - b0), 1);
         }
         __syncthreads();
         for (int i = tid; i < BM; i += 256) {
             const int c = lcount[i];
-            lbase[i] = c > 0 ? atomicAdd(q.count + b0 + i, c) : 0;
+            lbase[i] = c > 0 ? atomicAdd(q.c.count + b0 + i, c) : 0;
         }
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < MAXT; ++it) {
             if (t_img[it] < 0) continue;
             const int b = b0 + t_img[it], slot = lbase[t_img[it]] + t_rank[it];
-            if (slot >= q.cap) continue;
-            float* bo = q.cbox + ((size_t)b * q.cap + slot) * 4;
+            if (slot >= q.c.cap) continue;
+            float* bo = q.c.cbox + ((size_t)b * q.c.cap + slot) * 4;
             bo[0] = t_box[it][0]; bo[1] = t_box[it][1]; bo[2] = t_box[it][2]; bo[3] = t_box[it][3];
-            q.cscore[(size_t)b * q.cap + slot] = t_score[it];
-            q.ccls[(size_t)b * q.cap + slot] = t_cls[it];
-            q.cidx[(size_t)b * q.cap + slot] = t_cidx[it];
+            q.c.cscore[(size_t)b * q.c.cap + slot] = t_score[it];
+            q.c.ccls[(size_t)b * q.c.cap + slot] = t_cls[it];
+            q.c.cidx[(size_t)b * q.c.cap + slot] = t_cidx[it];
         }
         return;
     }

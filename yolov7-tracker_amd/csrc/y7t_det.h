@@ -5,14 +5,28 @@
 
 enum { Y7T_ACT_NONE = 0, Y7T_ACT_SILU = 1, Y7T_ACT_LEAKY = 2 };
 
-// Detect decode fused into the 1x1 conv's epilogue (y7t_det_forward_fused): level parameters + where the candidates go
-struct Y7TDecode {
+// One Detect level's geometry (the arithmetic on it: y7t_decode.h; y7t_level fills it)
+struct Y7TLevel {
     float stride, aw[3], ah[3];   // models/yolo.py:52-53: xy = (s*2 - 0.5 + grid) * stride; wh = (s*2)^2 * anchor_grid
-    int ny, nx, row0, na, no;     // row0: first row of this level in the reference's (B, A, no) ordering
-    float conf_thres;
+    int ny, nx, row0;             // row0: first row of this level in the reference's (B, A, no) ordering
+};
+// level l of a head with `na` anchors per cell: row0 is the sum over the finer levels (models/yolo.py:57 cat order); anchors: [nl][na][2] in pixels
+Y7TLevel y7t_level(int l, int na, const int* ny, const int* nx, const float* stride, const float* anchors);
+
+// The candidate arrays: the head of a postprocess workspace (y7t_post_ws), written by the decode pass or by the fused Detect epilogues.  (Member order, here and in
+// Y7TLevel: the bytes of Y7TDecode inside Y7TConvArgs stay where the measured conv kernels' argument loads expect them, profiles/post_decode_refactor_isa.txt.)
+struct Y7TCand {
+    float conf_thres;             // what a decode pass admits (y7t_post_ws leaves it 0: the pass's caller sets it)
     int cap;                      // candidate capacity per image
     float *cbox, *cscore, *ccls;  // [B][cap][4] xyxy, [B][cap], [B][cap]
-    int *cidx, *count;            // [B][cap] row index, [B] candidates found
+    int *cidx, *count;            // [B][cap] row index (tie-break / parity checks), [B] candidates found (may exceed cap -> overflow)
+};
+
+// Detect decode fused into the 1x1 conv's epilogue (y7t_det_forward_fused): the level + where the candidates go
+struct Y7TDecode {
+    Y7TLevel lv;
+    int na, no;
+    Y7TCand c;
 };
 
 struct Y7TConvArgs {
@@ -90,8 +104,16 @@ struct Y7TPostArgs {
     int filter_classes;     // keep the candidates whose class has its bit in class_mask (general.py:662-663)
     uint32_t class_mask[8]; // Y7T_NMS_MASK_WORDS: bit c % 32 of word c / 32 = class c
 };
-size_t y7t_post_ws_bytes(int B, int cap, int max_nms);
-// the candidate arrays at the start of a postprocess workspace (shared with the fused Detect epilogue)
-struct Y7TCandWs { float *cbox, *cscore, *ccls; int *cidx, *count; };
-Y7TCandWs y7t_post_cand_ws(void* ws, int B, int cap);
+// THE layout of a postprocess workspace: every array 256-byte aligned, in this order.  `total` is what a workspace needs (also on a null base: nothing is
+// dereferenced); the candidate arrays come first (the fused Detect epilogues fill them; Detector.candidate_arrays of detector/model.py restates their offsets)
+struct Y7TPostWs {
+    Y7TCand cand;
+    int* nsorted;           // [B]
+    float* sbox;            // [B][mcap][4] class-offset boxes in rank order; mcap = min(cap, max_nms): NMS runs on the top max_nms candidates only (general.py:664-665)
+    int* sorder;            // [B][mcap] candidate slot of each rank
+    float* lb;              // [B][5] letterbox parameters
+    int mcap;
+    size_t total;
+};
+Y7TPostWs y7t_post_ws(void* base, int B, int cap, int max_nms);
 int y7t_post_run(const Y7TPostArgs& a, hipStream_t s);

@@ -29,8 +29,6 @@ struct y7t_det {
     float stride[4] = {0, 0, 0, 0}, anchors[24] = {0};
 };
 
-struct Y7TFused { float conf_thres; int cap; Y7TCandWs ws; };
-
 extern "C" int y7t_det_create(const y7t_op* ops, int n_ops, const int64_t* bufs, int n_bufs, void* arena, size_t arena_bytes,
                               const void* w, const void* bias, int max_batch, y7t_det** out) {
     Y7T_ARG_CHECK(ops && n_ops > 0 && bufs && n_bufs > 0 && arena && w && bias && out && max_batch > 0);
@@ -90,7 +88,7 @@ extern "C" int y7t_det_num_ops(const y7t_det* d) { return d ? (int)d->ops.size()
 
 extern "C" int y7t_det_forward(y7t_det* d, int B, y7t_stream stream) { return y7t_det_forward_ops(d, B, 0, -1, stream); }
 
-static int forward_impl(y7t_det* d, int B, int first, int last, const Y7TFused* fused, hipStream_t s) {
+static int forward_impl(y7t_det* d, int B, int first, int last, const Y7TCand* fused, hipStream_t s) {
     Y7T_ARG_CHECK(d && B > 0 && B <= d->max_batch);
     if (last < 0) last = (int)d->ops.size();
     Y7T_ARG_CHECK(first >= 0 && first <= last && last <= (int)d->ops.size());
@@ -125,15 +123,12 @@ static int forward_impl(y7t_det* d, int B, int first, int last, const Y7TFused* 
                 const int l = op.detect_level;
                 if (l >= d->nl || op.Cout != d->na * d->no) { y7t_set_error("fused Detect: level %d not described by y7t_det_set_detect", l); return Y7T_E_STATE; }
                 a.epi = 1;
-                Y7TDecode& q = a.dec;
-                q.stride = d->stride[l]; q.ny = op.Ho; q.nx = op.Wo; q.na = d->na; q.no = d->no;
-                q.row0 = 0;
-                for (int k = 0; k < (int)d->ops.size(); ++k)    // rows of the finer levels come first (models/yolo.py:57 cat order)
-                    if (d->ops[k].type == Y7T_OP_CONV && d->ops[k].detect_level >= 0 && d->ops[k].detect_level < l)
-                        q.row0 += d->na * d->ops[k].Ho * d->ops[k].Wo;
-                for (int k = 0; k < d->na; ++k) { q.aw[k] = d->anchors[(l * d->na + k) * 2]; q.ah[k] = d->anchors[(l * d->na + k) * 2 + 1]; }
-                q.conf_thres = fused->conf_thres; q.cap = fused->cap;
-                q.cbox = fused->ws.cbox; q.cscore = fused->ws.cscore; q.ccls = fused->ws.ccls; q.cidx = fused->ws.cidx; q.count = fused->ws.count;
+                int ny[4] = {0, 0, 0, 0}, nx[4] = {0, 0, 0, 0};      // the levels' maps, from the plan's Detect convs
+                for (const y7t_op& o : d->ops)
+                    if (o.type == Y7T_OP_CONV && o.detect_level >= 0 && o.detect_level < d->nl) { ny[o.detect_level] = o.Ho; nx[o.detect_level] = o.Wo; }
+                a.dec.lv = y7t_level(l, d->na, ny, nx, d->stride, d->anchors);
+                a.dec.c = *fused;
+                a.dec.na = d->na; a.dec.no = d->no;
             }
             // frames per launch: the kernels address a tensor through 32-bit byte offsets (2 GiB); a batch whose input or output tensor is larger goes out as several launches
             // over consecutive runs of frames (batch-major NHWC: a run of frames is a contiguous piece of every tensor of the op) -- the 640^2 / 320^2 layers of w6 @ 1280
@@ -228,15 +223,16 @@ extern "C" int y7t_det_forward_fused(y7t_det* d, int B, int first, int last, flo
                                      y7t_stream stream) {
     Y7T_ARG_CHECK(d && ws && cap >= 64 && max_nms >= 1 && B > 0 && B <= d->max_batch);
     Y7T_ARG_CHECK(d->nl > 0);
-    Y7T_ARG_CHECK(ws_bytes >= y7t_post_ws_bytes(B, cap, max_nms));
-    Y7TFused f;
-    f.conf_thres = conf_thres; f.cap = cap; f.ws = y7t_post_cand_ws(ws, B, cap);
-    if (first == 0) Y7T_HIP_CHECK(hipMemsetAsync(f.ws.count, 0, sizeof(int) * B, (hipStream_t)stream));
+    const Y7TPostWs w = y7t_post_ws(ws, B, cap, max_nms);
+    Y7T_ARG_CHECK(ws_bytes >= w.total);
+    Y7TCand f = w.cand;
+    f.conf_thres = conf_thres;
+    if (first == 0) Y7T_HIP_CHECK(hipMemsetAsync(f.count, 0, sizeof(int) * B, (hipStream_t)stream));
     return forward_impl(d, B, first, last, &f, (hipStream_t)stream);
 }
 
 extern "C" size_t y7t_det_postprocess_workspace_bytes(int B, int cap, int max_nms) {
-    return (B > 0 && cap > 0 && max_nms > 0) ? y7t_post_ws_bytes(B, cap, max_nms) : 0;
+    return (B > 0 && cap > 0 && max_nms > 0) ? y7t_post_ws(nullptr, B, cap, max_nms).total : 0;
 }
 
 extern "C" int y7t_det_postprocess(const float* const* head, const int* ny, const int* nx, const float* strides, const float* anchors, int nl,

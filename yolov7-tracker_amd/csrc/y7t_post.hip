@@ -8,9 +8,11 @@
 //     (utils/general.py:607-665), rank sort by confidence, class-offset bitmask NMS with torchvision's greedy
 //     semantics (general.py:676-682), top-300, scale_coords + clip + round (general.py:319-340, tracker/track.py:234-244);
 //     with y7t_nms_opts: the multi-label form of the decode pass (general.py:654-656), the class filter (:662-663) and the agnostic offset (:677) in the rank sort
+//     (k_rank_sort<true>).  The decode's row arithmetic is y7t_decode.h, shared with the Detect epilogue of y7t_conv.hip; a level and the candidate arrays are
+//     described by Y7TLevel / Y7TCand (y7t_det.h), and y7t_post_ws below is the one layout of the workspace
 #include "y7t_common.h"
 #include <stdlib.h>
-#include "y7t_det.h"
+#include "y7t_decode.h"
 #include <string.h>
 
 typedef _Float16 half_t;
@@ -359,28 +361,20 @@ extern "C" int y7t_letterbox_layout_u8(const void* img, int B, int H0, int W0, i
 }
 
 // ------------------------------------------------------------------------------------------------ decode + filter
+// The row arithmetic of the two kernels below is y7t_decode.h's (shared with the Detect epilogue of y7t_conv.hip); theirs is the walk over the rows and the slots.
 struct DecodeLevel {
-    const float* p;   // head conv output, NHWC fp32: [B][ny][nx][na*no]
-    int ny, nx, row0; // row0: index of this level's first row in the reference's (B, A, no) ordering
-    float stride;
-    float aw[3], ah[3];
+    const float* p;       // head conv output, NHWC fp32: [B][ny][nx][na*no]
+    Y7TLevel g;
 };
 struct DecodeArgs {
     DecodeLevel lv[4];
-    int nl, na, no, B;
-    float conf_thres;
-    int cap;              // candidate capacity per image
-    float* cbox;          // [B][cap][4] xyxy
-    float* cscore;        // [B][cap]
-    float* ccls;          // [B][cap]
-    int* cidx;            // [B][cap] row index (tie-break / parity checks)
-    int* count;           // [B] candidates found (may exceed cap -> overflow)
+    int na, no, B;
+    Y7TCand c;
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __global__ void __launch_bounds__(256) k_decode_filter(const DecodeArgs a, int level) {
-    const DecodeLevel L = a.lv[level];
+    const DecodeLevel lv = a.lv[level];
+    const Y7TLevel& L = lv.g;
     const int per_img = a.na * L.ny * L.nx;
     const long long tot = (long long)a.B * per_img;
     const int nc = a.no - 5;
@@ -388,25 +382,19 @@ __global__ void __launch_bounds__(256) k_decode_filter(const DecodeArgs a, int l
         const int b = (int)(t / per_img), r = (int)(t - (long long)b * per_img);
         // thread order: x fastest, then anchor, then y -> neighbouring threads read neighbouring NHWC rows
         const int x = r % L.nx, an = (r / L.nx) % a.na, y = r / (L.nx * a.na);
-        const float* p = L.p + ((((size_t)b * L.ny + y) * L.nx + x) * a.na + an) * a.no;
-        const float obj = sigmoidf_(p[4]);
-        if (!(obj > a.conf_thres)) continue;                  // xc = prediction[..., 4] > conf_thres
-        float best = -1.f; int bj = 0;
-        for (int c = 0; c < nc; ++c) {                        // x[:, 5:] *= x[:, 4:5]; conf, j = x[:, 5:].max(1)
-            const float s = sigmoidf_(p[5 + c]) * obj;
-            if (s > best) { best = s; bj = c; }
-        }
-        if (!(best > a.conf_thres)) continue;
-        const float sx = sigmoidf_(p[0]), sy = sigmoidf_(p[1]), sw = sigmoidf_(p[2]), sh = sigmoidf_(p[3]);
-        const float cx = (sx * 2.f - 0.5f + (float)x) * L.stride, cy = (sy * 2.f - 0.5f + (float)y) * L.stride;
-        const float w = (sw * 2.f) * (sw * 2.f) * L.aw[an], h = (sh * 2.f) * (sh * 2.f) * L.ah[an];
-        const int slot = atomicAdd(a.count + b, 1);
-        if (slot >= a.cap) continue;
-        float* bo = a.cbox + ((size_t)b * a.cap + slot) * 4;
-        bo[0] = cx - w / 2; bo[1] = cy - h / 2; bo[2] = cx + w / 2; bo[3] = cy + h / 2;   // xywh2xyxy
-        a.cscore[(size_t)b * a.cap + slot] = best;
-        a.ccls[(size_t)b * a.cap + slot] = (float)bj;
-        a.cidx[(size_t)b * a.cap + slot] = L.row0 + (an * L.ny + y) * L.nx + x;
+        const float* p = lv.p + ((((size_t)b * L.ny + y) * L.nx + x) * a.na + an) * a.no;
+        const float obj = y7t_sigmoid(p[4]);
+        if (!y7t_conf_passes(obj, a.c.conf_thres)) continue;
+        const Y7TBest best = y7t_best_class(p, nc, obj);
+        if (!y7t_conf_passes(best.conf, a.c.conf_thres)) continue;
+        float c[4];
+        y7t_decode_xywh(p, x, y, an, L, c);
+        const int slot = atomicAdd(a.c.count + b, 1);
+        if (slot >= a.c.cap) continue;
+        y7t_xywh2xyxy(c, a.c.cbox + ((size_t)b * a.c.cap + slot) * 4);
+        a.c.cscore[(size_t)b * a.c.cap + slot] = best.conf;
+        a.c.ccls[(size_t)b * a.c.cap + slot] = (float)best.cls;
+        a.c.cidx[(size_t)b * a.c.cap + slot] = y7t_anchor_row(L, an, y, x);
     }
 }
 
@@ -419,7 +407,8 @@ __global__ void __launch_bounds__(256) k_decode_filter(const DecodeArgs a, int l
 // The loop is uniform over the workgroup (whole strips of 256 rows, `live` masks the tail), so the scan's cross-lane reads run with every lane active.
 // Slot order inside a row is class ascending; cap cuts a reservation that straddles it: the slots below cap are written, the others are not.
 __global__ void __launch_bounds__(256) k_decode_filter_ml(const DecodeArgs a, int level) {
-    const DecodeLevel L = a.lv[level];
+    const DecodeLevel lv = a.lv[level];
+    const Y7TLevel& L = lv.g;
     const int per_img = a.na * L.ny * L.nx;
     const long long tot = (long long)a.B * per_img;
     const int nc = a.no - 5;
@@ -429,13 +418,13 @@ __global__ void __launch_bounds__(256) k_decode_filter_ml(const DecodeArgs a, in
         const bool live = t < tot;
         const int b = live ? (int)(t / per_img) : -1, r = live ? (int)(t - (long long)b * per_img) : 0;
         const int x = r % L.nx, an = (r / L.nx) % a.na, y = r / (L.nx * a.na);
-        const float* p = L.p + ((((size_t)(live ? b : 0) * L.ny + y) * L.nx + x) * a.na + an) * a.no;
+        const float* p = lv.p + ((((size_t)(live ? b : 0) * L.ny + y) * L.nx + x) * a.na + an) * a.no;
         float obj = 0.f;
         int k = 0;
         if (live) {
-            obj = sigmoidf_(p[4]);
-            if (obj > a.conf_thres)                               // xc = prediction[..., 4] > conf_thres
-                for (int c = 0; c < nc; ++c) k += (sigmoidf_(p[5 + c]) * obj > a.conf_thres) ? 1 : 0;      // x[:, 5:] *= x[:, 4:5]; (x[:, 5:] > conf_thres)
+            obj = y7t_sigmoid(p[4]);
+            if (y7t_conf_passes(obj, a.c.conf_thres))
+                for (int c = 0; c < nc; ++c) k += y7t_conf_passes(y7t_class_conf(p, c, obj), a.c.conf_thres) ? 1 : 0;      // (x[:, 5:] > conf_thres)
         }
         int slot = 0;
         unsigned long long pend = __ballot(k > 0);
@@ -451,27 +440,25 @@ __global__ void __launch_bounds__(256) k_decode_filter_ml(const DecodeArgs a, in
             }
             const int total = __shfl(incl, 63);
             int base = 0;
-            if (lane == src) base = atomicAdd(a.count + bb, total);
+            if (lane == src) base = atomicAdd(a.c.count + bb, total);
             base = __shfl(base, src);
             if (mine) slot = base + incl - k;
             pend &= ~__ballot(mine);
         }
-        if (k == 0 || slot >= a.cap) continue;
-        const float sx = sigmoidf_(p[0]), sy = sigmoidf_(p[1]), sw = sigmoidf_(p[2]), sh = sigmoidf_(p[3]);
-        const float cx = (sx * 2.f - 0.5f + (float)x) * L.stride, cy = (sy * 2.f - 0.5f + (float)y) * L.stride;
-        const float w = (sw * 2.f) * (sw * 2.f) * L.aw[an], h = (sh * 2.f) * (sh * 2.f) * L.ah[an];
-        const float x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2;      // xywh2xyxy
-        const int row = L.row0 + (an * L.ny + y) * L.nx + x;
-        const int end = slot + k < a.cap ? slot + k : a.cap;
-        for (int c = 0; c < nc && slot < end; ++c) {              // the same expression as the count above: the same k classes, in class order
-            const float s = sigmoidf_(p[5 + c]) * obj;
-            if (!(s > a.conf_thres)) continue;
-            const size_t o = (size_t)b * a.cap + slot;
-            float* bo = a.cbox + o * 4;
-            bo[0] = x1; bo[1] = y1; bo[2] = x2; bo[3] = y2;
-            a.cscore[o] = s;
-            a.ccls[o] = (float)c;
-            a.cidx[o] = row;
+        if (k == 0 || slot >= a.c.cap) continue;
+        float box[4];
+        y7t_decode_box(p, x, y, an, L, box);
+        const int row = y7t_anchor_row(L, an, y, x);
+        const int end = slot + k < a.c.cap ? slot + k : a.c.cap;
+        for (int c = 0; c < nc && slot < end; ++c) {              // the same function as the count above: the same k classes, in class order
+            const float s = y7t_class_conf(p, c, obj);
+            if (!y7t_conf_passes(s, a.c.conf_thres)) continue;
+            const size_t o = (size_t)b * a.c.cap + slot;
+            float* bo = a.c.cbox + o * 4;
+            bo[0] = box[0]; bo[1] = box[1]; bo[2] = box[2]; bo[3] = box[3];
+            a.c.cscore[o] = s;
+            a.c.ccls[o] = (float)c;
+            a.c.cidx[o] = row;
             ++slot;
         }
     }
@@ -487,95 +474,61 @@ struct SortOpts {
     int nc_key;           // multi_label: the candidates of a row share cidx, the key's low word is row * nc_key + class; 0: the row alone
 };
 
-// rank by (score desc, row index asc); scatter class-offset boxes (x[:, :4] + cls*4096) into sorted order
+// rank by (score desc, row index asc); scatter class-offset boxes (x[:, :4] + cls*4096) into sorted order.
+// OPTS = false: the tracking path's kernel; it never reads so_.  OPTS = true adds what y7t_nms_opts asks for around the same ranking loop: key_of (a masked-out
+// candidate is key 0; multi_label keys carry row * nc + class), nsorted -- the number of candidates that PASSED the mask: block 0 of an image counts the non-zero keys
+// it stages through LDS, every candidate's key passes through exactly one of its threads -- and the scatter, which skips key 0 and leaves the class offset out when
+// agnostic.
+template <bool OPTS>
 __global__ void __launch_bounds__(256) k_rank_sort(const float* __restrict__ cbox, const float* __restrict__ cscore, const float* __restrict__ ccls,
                                                    const int* __restrict__ cidx, const int* __restrict__ count, int cap, int max_nms,
-                                                   float* __restrict__ sbox, int* __restrict__ sorder, int* __restrict__ nsorted, int mcap) {
+                                                   float* __restrict__ sbox, int* __restrict__ sorder, int* __restrict__ nsorted, int mcap, const SortOpts so_) {
     // round 6: (score desc, row index asc) as ONE unsigned 64-bit key -- the score's bit pattern (scores are positive floats: their bit patterns order like their
     // values) over the complement of the row index -- so a comparison is one LDS read and one 64-bit compare instead of two reads and three compares (k_rank_sort at one
     // frame: 52 us of the batch-1 frame).  Keys are unique (row indices are), so `>` alone gives the rank; an empty slot has key 0 and outranks nothing.
     __shared__ unsigned long long sk[256];
+    [[maybe_unused]] __shared__ int s_passed;      // (OPTS only; no LDS where nothing uses it)
     const int b = blockIdx.y;
     int n = count[b]; if (n > cap) n = cap;
     const int i = blockIdx.x * 256 + threadIdx.x;
     // published for EVERY image, before the early return: block 0 of an image without candidates leaves here too, and k_nms_keep would otherwise walk whatever the
     // previous call on this workspace sorted (nothing else resets nsorted) and report that frame's detections for an empty one
-    if (i == 0) nsorted[b] = n < max_nms ? n : max_nms;
-    if (blockIdx.x * 256 >= n) return;
-    const float* sc = cscore + (size_t)b * cap;
-    const int* ix = cidx + (size_t)b * cap;
-    auto key_of = [&](int j) -> unsigned long long {
-        const float v = sc[j];
-        if (!(v > 0.f)) return 0ull;      // (not a candidate score: conf_thres > 0 keeps every real one positive; NaN sorts last)
-        return ((unsigned long long)__builtin_bit_cast(unsigned, v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)ix[j]);
-    };
-    const unsigned long long my_k = i < n ? key_of(i) : 0ull;
-    int rank = 0;
-    unsigned long long nxt = (int)threadIdx.x < n ? key_of(threadIdx.x) : 0ull;      // the next chunk's key: its two global loads are in flight while the current chunk is compared
-    for (int base = 0; base < n; base += 256) {
-        __syncthreads();
-        sk[threadIdx.x] = nxt;
-        __syncthreads();
-        const int jn = base + 256 + threadIdx.x;
-        nxt = jn < n ? key_of(jn) : 0ull;
-        const int lim = (n - base) < 256 ? (n - base) : 256;
-        if (lim == 256) {
-#pragma unroll 8
-            for (int t = 0; t < 256; ++t) rank += sk[t] > my_k;
-        } else {
-            for (int t = 0; t < lim; ++t) rank += sk[t] > my_k;
-        }
+    if constexpr (OPTS) {
+        if (i == 0 && n == 0) nsorted[b] = 0;      // (with candidates, block 0 publishes the number that passed the mask at its end)
+    } else {
+        if (i == 0) nsorted[b] = n < max_nms ? n : max_nms;
     }
-    if (i < n && rank < max_nms) {
-        const float off = ccls[(size_t)b * cap + i] * 4096.f;
-        const float* bo = cbox + ((size_t)b * cap + i) * 4;
-        float* so = sbox + ((size_t)b * mcap + rank) * 4;
-        so[0] = bo[0] + off; so[1] = bo[1] + off; so[2] = bo[2] + off; so[3] = bo[3] + off;
-        sorder[(size_t)b * mcap + rank] = i;
-    }
-}
-
-// k_rank_sort with y7t_nms_opts: the class mask, (row, class) keys, the agnostic offset.  A sibling, so that the tracking path's kernel above stays the code that was
-// measured; the ranking loop is the same.  What differs: key_of (a masked-out candidate is key 0; multi_label keys carry row * nc + class), nsorted -- the number of
-// candidates that PASSED the mask: block 0 of an image counts the non-zero keys it stages through LDS, every candidate's key passes through exactly one of its
-// threads -- and the scatter, which skips key 0 and leaves the class offset out when agnostic.
-__global__ void __launch_bounds__(256) k_rank_sort_opts(const float* __restrict__ cbox, const float* __restrict__ cscore, const float* __restrict__ ccls,
-                                                        const int* __restrict__ cidx, const int* __restrict__ count, int cap, int max_nms,
-                                                        float* __restrict__ sbox, int* __restrict__ sorder, int* __restrict__ nsorted, int mcap, const SortOpts so_) {
-    __shared__ unsigned long long sk[256];
-    __shared__ int s_passed;
-    const int b = blockIdx.y;
-    int n = count[b]; if (n > cap) n = cap;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0 && n == 0) nsorted[b] = 0;      // (an image without candidates: block 0 leaves below; with candidates it publishes the number that passed the mask at its end)
     if (blockIdx.x * 256 >= n) return;
     const float* sc = cscore + (size_t)b * cap;
     const float* cl = ccls + (size_t)b * cap;
     const int* ix = cidx + (size_t)b * cap;
-    const unsigned kmul = so_.nc_key ? (unsigned)so_.nc_key : 1u;
+    [[maybe_unused]] const unsigned kmul = so_.nc_key ? (unsigned)so_.nc_key : 1u;
     auto key_of = [&](int j) -> unsigned long long {
         const float v = sc[j];
-        if (!(v > 0.f)) return 0ull;
+        if (!(v > 0.f)) return 0ull;      // (not a candidate score: conf_thres > 0 keeps every real one positive; NaN sorts last)
         unsigned low = (unsigned)ix[j];
-        if (so_.filter || so_.nc_key) {
-            const int c = (int)cl[j];
-            if (so_.filter) {
-                unsigned w = 0u;      // mask[c / 32] as a chain of selects: the mask stays in scalar registers (a divergent index would move it to scratch)
+        if constexpr (OPTS) {
+            if (so_.filter || so_.nc_key) {
+                const int c = (int)cl[j];
+                if (so_.filter) {
+                    unsigned w = 0u;      // mask[c / 32] as a chain of selects: the mask stays in scalar registers (a divergent index would move it to scratch)
 #pragma unroll
-                for (int q = 0; q < 8; ++q) w = (c >> 5) == q ? so_.mask[q] : w;
-                if (!((w >> (c & 31)) & 1u)) return 0ull;
+                    for (int q = 0; q < 8; ++q) w = (c >> 5) == q ? so_.mask[q] : w;
+                    if (!((w >> (c & 31)) & 1u)) return 0ull;
+                }
+                low = low * kmul + (so_.nc_key ? (unsigned)c : 0u);
             }
-            low = low * kmul + (so_.nc_key ? (unsigned)c : 0u);
         }
         return ((unsigned long long)__builtin_bit_cast(unsigned, v) << 32) | (unsigned long long)(0xFFFFFFFFu - low);
     };
     const unsigned long long my_k = i < n ? key_of(i) : 0ull;
-    int rank = 0, passed = 0;
-    unsigned long long nxt = (int)threadIdx.x < n ? key_of(threadIdx.x) : 0ull;
+    int rank = 0;
+    [[maybe_unused]] int passed = 0;
+    unsigned long long nxt = (int)threadIdx.x < n ? key_of(threadIdx.x) : 0ull;      // the next chunk's key: its two global loads are in flight while the current chunk is compared
     for (int base = 0; base < n; base += 256) {
         __syncthreads();
         sk[threadIdx.x] = nxt;
-        passed += nxt != 0ull;
+        if constexpr (OPTS) passed += nxt != 0ull;
         __syncthreads();
         const int jn = base + 256 + threadIdx.x;
         nxt = jn < n ? key_of(jn) : 0ull;
@@ -587,15 +540,18 @@ __global__ void __launch_bounds__(256) k_rank_sort_opts(const float* __restrict_
             for (int t = 0; t < lim; ++t) rank += sk[t] > my_k;
         }
     }
-    if (blockIdx.x == 0) {      // (uniform over the workgroup)
-        if (threadIdx.x == 0) s_passed = 0;
-        __syncthreads();
-        if (passed) atomicAdd(&s_passed, passed);
-        __syncthreads();
-        if (threadIdx.x == 0) nsorted[b] = s_passed < max_nms ? s_passed : max_nms;
+    if constexpr (OPTS) {
+        if (blockIdx.x == 0) {      // (uniform over the workgroup)
+            if (threadIdx.x == 0) s_passed = 0;
+            __syncthreads();
+            if (passed) atomicAdd(&s_passed, passed);
+            __syncthreads();
+            if (threadIdx.x == 0) nsorted[b] = s_passed < max_nms ? s_passed : max_nms;
+        }
     }
-    if (i < n && my_k != 0ull && rank < max_nms) {
-        const float off = so_.agnostic ? 0.f : cl[i] * 4096.f;
+    if (i < n && (!OPTS || my_k != 0ull) && rank < max_nms) {
+        // (one address, spelled as each instance's compiled code had it before the two kernels became one: the keys of OPTS read through cl anyway)
+        const float off = OPTS ? (so_.agnostic ? 0.f : cl[i] * 4096.f) : ccls[(size_t)b * cap + i] * 4096.f;
         const float* bo = cbox + ((size_t)b * cap + i) * 4;
         float* so = sbox + ((size_t)b * mcap + rank) * 4;
         so[0] = bo[0] + off; so[1] = bo[1] + off; so[2] = bo[2] + off; so[3] = bo[3] + off;
@@ -756,28 +712,32 @@ __global__ void __launch_bounds__(256) k_nms_keep(const float* __restrict__ sbox
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-size_t y7t_post_ws_bytes(int B, int cap, int max_nms) {
-    const size_t mcap = (size_t)(cap < max_nms ? cap : max_nms);    // NMS runs on the top max_nms candidates only (general.py:664-665)
+Y7TPostWs y7t_post_ws(void* base, int B, int cap, int max_nms) {
     size_t o = 0;
-    auto take = [&](size_t bytes) { o = (o + bytes + 255) & ~(size_t)255; };
-    take((size_t)B * cap * 16); take((size_t)B * cap * 4); take((size_t)B * cap * 4); take((size_t)B * cap * 4);  // cbox cscore ccls cidx
-    take((size_t)B * 4); take((size_t)B * 4);                                                                    // count nsorted
-    take((size_t)B * mcap * 16); take((size_t)B * mcap * 4);                                                     // sbox sorder
-    take((size_t)B * 5 * 4);                                                                                     // letterbox params
-    return o + 256;
+    auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = (o + bytes + 255) & ~(size_t)255; return p; };
+    Y7TPostWs w;
+    w.mcap = cap < max_nms ? cap : max_nms;
+    w.cand.cbox = (float*)take((size_t)B * cap * 16);
+    w.cand.cscore = (float*)take((size_t)B * cap * 4);
+    w.cand.ccls = (float*)take((size_t)B * cap * 4);
+    w.cand.cidx = (int*)take((size_t)B * cap * 4);
+    w.cand.count = (int*)take((size_t)B * 4);
+    w.cand.cap = cap; w.cand.conf_thres = 0.f;
+    w.nsorted = (int*)take((size_t)B * 4);
+    w.sbox = (float*)take((size_t)B * w.mcap * 16);
+    w.sorder = (int*)take((size_t)B * w.mcap * 4);
+    w.lb = (float*)take((size_t)B * 5 * 4);
+    w.total = o + 256;
+    return w;
 }
 
-Y7TCandWs y7t_post_cand_ws(void* ws, int B, int cap) {
-    char* base = (char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base + o; o = (o + bytes + 255) & ~(size_t)255; return p; };
-    Y7TCandWs c;
-    c.cbox = (float*)take((size_t)B * cap * 16);
-    c.cscore = (float*)take((size_t)B * cap * 4);
-    c.ccls = (float*)take((size_t)B * cap * 4);
-    c.cidx = (int*)take((size_t)B * cap * 4);
-    c.count = (int*)take((size_t)B * 4);
-    return c;
+Y7TLevel y7t_level(int l, int na, const int* ny, const int* nx, const float* stride, const float* anchors) {
+    Y7TLevel L;
+    memset(&L, 0, sizeof(L));
+    L.ny = ny[l]; L.nx = nx[l]; L.stride = stride[l];
+    for (int f = 0; f < l; ++f) L.row0 += na * ny[f] * nx[f];
+    for (int k = 0; k < na; ++k) { L.aw[k] = anchors[(l * na + k) * 2]; L.ah[k] = anchors[(l * na + k) * 2 + 1]; }
+    return L;
 }
 
 int y7t_post_run(const Y7TPostArgs& a, hipStream_t s) {
@@ -787,52 +747,33 @@ int y7t_post_run(const Y7TPostArgs& a, hipStream_t s) {
                       a.max_det, (int)(60u * 1024u / (6 * sizeof(float))));
         return Y7T_E_ARG;
     }
-    const size_t mcap = (size_t)(cap < a.max_nms ? cap : a.max_nms);
-    char* base = (char*)a.ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base + o; o = (o + bytes + 255) & ~(size_t)255; return p; };
-    float* cbox = (float*)take((size_t)B * cap * 16);
-    float* cscore = (float*)take((size_t)B * cap * 4);
-    float* ccls = (float*)take((size_t)B * cap * 4);
-    int* cidx = (int*)take((size_t)B * cap * 4);
-    int* count = (int*)take((size_t)B * 4);
-    int* nsorted = (int*)take((size_t)B * 4);
-    float* sbox = (float*)take((size_t)B * mcap * 16);
-    int* sorder = (int*)take((size_t)B * mcap * 4);
-    float* lb = (float*)take((size_t)B * 5 * 4);
-    if (o + 256 > a.ws_bytes) { y7t_set_error("postprocess workspace too small (%zu < %zu)", a.ws_bytes, o + 256); return Y7T_E_ARG; }
-    if (!a.predecoded) Y7T_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int) * B, s));
-    Y7T_HIP_CHECK(hipMemcpyAsync(lb, a.letterbox_dev, sizeof(float) * 5 * B, hipMemcpyDeviceToDevice, s));
+    const Y7TPostWs w = y7t_post_ws(a.ws, B, cap, a.max_nms);
+    const Y7TCand& c = w.cand;
+    if (w.total > a.ws_bytes) { y7t_set_error("postprocess workspace too small (%zu < %zu)", a.ws_bytes, w.total); return Y7T_E_ARG; }
+    if (!a.predecoded) Y7T_HIP_CHECK(hipMemsetAsync(c.count, 0, sizeof(int) * B, s));
+    Y7T_HIP_CHECK(hipMemcpyAsync(w.lb, a.letterbox_dev, sizeof(float) * 5 * B, hipMemcpyDeviceToDevice, s));
     DecodeArgs d;
     memset(&d, 0, sizeof(d));
-    d.nl = a.nl; d.na = a.na; d.no = a.no; d.B = B; d.conf_thres = a.conf_thres; d.cap = cap;
-    d.cbox = cbox; d.cscore = cscore; d.ccls = ccls; d.cidx = cidx; d.count = count;
-    int row0 = 0;
-    for (int l = 0; l < a.nl; ++l) {
-        d.lv[l].p = a.head[l]; d.lv[l].ny = a.ny[l]; d.lv[l].nx = a.nx[l]; d.lv[l].stride = a.stride[l]; d.lv[l].row0 = row0;
-        for (int k = 0; k < a.na; ++k) { d.lv[l].aw[k] = a.anchors[(l * a.na + k) * 2]; d.lv[l].ah[k] = a.anchors[(l * a.na + k) * 2 + 1]; }
-        row0 += a.na * a.ny[l] * a.nx[l];
-    }
+    d.c = c; d.na = a.na; d.no = a.no; d.B = B; d.c.conf_thres = a.conf_thres;
     for (int l = 0; l < a.nl && !a.predecoded; ++l) {
+        d.lv[l].p = a.head[l];
+        d.lv[l].g = y7t_level(l, a.na, a.ny, a.nx, a.stride, a.anchors);
         const long long tot = (long long)B * a.na * a.ny[l] * a.nx[l];
         int blocks = (int)((tot + 255) / 256); if (blocks > 4096) blocks = 4096;
         if (a.multi_label) hipLaunchKernelGGL(k_decode_filter_ml, dim3(blocks), dim3(256), 0, s, d, l);
         else hipLaunchKernelGGL(k_decode_filter, dim3(blocks), dim3(256), 0, s, d, l);
         Y7T_LAUNCH_CHECK();
     }
-    if (a.agnostic || a.multi_label || a.filter_classes) {
-        SortOpts so;
-        for (int w = 0; w < 8; ++w) so.mask[w] = a.class_mask[w];
-        so.filter = a.filter_classes; so.agnostic = a.agnostic; so.nc_key = a.multi_label ? a.no - 5 : 0;
-        hipLaunchKernelGGL(k_rank_sort_opts, dim3((cap + 255) / 256, B), dim3(256), 0, s, cbox, cscore, ccls, cidx, count, cap, a.max_nms, sbox, sorder, nsorted,
-                           (int)mcap, so);
-    } else {
-        hipLaunchKernelGGL(k_rank_sort, dim3((cap + 255) / 256, B), dim3(256), 0, s, cbox, cscore, ccls, cidx, count, cap, a.max_nms, sbox, sorder, nsorted, (int)mcap);
-    }
+    SortOpts so;      // (all zero on the tracking path, whose kernel does not read it)
+    for (int q = 0; q < 8; ++q) so.mask[q] = a.class_mask[q];
+    so.filter = a.filter_classes; so.agnostic = a.agnostic; so.nc_key = a.multi_label ? a.no - 5 : 0;
+    const auto rank_sort = (a.agnostic || a.multi_label || a.filter_classes) ? k_rank_sort<true> : k_rank_sort<false>;
+    hipLaunchKernelGGL(rank_sort, dim3((cap + 255) / 256, B), dim3(256), 0, s, c.cbox, c.cscore, c.ccls, c.cidx, c.count, cap, a.max_nms, w.sbox, w.sorder, w.nsorted,
+                       w.mcap, so);
     Y7T_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_nms_keep, dim3(B), dim3(256), (size_t)a.max_det * 6 * sizeof(float), s, sbox, nsorted, sorder, cbox, cscore, ccls, cap, (int)mcap,
-                       a.iou_thres, a.max_det, lb, a.dets, a.ndets, a.keep_idx);
+    hipLaunchKernelGGL(k_nms_keep, dim3(B), dim3(256), (size_t)a.max_det * 6 * sizeof(float), s, w.sbox, w.nsorted, w.sorder, c.cbox, c.cscore, c.ccls, cap, w.mcap,
+                       a.iou_thres, a.max_det, w.lb, a.dets, a.ndets, a.keep_idx);
     Y7T_LAUNCH_CHECK();
-    if (a.count_out) Y7T_HIP_CHECK(hipMemcpyAsync(a.count_out, count, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
+    if (a.count_out) Y7T_HIP_CHECK(hipMemcpyAsync(a.count_out, c.count, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
     return 0;
 }

@@ -433,7 +433,7 @@ class Detector:
             p.lb[:B].copy_(torch.from_numpy(lb))
             p._lb_key = key
         ps = p.post[out.pset]
-        ps.last_B = B                    # the workspace arrays are laid out for THIS batch (y7t_post_cand_ws): candidate_arrays needs it
+        ps.last_B = B                    # the workspace arrays are laid out for THIS batch (y7t_post_ws): candidate_arrays needs it
         if out.fused is not None:
             if abs(float(conf_thres) - float(out.fused)) > 1e-12:
                 raise ValueError("this forward fused the Detect decode with conf_thres=%g; post-processing it with %g needs a plain forward"
@@ -459,7 +459,8 @@ class Detector:
         -> (cbox (B, cap, 4) f32 xyxy, cscore (B, cap) f32, ccls (B, cap) f32, cidx (B, cap) i32 anchor row, count (B,) i32).  What the fused Detect
         epilogues / the decode pass wrote = `x` of utils/general.py:662 before the NMS; for parity checks and callers that want raw candidates."""
         p = self.plan
-        # y7t_post_cand_ws lays the arrays out with the batch of the forward / post-process that filled them, not with max_batch (ADVICE r3)
+        # mirrors the first five arrays of y7t_post_ws (csrc/y7t_post.hip), the one place the C side lays a workspace out (tests/test_postprocess_gpu.py holds the two
+        # together); it lays them out with the batch of the forward / post-process that filled them, not with max_batch (ADVICE r3)
         B = B if B is not None else getattr(p.post[pset], "last_B", self.max_batch)
         if not 1 <= B <= self.max_batch:
             raise ValueError("candidate_arrays: batch %d outside [1, %d]" % (B, self.max_batch))
