@@ -334,6 +334,40 @@ int y7t_aflink_score_pairs_f32(void* obj, const float* x1, const float* x2, int 
 int y7t_aflink_candidates(void* obj, const double* rows, const int* row_offsets, int n_tracklets, double thrT0, double thrT1, double thrS, int* pairs_out,
                           float* x1_out, float* x2_out, float* scores_out, int* count_out, int* status_out, y7t_stream stream);
 
+/* GSI, the Gaussian-smoothed interpolation of StrongSORT++ (the reference ships no GSI code: `use_GSI` is never read in tracker/strongsort.py; the procedure is
+ * this project's restatement of the StrongSORT release's GSI.py, DESIGN.md section 4 "GSI"): after a sequence, the short gaps a missed detection leaves in a
+ * track are filled linearly and every track is smoothed by a Gaussian-process regression over its frames.  float64 throughout; no atomics; results are
+ * bit-identical from call to call and a track's result does not depend on the other tracks.
+ *
+ * A table of tracks is `runs`: float64 rows [frame, x, y, w, h], the tracks' rows one run after the other, every run sorted by frame with no frame twice, and
+ * `offsets`: n_tracks + 1 int32, run k = rows [offsets[k], offsets[k + 1]).  Both in device memory.
+ *
+ * The GSI OBJECT is caller-owned device memory of y7t_gsi_workspace_bytes(max_tracks, max_rows, max_len) bytes at a 256-byte aligned address.  Capacities:
+ * 1 <= max_tracks <= 32768 = the tracks one group of launches takes (a longer table is taken in groups of max_tracks, with the same result), max_rows >= 1 = the
+ * rows of a table after interpolation, 1 <= max_len <= 4096 = the rows of its longest track after interpolation.  The workspace holds one integer a track and a
+ * pool of matrix slots for the tracks longer than 128 rows (at most 512 MiB); y7t_gsi_workspace_bytes returns 0 for capacities out of range.
+ * y7t_gsi_init / y7t_gsi_release: as for the AFLink object (release: the object's memory is about to be freed).
+ * y7t_gsi_interpolate: for consecutive rows of a track at frames f0 < f1 with f0 + 1 < f1 < f0 + interval every frame f in between receives a row, its x, y, w, h
+ *   = v0 + (v1 - v0) / (f1 - f0) * (f - f0) evaluated in exactly that order (no fused multiply-add).  runs_out (max_rows x 5 float64): the runs with their gaps
+ *   filled; offsets_out (n_tracks + 1 int32): their offsets; src_out (max_rows int32): for every output row the input row it is (a new row: the row at f0);
+ *   count_out (int32): the number of output rows; status_out (int32): bit 0 = more than max_rows output rows (the first max_rows are written), bit 1 = a track is
+ *   longer than max_len afterwards.  Everything stays on the device: asynchronous, no read-back.
+ * y7t_gsi_smooth: for every track of n rows at frames t, with its length scale len_scale[k] (float64, device; the release's is
+ *   clip(tau * log(tau^3 / n), 1 / tau, tau^2), computed by the caller): K[i][j] = exp(-0.5 * ((t_i - t_j) / len_scale)^2), A = K + reg I (reg = 1e-10 is
+ *   GaussianProcessRegressor's default), A = L L^T, a = A^-1 Y for Y = the columns x, y, w, h; out (rows x 4 float64) = K a.  `longest` = the rows of the longest
+ *   track as the caller knows them: above max_len the call is refused before any launch (Y7T_E_CAPACITY).  status_out: one int32 per track, 0 = smoothed;
+ *   bit 0 = a non-positive pivot, bit 1 = the track is longer than `longest`, bit 2 = no launch reached it (more rows than max_rows); with any bit set the
+ *   track's columns are copied to `out` as they came -- no NaN travels on.  Asynchronous, no read-back.
+ * Errors: Y7T_E_ARG (a null pointer, a misaligned or too small object, a capacity out of range, reg < 0), Y7T_E_STATE (an address y7t_gsi_init never saw),
+ * Y7T_E_CAPACITY (longest > max_len). */
+size_t y7t_gsi_workspace_bytes(int max_tracks, int max_rows, int max_len);
+int y7t_gsi_init(void* obj, size_t bytes, int max_tracks, int max_rows, int max_len, y7t_stream stream);
+int y7t_gsi_release(void* obj);
+int y7t_gsi_interpolate(void* obj, const double* runs, const int* offsets, int n_tracks, int interval, double* runs_out, int* offsets_out, int* src_out,
+                        int* count_out, int* status_out, y7t_stream stream);
+int y7t_gsi_smooth(void* obj, const double* runs, const int* offsets, const double* len_scale, int n_tracks, int longest, double reg, double* out,
+                   int* status_out, y7t_stream stream);
+
 /* byte offsets of the arrays inside a state blob, for host-side views (tracked_stracks, lost_stracks, ...).
  * names/offsets: see y7t_tracker_field_name(i); returns the number of fields. */
 int y7t_tracker_layout(int cap_tracks, int cap_dets, int64_t* offsets, int max_fields);

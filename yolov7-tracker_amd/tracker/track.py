@@ -179,6 +179,9 @@ def main(opts, cfgs):
         if aflink_weights is not None:      # (extension) --aflink: the rows that would have been written, linked; the file and TrackEval see the linked ids
             from . import aflink
             results = aflink.link_results(aflink_weights, results, max_pairs=opts.aflink_max_pairs)
+        if getattr(opts, 'gsi', False):      # (extension) --gsi: after --aflink (StrongSORT++'s order): short gaps filled, every track smoothed, before the file is written
+            from . import gsi
+            results = gsi.smooth_results(results, interval=opts.gsi_interval, tau=opts.gsi_tau)
         save_results(opts.results_root, folder_name, seq, results)
     print(f'average fps: {np.mean(seq_fps)}')
     if opts.track_eval and (synthetic or cfgs.get('TRACK_EVAL')):
@@ -264,6 +267,11 @@ def build_parser():
                         help="(extension) link fragmented tracklets after each sequence with AFLink (tracker/aflink.py): a PostLinker state dict file, or "
                              "random:aflink[:seed[:gain]]; default off")
     parser.add_argument('--aflink_max_pairs', type=int, default=65536, help='(extension) --aflink: capacity of the candidate pair list')
+    parser.add_argument('--gsi', action='store_true',
+                        help="(extension) after each sequence (and after --aflink), fill the gaps shorter than --gsi_interval frames linearly and smooth every track with "
+                             "GSI (tracker/gsi.py); the rows GSI adds are not filtered by --min_area again; default off")
+    parser.add_argument('--gsi_interval', type=int, default=20, help='(extension) --gsi: gaps of fewer than this many frames are filled')
+    parser.add_argument('--gsi_tau', type=float, default=10, help="(extension) --gsi: the smoother's time constant")
     parser.add_argument('--yolo_root', type=str, default='./', help="(extension) where ./<dataset>/test.txt of --data_format yolo lives (the reference: the working directory)")
     # the NMS arguments of the reference's detect.py:166-167 (non_max_suppression applies them before its max_nms / max_det cuts)
     parser.add_argument('--classes', nargs='+', type=int, default=None, help='(extension) filter by class: --classes 0, or --classes 0 2 3')
