@@ -528,6 +528,33 @@ int y7t_det_postprocess_ex(const float* const* head_host_array_of_dev_ptrs, cons
                            int max_nms, int cap, const float* letterbox, float* dets, int* ndets, int* keep_idx, int* cand_count,
                            void* workspace, size_t workspace_bytes, y7t_stream stream, const y7t_nms_opts* opts);
 
+/* Test-time augmentation: Model.forward(x, augment=True) (models/yolo.py:301-317) is three passes -- scales 1, 0.83, 0.67, the middle one flipped left-right --
+ * whose decoded rows, brought back to the first pass's coordinates, are concatenated before ONE non_max_suppression.  A pass is: its input (y7t_input_layout for
+ * ratio 1, y7t_tta_scale_layout otherwise), the plain launch list of the plan of its size (y7t_det_forward_ops), y7t_det_decode_append; after the last pass
+ * y7t_det_postprocess(_ex) with head == NULL on the same workspace.  Passes of one size share a plan and its arena, so a pass is decoded before the next one runs.
+ *
+ * y7t_tta_scale_layout: x.flip(flip) (0 none, 2 up-down, 3 left-right: the reference's dims) -> scale_img (utils/torch_utils.py:247-257): F.interpolate to
+ * hs x ws (bilinear, align_corners=False), pad right and bottom with 0.447 to Hp x Wp -> the input layout of y7t_input_layout (same img / is_u8 / reorg / ldout; a uint8
+ * frame is converted as there first), one launch, no intermediate image.  hs = int(H * ratio), Hp = ceil(H * ratio / gs) * gs, computed by the caller in doubles as the
+ * reference writes them.  float32 arithmetic in the order csrc/y7t_tta.h states; hs == H copies.  out: B x Hp x Wp (/ 2 with reorg) x ldout fp16, below 2 GiB. */
+int y7t_tta_scale_layout(const void* img, int is_u8, int B, int H, int W, int flip, int hs, int ws, int Hp, int Wp, int reorg, void* out_f16, int ldout,
+                         y7t_stream stream);
+
+/* The Detect decode + candidate filter of ONE pass (the decode pass of y7t_det_postprocess: obj > conf_thres, best class, conf > conf_thres), with the pass's transform
+ * between decode and xywh2xyxy -- xywh / scale (a float32 division), then x = flip_extent - x (flip 3) or y = flip_extent - y (flip 2); flip_extent is the FIRST pass's
+ * width or height -- APPENDED to the candidate arrays at the start of `workspace` (layout of y7t_det_postprocess; cap, max_nms as there) with row index
+ * row_base + (row inside the pass); row_base = the rows of the passes before (torch.cat(y, 1) order).  first_pass != 0 zeroes the candidate counters first; another pass
+ * leaves them.  Past cap the counter grows and nothing is written.  multi_label != 0 with more than one class: Y7T_E_STATE, that form is not built.  Asynchronous, capturable. */
+typedef struct y7t_tta_pass {
+    float scale;
+    int32_t flip;
+    float flip_extent;
+    int32_t row_base;
+} y7t_tta_pass;
+int y7t_det_decode_append(const float* const* head_host_array_of_dev_ptrs, const int* ny, const int* nx, const float* strides, const float* anchors, int nl,
+                          int na, int no, int B, float conf_thres, int cap, int max_nms, int multi_label, const y7t_tta_pass* pass, int first_pass,
+                          void* workspace, size_t workspace_bytes, y7t_stream stream);
+
 /* ---------------------------------------------------------------- ReID embedding (DeepSORT's appearance branch) ---- */
 /* DeepSORT.get_feature -> Extractor (tracker/deepsort.py:19-41, tracker/reid_models/deepsort_reid.py:112-153) with OSNet
  * (tracker/reid_models/OSNet.py:282-438) as the network: crops of the frame -> /255, bilinear resize to in_h x in_w (cv2.INTER_LINEAR

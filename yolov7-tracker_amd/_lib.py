@@ -111,6 +111,9 @@ SIGNATURES = {
                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "y7t_det_postprocess_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "y7t_tta_scale_layout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "y7t_det_decode_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int,
+                                      c_void_p, c_size_t, c_void_p]),
     "y7t_reid_create": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "y7t_reid_destroy": (c_int, [c_void_p]),
     "y7t_reid_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
@@ -200,6 +203,11 @@ def nms_opts(classes=None, agnostic=False, multi_label=False):
         if 0 <= c < 32 * NMS_MASK_WORDS:
             o.class_mask[c >> 5] |= 1 << (c & 31)
     return o
+
+
+class TtaPass(ctypes.Structure):
+    """y7t_tta_pass (include/y7t.h): one pass's de-scale / de-flip and the first row of its anchors in the concatenation"""
+    _fields_ = [("scale", ctypes.c_float), ("flip", ctypes.c_int32), ("flip_extent", ctypes.c_float), ("row_base", ctypes.c_int32)]
 
 
 def cu_masked_streams(reserved, total=None):

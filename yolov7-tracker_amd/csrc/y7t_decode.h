@@ -5,6 +5,7 @@
 // `v`: the row's `no` fp32 logits -- x, y, w, h, objectness, classes.
 #pragma once
 #include "y7t_det.h"
+#include "y7t_tta.h"
 
 __device__ __forceinline__ float y7t_sigmoid(float x) {
 #pragma clang fp contract(off)
@@ -50,6 +51,13 @@ __device__ __forceinline__ void y7t_xywh2xyxy(const float* c, float* box) {
 __device__ __forceinline__ void y7t_decode_box(const float* v, int x, int y, int an, const Y7TLevel& L, float* box) {
     float c[4];
     y7t_decode_xywh(v, x, y, an, L, c);
+    y7t_xywh2xyxy(c, box);
+}
+// ... of one pass of augmented inference (models/yolo.py:311-315): the row's xywh brought back to the first pass's coordinates (y7t_tta.h) before the corners
+__device__ __forceinline__ void y7t_decode_box_tta(const float* v, int x, int y, int an, const Y7TLevel& L, const Y7TTtaPass& pass, float* box) {
+    float c[4];
+    y7t_decode_xywh(v, x, y, an, L, c);
+    y7t_tta_descale_deflip(c, pass);
     y7t_xywh2xyxy(c, box);
 }
 

@@ -104,6 +104,52 @@ class HeadOutput:
         return torch.float32
 
 
+def tta_pass_sizes(H, W, ratio, gs):
+    """scale_img's sizes (utils/torch_utils.py:252-256) in Python doubles, exactly as the reference writes them: -> (hs, ws) the resampled image, (Hp, Wp) the padded one"""
+    if ratio == 1.0:
+        return (H, W), (H, W)
+    return (int(H * ratio), int(W * ratio)), tuple(math.ceil(x * ratio / gs) * gs for x in (H, W))
+
+
+class AugmentedOutput(HeadOutput):
+    """what `model(img, augment=True)[0]` stands for (models/yolo.py:301-317): the candidates of all passes, de-scaled and de-flipped to the first pass's coordinates,
+    in the detector's augmented post-processing set -- `non_max_suppression` / `Detector.postprocess` run ONE NMS over them.  Passes of one size share an arena, so
+    every pass was decoded before the next one ran and no head tensor survives: `raw()` does not exist, and `decoded()` -- the reference's (B, A0 + A1 + A2, no)
+    tensor -- is there only if the forward kept the per-pass tensors (`keep_decoded=True`; `model(img, augment=True)` does)."""
+
+    def __init__(self, det, B, img_shape, aug, conf_thres, rows, kept=None):
+        super().__init__(det, B, img_shape, fused=conf_thres)
+        self.aug, self.rows, self._kept = aug, rows, kept      # rows: anchors of every pass; kept: the decoded + transformed tensor of every pass, or None
+        self._aug_epoch = aug.epoch
+
+    @property
+    def shape(self):
+        return (self.B, sum(self.rows), self.det.plan.det["no"])
+
+    def raw(self):
+        raise _lib.Y7TError("an augmented forward has no raw head tensors: passes of one size share an arena, each is decoded before the next runs")
+
+    def decoded(self):
+        """(B, A0 + A1 + A2, no) float32 == the reference's `model(img, augment=True)[0]`; a parity and inspection path, not the fast one"""
+        if self._kept is None:
+            raise _lib.Y7TError("this augmented forward did not keep its decoded passes: forward_augment(img, keep_decoded=True)")
+        return torch.cat(self._kept, 1)
+
+    def candidate_arrays(self):
+        """device views (cbox, cscore, ccls, cidx, count) of the union candidates, as Detector.candidate_arrays lays them out; cidx counts rows across the passes"""
+        self.det._check_aug(self)
+        return _cand_views(self.aug.ws, self.B, self.aug.cap)
+
+
+def _cand_views(ws, B, cap):
+    """the first five arrays of y7t_post_ws (csrc/y7t_post.hip) of a workspace filled for batch B"""
+    rup = lambda n: (n + 255) // 256 * 256
+    o1 = rup(B * cap * 16); o2 = o1 + rup(B * cap * 4); o3 = o2 + rup(B * cap * 4); o4 = o3 + rup(B * cap * 4)
+    return (ws[:B * cap * 16].view(torch.float32).view(B, cap, 4), ws[o1:o1 + B * cap * 4].view(torch.float32).view(B, cap),
+            ws[o2:o2 + B * cap * 4].view(torch.float32).view(B, cap), ws[o3:o3 + B * cap * 4].view(torch.int32).view(B, cap),
+            ws[o4:o4 + B * 4].view(torch.int32))
+
+
 class Plan_PostSet:
     """workspace + outputs of one decode/NMS chain (y7t_det_postprocess)"""
 
@@ -123,6 +169,7 @@ class Detector:
         # seeded random weights only (state_dict None): see weights.random_state_dict / calibrate_bn
         self._bn_bias_mean, self._calib_image = float(bn_bias_mean), calib_image
         self._plans = {}
+        self._aug = {}              # augmented post-processing sets, by input size and pass sizes (forward_augment)
         self._epoch = 0             # forwards run so far (a HeadOutput is only valid against the arena of its own forward)
         self.plan = None
         self._handle = None
@@ -415,12 +462,144 @@ class Detector:
         return HeadOutput(self, B, (H, W), fused=fuse_decode, pset=pset), (H, W)
 
     def __call__(self, img, augment=False):
+        """models/yolo.py:301-319: `model(img)[0]` is the HeadOutput of a plain forward, `model(img, augment=True)[0]` the AugmentedOutput of the three-pass one
+        (with its decoded passes kept, so that code written against the reference's tensor keeps working)"""
+        if augment:
+            return (self.forward_augment(img, keep_decoded=True),)
         return (self.forward(img),)
+
+    def _aug_set(self, hw, sizes, B):
+        """the augmented post-processing set of input size `hw`: allocated on the first augmented call of that size"""
+        key = (hw, tuple(sizes))
+        if key not in self._aug:
+            rows = []
+            for pad in sizes:
+                self._select(pad)
+                rows.append(sum(self.plan.det["na"] * hd["ny"] * hd["nx"] for hd in self.plan.heads))
+            a = Plan_PostSet()
+            a.rows, a.cap, a.epoch = rows, (sum(rows) + 63) // 64 * 64, 0      # every anchor of every pass fits (rounded as plan.cap is)
+            mb = self.max_batch
+            a.ws = torch.zeros(int(self._L.y7t_det_postprocess_workspace_bytes(mb, a.cap, MAX_NMS)), dtype=torch.uint8, device="cuda")
+            a.dets = torch.zeros((mb, MAX_DET, 6), dtype=torch.float32, device="cuda")
+            a.ndets = torch.zeros(mb, dtype=torch.int32, device="cuda")
+            a.keep = torch.zeros((mb, MAX_DET), dtype=torch.int32, device="cuda")
+            a.cand = torch.zeros(mb, dtype=torch.int32, device="cuda")
+            a.lb = torch.zeros((mb, 5), dtype=torch.float32, device="cuda")
+            self._aug[key] = a
+        return self._aug[key]
+
+    def _check_aug(self, out):
+        if out._aug_epoch != out.aug.epoch:
+            raise _lib.Y7TError("the candidates of this augmented forward have been overwritten by a later augmented forward of the same size")
+
+    def forward_augment(self, img, scales=(1, 0.83, 0.67), flips=(None, 3, None), conf_thres=0.01, keep_decoded=False):
+        """Augmented inference, models/yolo.py:301-317: one pass per (scale, flip) -- flip 3 left-right, 2 up-down, applied before scale_img
+        (utils/torch_utils.py:247-257) -- over `img` ((B,3,H,W) float32 RGB in [0,1] or (B,H,W,3) uint8 BGR frames, of a size the detector accepts), each pass the PLAIN
+        launch list of the plan of its padded size followed by a decode pass that appends its candidates above `conf_thres`, de-scaled and de-flipped, to one augmented
+        post-processing set.  -> AugmentedOutput; `postprocess` / `non_max_suppression` then run one NMS over the union, with the same conf_thres.
+        Passes of the same padded size share a plan and its arena, which is why a pass is decoded before the next one runs.  The plans of the smaller sizes and the
+        augmented set (capacity: the anchors of all passes; its own dets / ndets / keep / cand) are created on the first augmented call: their arenas cost device memory
+        only for users of the feature.  keep_decoded: also build every pass's (B, A_i, no) tensor the reference concatenates (torch, with the transform on the host: a
+        parity path).  The fused Detect epilogues are not used by the passes; a transform-aware fused form is a later step."""
+        if len(scales) != len(flips) or not scales:
+            raise ValueError("forward_augment: one flip per scale")
+        if any(f not in (None, 0, 2, 3) for f in flips):
+            raise ValueError("forward_augment: flips are None, 2 (up-down) or 3 (left-right)")
+        if img.dim() == 3:
+            img = img[None]
+        if img.device.type != "cuda":
+            img = img.cuda(non_blocking=True)
+        is_u8 = img.dtype == torch.uint8
+        if is_u8:
+            B, H, W = img.shape[0], img.shape[1], img.shape[2]
+        else:
+            img = img.float()
+            B, H, W = img.shape[0], img.shape[2], img.shape[3]
+        img = img.contiguous()
+        if B > self.max_batch:
+            raise ValueError("batch %d > max_batch %d" % (B, self.max_batch))
+        gs = int(self.stride.max())
+        sizes = [tta_pass_sizes(H, W, float(r), gs) for r in scales]
+        aug = self._aug_set((H, W), [pad for _, pad in sizes], B)
+        aug.epoch += 1
+        aug.last_B = B
+        s, kept, row_base = _lib.stream_ptr(), [], 0
+        for i, (ratio, flip, ((hs, ws), pad)) in enumerate(zip(scales, flips, sizes)):
+            self._select(pad)
+            p = self.plan
+            if float(ratio) == 1.0 and not flip:
+                first = self._front(img, is_u8, B, H, W, None, 0)
+            else:
+                _lib.check(self._L.y7t_tta_scale_layout(_lib.ptr(img), int(is_u8), B, H, W, int(flip or 0), hs, ws, pad[0], pad[1], int(p.reorg), _lib.ptr(p.arena),
+                                                        p.in_ld, s))
+                first = 0
+            self._run_ops(B, first, -1, None, 0)
+            self._epoch += 1
+            tp = _lib.TtaPass(float(ratio), int(flip or 0), float(W if flip == 3 else H if flip == 2 else 0), row_base)
+            _lib.check(self._L.y7t_det_decode_append(p.head_ptrs, p.ny, p.nx, p.strides, p.anchors, len(p.heads), p.det["na"], p.det["no"], B, float(conf_thres),
+                                                     aug.cap, MAX_NMS, 0, ctypes.byref(tp), int(i == 0), _lib.ptr(aug.ws), aug.ws.numel(), s))
+            if keep_decoded:
+                y = HeadOutput(self, B, pad).decoded().cpu()
+                if float(ratio) != 1.0 or flip:      # yolo.py:311-315 as the reference's CPU path rounds it: a float32 division by the scalar, then the de-flip
+                    y[..., :4] /= float(ratio)
+                    if flip == 2:
+                        y[..., 1] = H - y[..., 1]
+                    elif flip == 3:
+                        y[..., 0] = W - y[..., 0]
+                kept.append(y.cuda())
+            row_base += aug.rows[i]
+        self._select(sizes[0][1])      # leave the detector on the first pass's plan, as a plain forward of `img` would
+        self._img_keep = img
+        return AugmentedOutput(self, B, (H, W), aug, float(conf_thres), list(aug.rows), kept if keep_decoded else None)
+
+    def forward_frames_augment(self, frames, img_size=1280, **kw):
+        """forward_frames for augmented inference: raw (B,H0,W0,3) uint8 BGR frames that ARE the letterboxed image -- no resampling and no padding, e.g. frames
+        rendered or stored at the network's size -- so that the first pass takes the input path of the plain forward (the fused frame -> stem kernel where the plan has
+        it) and the scaled passes resample the same frame.  A frame that needs letterboxing is refused: the fused stem letterboxes on the fly and never writes the
+        image the scaled passes would have to read; letterbox on the host and call forward_augment.  -> (AugmentedOutput, (H, W))"""
+        if frames.dim() == 3:
+            frames = frames[None]
+        H0, W0 = int(frames.shape[1]), int(frames.shape[2])
+        H, W, new_h, new_w, top, left = self.letterbox_params((H0, W0), img_size, int(self.stride.max()))
+        if (H, W) != (H0, W0) or (new_h, new_w) != (H0, W0):
+            raise ValueError("augmented inference from raw frames needs frames of the network's size: %dx%d letterboxes to %dx%d (resized to %dx%d), an image the "
+                             "device path never materialises -- letterbox on the host (the loader's default) and call forward_augment" % (H0, W0, H, W, new_h, new_w))
+        return self.forward_augment(frames, **kw), (H, W)
+
+    def _postprocess_aug(self, out, conf_thres, iou_thres, ori_shapes, classes, agnostic, multi_label):
+        """ONE NMS over the union candidates of an augmented forward: the head == NULL path of y7t_det_postprocess(_ex) on the augmented set"""
+        self._check_aug(out)
+        if abs(float(conf_thres) - float(out.fused)) > 1e-12:
+            raise ValueError("this forward fused the Detect decode with conf_thres=%g; post-processing it with %g needs a plain forward" % (out.fused, conf_thres))
+        p, a, B = self.plan, out.aug, out.B
+        if multi_label and p.det["no"] > 6:
+            raise ValueError("multi_label over an augmented forward is not built: its decode passes keep the best class of a row")
+        H, W = out.img_shape
+        lb = np.zeros((B, 5), np.float32)
+        for b in range(B):
+            h0, w0 = (H, W) if ori_shapes is None else ori_shapes[b][:2]
+            gain = min(H / h0, W / w0)
+            lb[b] = (gain, (W - w0 * gain) / 2, (H - h0 * gain) / 2, h0, w0)
+        key = lb.tobytes()
+        if getattr(a, "_lb_key", None) != key:
+            a.lb[:B].copy_(torch.from_numpy(lb))
+            a._lb_key = key
+        opts = _lib.nms_opts(classes, agnostic, False)
+        args = (None, p.ny, p.nx, p.strides, p.anchors, len(p.heads), p.det["na"], p.det["no"], B, float(conf_thres), float(iou_thres), MAX_DET, MAX_NMS,
+                a.cap, _lib.ptr(a.lb), _lib.ptr(a.dets), _lib.ptr(a.ndets), _lib.ptr(a.keep), _lib.ptr(a.cand), _lib.ptr(a.ws), a.ws.numel(), _lib.stream_ptr())
+        if opts is None:
+            _lib.check(self._L.y7t_det_postprocess(*args))
+        else:
+            _lib.check(self._L.y7t_det_postprocess_ex(*args, ctypes.byref(opts)))
+        return a.dets, a.ndets
 
     def postprocess(self, out, conf_thres=0.01, iou_thres=0.45, ori_shapes=None, classes=None, agnostic=False, multi_label=False):
         """decode + NMS + scale_coords + round on the device.  ori_shapes: list of (H0, W0) per image (None: no rescale).
         classes / agnostic / multi_label: as in non_max_suppression (utils/general.py:607); multi_label needs a forward without fuse_decode.
+        An AugmentedOutput (forward_augment) is post-processed on its own set: one NMS over the union of its passes, conf_thres as in the forward, no multi_label.
         -> (dets (B, 300, 6) float32 device tensor, ndets (B,) int32 device tensor); asynchronous."""
+        if isinstance(out, AugmentedOutput):
+            return self._postprocess_aug(out, conf_thres, iou_thres, ori_shapes, classes, agnostic, multi_label)
         p, B = self.plan, out.B
         H, W = out.img_shape
         lb = np.zeros((B, 5), np.float32)
@@ -464,12 +643,7 @@ class Detector:
         B = B if B is not None else getattr(p.post[pset], "last_B", self.max_batch)
         if not 1 <= B <= self.max_batch:
             raise ValueError("candidate_arrays: batch %d outside [1, %d]" % (B, self.max_batch))
-        cap, ws = self.max_cand, p.post[pset].ws
-        rup = lambda n: (n + 255) // 256 * 256
-        o1 = rup(B * cap * 16); o2 = o1 + rup(B * cap * 4); o3 = o2 + rup(B * cap * 4); o4 = o3 + rup(B * cap * 4)
-        return (ws[:B * cap * 16].view(torch.float32).view(B, cap, 4), ws[o1:o1 + B * cap * 4].view(torch.float32).view(B, cap),
-                ws[o2:o2 + B * cap * 4].view(torch.float32).view(B, cap), ws[o3:o3 + B * cap * 4].view(torch.int32).view(B, cap),
-                ws[o4:o4 + B * 4].view(torch.int32))
+        return _cand_views(p.post[pset].ws, B, self.max_cand)
 
     def stage_heads(self, out):
         """Copy the four raw head buffers of `out` (a few MB per frame, device to device, on the current stream) into a staging
@@ -522,7 +696,7 @@ class Detector:
 
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, labels=()):
     """utils/general.py:607-695 on the device; `labels` (autolabelling apriori) is not implemented.
-    prediction: the HeadOutput returned by Detector.  classes: None or a list of class ids kept before the max_nms cut; agnostic: NMS across classes;
+    prediction: the HeadOutput returned by Detector (an AugmentedOutput of `model(img, augment=True)`: one NMS over the union of its passes).  classes: None or a list of class ids kept before the max_nms cut; agnostic: NMS across classes;
     multi_label: one candidate per (anchor, class) above conf_thres -- it needs the per-class scores, i.e. a forward without fuse_decode (ValueError otherwise).
     -> list of (n, 6) tensors [xyxy, conf, cls], score-descending (equal scores: anchor row, then class, ascending)."""
     if not isinstance(prediction, HeadOutput):
@@ -533,11 +707,16 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     det = prediction.det
     dets, nd = det.postprocess(prediction, conf_thres, iou_thres, None, classes=classes, agnostic=agnostic, multi_label=multi_label)
     nd = nd.cpu().numpy()
-    det.check_overflow()
+    aug = prediction.aug if isinstance(prediction, AugmentedOutput) else None      # (its capacity is every anchor of every pass: no overflow to check)
+    if aug is None:
+        det.check_overflow()
     out = []
     for b in range(prediction.B):
         d = dets[b, :nd[b]].clone()
-        d[:, :4] = det.plan_raw_boxes(b, int(nd[b]), prediction.pset)   # un-rounded boxes: rounding is the caller's (track.py:240)
+        if aug is not None:
+            d[:, :4] = _cand_views(aug.ws, prediction.B, aug.cap)[0][b, aug.keep[b, :int(nd[b])].long()]
+        else:
+            d[:, :4] = det.plan_raw_boxes(b, int(nd[b]), prediction.pset)   # un-rounded boxes: rounding is the caller's (track.py:240)
         out.append(d)
     return out
 

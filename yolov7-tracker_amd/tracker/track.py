@@ -8,6 +8,7 @@ device-resident SORT / ByteTrack trackers.
 Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / arch name for state-dict checkpoints),
 --nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch,
 --gmc {none,ecc,features} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
+--augment (the detector's three-pass test-time augmentation, as detect.py --augment; default off).
 --botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
 """
 import argparse
@@ -147,7 +148,12 @@ def main(opts, cfgs):
             outs = None
             if any(detect):
                 # conf_thres 0.01 (track.py:239) is known here, so the Detect convs decode + filter in their epilogue (fused forward)
-                if opts.device_preprocess:      # raw uint8 frames -> letterbox + layout on the GPU
+                if getattr(opts, 'augment', False):      # (extension) the three-pass forward of detect.py --augment: plain heads, one NMS over the union
+                    if opts.device_preprocess:      # frames of the network's size only: pass 0 from the raw frame (fused stem), the scaled passes resample the same frame
+                        head, lb_size = model.forward_frames_augment(imgs0, img_size=opts.img_size, conf_thres=0.01)
+                    else:
+                        head, lb_size = model.forward_augment(imgs.cuda(), conf_thres=0.01), imgs.shape[2:]
+                elif opts.device_preprocess:      # raw uint8 frames -> letterbox + layout on the GPU
                     head, lb_size = model.forward_frames(imgs0, img_size=opts.img_size, fuse_decode=0.01)
                 else:
                     head, lb_size = model.forward(imgs.cuda(), fuse_decode=0.01), imgs.shape[2:]
@@ -276,6 +282,9 @@ def build_parser():
     # the NMS arguments of the reference's detect.py:166-167 (non_max_suppression applies them before its max_nms / max_det cuts)
     parser.add_argument('--classes', nargs='+', type=int, default=None, help='(extension) filter by class: --classes 0, or --classes 0 2 3')
     parser.add_argument('--agnostic_nms', action='store_true', help='(extension) class-agnostic NMS')
+    parser.add_argument('--augment', action='store_true',
+                        help="(extension) augmented inference, detect.py / test.py --augment of the reference (models/yolo.py:301-317): three passes at scales 1, 0.83, 0.67, the "
+                             "middle one flipped left-right, one NMS over their union; with --device_preprocess only for frames of the network's size (no letterboxing)")
     return parser
 
 
