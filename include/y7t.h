@@ -368,6 +368,37 @@ int y7t_gsi_interpolate(void* obj, const double* runs, const int* offsets, int n
 int y7t_gsi_smooth(void* obj, const double* runs, const int* offsets, const double* len_scale, int n_tracks, int longest, double reg, double* out,
                    int* status_out, y7t_stream stream);
 
+/* mAP evaluation of the detector, as the reference's test.py grades a checkpoint: the per-image statistics of test.py:126-209 and ap_per_class / compute_ap of
+ * utils/metrics.py:18-106 (DESIGN.md section 4 "mAP evaluation").  No prediction row reaches the host; no atomics; the stored rows do not depend on how the images
+ * were split into calls, and two computes over one state give the same bits.
+ *
+ * The STATE is caller-owned device memory of y7t_map_bytes(cap_rows, nc) bytes at a 256-byte aligned address (0 for cap_rows < 1 or nc outside [1, 65535]): a
+ * 256-byte header of int32 words (0: rows stored, 1: images seen, 2: status), nt (int64[nc], targets per class), and per stored row conf (float32), cls (int32) and
+ * correct (int32, bit k = IoU > iouv[k]), followed by the workspace of the compute (about 48 bytes a row in all).  y7t_map_layout: out4 = the byte offsets of nt,
+ * conf, cls, correct.  y7t_map_init zeroes the counts (it is also the reset); y7t_map_release: the memory is about to be freed.
+ * y7t_map_update: one batch.  dets (batch x max_det x 6 float32, of which conf and cls are read), ndets (batch int32), keep (batch x max_det int32) as
+ *   y7t_det_postprocess wrote them; cand_boxes: the candidate boxes `keep` indexes (image b's at cand_boxes + b * cand_stride * 4, cand_rows of them valid: xyxy in
+ *   network pixels, NOT rounded); targets (L x 6 float32 [image, class, x, y, w, h], normalised, grouped by image) with target_offsets (batch + 1 int32: image b's
+ *   rows are [offsets[b], offsets[b + 1])); the batch's img_h, img_w; lb (batch x 5 float32: gain, padx, pady, h0, w0, the layout of y7t_det_postprocess); iouv (10
+ *   float32, torch.linspace(0.5, 0.95, 10)).  float32, one rounded operation at a time in torch's order: targets *= (W, H, W, H), xywh2xyxy, scale_coords with the
+ *   ratio and pad of lb for targets and predictions, box_iou = inter / ((area1 + area2) - inter).  Every prediction takes its same-class target of largest IoU
+ *   (lowest index on a tie) and claims it when that IoU is > iouv[0]; a target's first claimant in row order gets correct = iou > iouv, later ones stay all-false.
+ *   Rows are appended in image order.  A call that would pass cap_rows stores nothing -- no rows, no targets, no images -- and sets status bit 0.  max_det <= 1024.
+ *   Asynchronous, no read-back.
+ * y7t_map_compute: a stable least-significant-digit radix sort of the rows by (class ascending, conf descending, arrival order), then per class and threshold the
+ *   integer counts, float64 recall = tpc / (n_l + 1e-16) and precision = tpc / (tpc + fpc), the suffix-maximum envelope with compute_ap's sentinels, np.interp at
+ *   np.linspace(0, 1, 101) and the trapezoid sum; for threshold 0 the precision and recall curves over -conf at np.linspace(0, 1, 1000).  Device outputs: ap_out
+ *   (nc x 10 float64), p_out and r_out (nc x 1000 float64; a class without targets or without predictions is all zero), nt_out (nc int64), classes_out (nc int32:
+ *   the classes that have targets, ascending, then -1), info_out (4 int32: rows, images seen, status, number of such classes).  Asynchronous.
+ * Errors: Y7T_E_ARG (a null pointer, a misaligned or too small state, a capacity out of range), Y7T_E_STATE (an address y7t_map_init never saw). */
+size_t y7t_map_bytes(int cap_rows, int nc);
+int y7t_map_layout(int cap_rows, int nc, size_t* out4);
+int y7t_map_init(void* obj, size_t bytes, int cap_rows, int nc, y7t_stream stream);
+int y7t_map_release(void* obj);
+int y7t_map_update(void* obj, const float* dets, const int* ndets, const int* keep, const float* cand_boxes, int cand_rows, int cand_stride, int batch, int max_det,
+                   const float* targets, const int* target_offsets, int img_h, int img_w, const float* lb, const float* iouv, y7t_stream stream);
+int y7t_map_compute(void* obj, double* ap_out, double* p_out, double* r_out, long long* nt_out, int* classes_out, int* info_out, y7t_stream stream);
+
 /* byte offsets of the arrays inside a state blob, for host-side views (tracked_stracks, lost_stracks, ...).
  * names/offsets: see y7t_tracker_field_name(i); returns the number of fields. */
 int y7t_tracker_layout(int cap_tracks, int cap_dets, int64_t* offsets, int max_fields);

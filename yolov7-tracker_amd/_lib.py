@@ -83,6 +83,13 @@ SIGNATURES = {
     "y7t_gsi_release": (c_int, [c_void_p]),
     "y7t_gsi_interpolate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "y7t_gsi_smooth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "y7t_map_bytes": (c_size_t, [c_int, c_int]),
+    "y7t_map_layout": (c_int, [c_int, c_int, c_void_p]),
+    "y7t_map_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "y7t_map_release": (c_int, [c_void_p]),
+    "y7t_map_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p]),
+    "y7t_map_compute": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "y7t_kf_multi_gmc_f64":(c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "y7t_ecc_prepare_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "y7t_ecc_workspace_bytes": (c_int, [c_int, c_int, c_void_p]),

@@ -172,6 +172,23 @@ def make_frames(n_frames=4, n_obj=80, size=1280, seq_idx=0):
     return frames
 
 
+def make_frame_labels(n_frames=4, n_obj=80, size=1280, seq_idx=0):
+    """the rectangles make_frames(...) paints, as detector labels: per frame float32 (n, 5) rows [class, x, y, w, h], centre and size normalised by `size`
+    (the reference's label files), for the rectangles of which at least 2 x 2 pixels lie inside the frame"""
+    rng = np.random.default_rng(BASE_SEED + 1000 + seq_idx)
+    cx, cy, w, h, vx, vy, cls, _ = _tracks(rng, n_obj, size)
+    out = []
+    for _ in range(n_frames):
+        cx = cx + vx
+        cy = cy + vy
+        x1, y1 = np.clip(cx - w / 2, 0, size), np.clip(cy - h / 2, 0, size)
+        x2, y2 = np.clip(cx + w / 2, 0, size), np.clip(cy + h / 2, 0, size)
+        vis = (x2 - x1 >= 2) & (y2 - y1 >= 2)
+        rows = np.stack([cls.astype(np.float64), (x1 + x2) / 2 / size, (y1 + y2) / 2 / size, (x2 - x1) / size, (y2 - y1) / size], 1)[vis]
+        out.append(rows.astype(np.float32))
+    return out
+
+
 def make_warps(n_frames=100, seq_idx=0, rot=0.002, shift=2.0):
     """-> (n_frames, 2, 3) float64 camera-motion matrices near the identity (what BoT-SORT's GMC.apply would estimate from
     ORB matches, /root/reference/tracker/botsort.py:13-248 -- the estimation itself is OpenCV and out of scope)."""
