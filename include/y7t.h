@@ -598,7 +598,22 @@ enum { Y7T_REID_CONV = 0, Y7T_REID_DWCONV3 = 1, Y7T_REID_MAXPOOL3S2 = 2, Y7T_REI
         * H_PACK fp32 (H, W, 3) -> fp16 (H, W, 16); H_CONV k in {1, 3}, C % 8 == 0, Co % 64 == 0, weights fp16 [Co][round_up(k*k*C, 64)] with
         * k index (kh * k + kw) * C + ci stored at float offset w_off of the blob, fp32 bias [Co] at b_off, no activation; H_MAXPOOL_RELU
         * relu then 3x3 / 2 / pad 1; H_RELU; H_ADD_RELU relu(in + aux); H_GAP_L2NORM mean over the map then x / |x| -> fp32 (C) */
-       Y7T_REID_H_PACK = 9, Y7T_REID_H_CONV = 10, Y7T_REID_H_MAXPOOL_RELU = 11, Y7T_REID_H_RELU = 12, Y7T_REID_H_ADD_RELU = 13, Y7T_REID_H_GAP_L2NORM = 14 };
+       Y7T_REID_H_PACK = 9, Y7T_REID_H_CONV = 10, Y7T_REID_H_MAXPOOL_RELU = 11, Y7T_REID_H_RELU = 12, Y7T_REID_H_ADD_RELU = 13, Y7T_REID_H_GAP_L2NORM = 14,
+       /* The general OSNet path (csrc/y7t_reid_osnet.hip, tracker/reid.py::lower_osnet_f16; DESIGN.md section 4 "OSNet family"): fp16 NHWC maps whose channel
+        * counts are padded to a multiple of 16 (pad channels exactly zero), 1x1 weights as MFMA A fragments (reid.py::_frags) at float offset w_off (a multiple
+        * of 4), fp32 bias at b_off.
+        * H_OS_STEM     in: fp32 (H, W, 3) crops -> raw 7x7 / 2 / 3 conv + bias, fp16 (Ho, Wo, Co), Co <= 64; fragments [Co / 16][14][64][4]
+        * H_OS_PW       1x1 C -> Co over the map; relu bit 0 = ReLU; k = residual mode: 0 none, 1 + aux, 2 a second GEMM over aux (s channels, fragments at w2_off)
+        * H_OS_LIGHT    level k (0 .. 3) of an OSBlock's four LightConv3x3 chains, s = 4 - k branches, C = mid channels <= 128, p = rows of a strip (0: as many
+        *               as fit the LDS); in: conv1's output (k == 0) or the branch buffer, out: the branch buffer (10 slots of H W C halves per crop),
+        *               aux: fp32 per-strip channel sums [4][strips][C] per crop; per branch at w_off: fragments | fp32 taps [9][C] | fp32 bias [C]
+        * H_OS_GATESUM  in: the branch buffer, aux: the sums -> sum_b gate_b x2_b, fp16 (H, W, C); R <= 8; fc1 [R][C] / bias at w_off / b_off, fc2 [C][R] / bias at
+        *               w2_off / b2_off; p as in H_OS_LIGHT
+        * H_OS_INSTNORM InstanceNorm2d(affine, eps 1e-5) per (crop, channel) over fp16 (H, W, C), gamma at w_off, beta at b_off, relu; INSTNORM: the same on fp32
+        *               maps, for the exact op list (C % 8 == 0)
+        * H_OS_AVGPOOL  AvgPool2d(2) on fp16 maps; H_OS_GAPFC mean over the map -> fp16 (C) in aux, then Linear C -> Co + bias (+ ReLU) -> fp32 (Co) */
+       Y7T_REID_H_OS_STEM = 15, Y7T_REID_H_OS_PW = 16, Y7T_REID_H_OS_LIGHT = 17, Y7T_REID_H_OS_GATESUM = 18, Y7T_REID_H_OS_INSTNORM = 19, Y7T_REID_H_OS_AVGPOOL = 20,
+       Y7T_REID_H_OS_GAPFC = 21, Y7T_REID_INSTNORM = 22 };
 typedef struct y7t_reid_op {
     int32_t type;
     int32_t in_buf, out_buf, aux_buf;   /* arena buffers; aux: second addend (ADD_RELU), pooled + gate scratch (GATE_ACC), -1 otherwise */

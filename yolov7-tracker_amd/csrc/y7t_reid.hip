@@ -12,6 +12,7 @@
 #include "y7t_common.h"
 #include "y7t_conv_common.h"
 #include "y7t_reid_fused.h"
+#include "y7t_reid_osnet.h"
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
@@ -21,7 +22,9 @@ static_assert(sizeof(y7t_reid_op) == 96, "y7t_reid_op layout must match tracker/
 enum { R_CONV = 0, R_DWCONV3 = 1, R_MAXPOOL3S2 = 2, R_AVGPOOL2 = 3, R_GATE_ACC = 4, R_ADD_RELU = 5, R_GAP = 6, R_FC = 7, R_L2NORM = 8,
        // fp16 NHWC activations, convolutions on the detector's MFMA kernels (y7t_conv_launch): the reference's DeepSORT embedding network
        // (reid_models/deepsort_reid.py Net: 1.1 GMAC per crop -- GEMM-shaped, unlike OSNet's depthwise stacks)
-       R_H_PACK = 9, R_H_CONV = 10, R_H_MAXPOOL_RELU = 11, R_H_RELU = 12, R_H_ADD_RELU = 13, R_H_GAP_L2NORM = 14 };
+       R_H_PACK = 9, R_H_CONV = 10, R_H_MAXPOOL_RELU = 11, R_H_RELU = 12, R_H_ADD_RELU = 13, R_H_GAP_L2NORM = 14,
+       // the general OSNet path (y7t_reid_osnet.hip: checked and launched there) and the fp32 instance norm of the exact list
+       R_H_OS_FIRST = 15, R_LAST = 22 };
 
 struct y7t_reid {
     std::vector<y7t_reid_op> ops;
@@ -302,8 +305,9 @@ extern "C" int y7t_reid_create(const y7t_reid_op* ops, int n_ops, const int64_t*
     Y7T_ARG_CHECK(ops && n_ops > 0 && buf_offsets && n_bufs > 0 && arena && weights_f32 && out && max_crops > 0 && in_h > 0 && in_w > 0 && feat_dim > 0);
     bool need_ws = false;
     for (int i = 0; i < n_ops; ++i) {
-        Y7T_ARG_CHECK(ops[i].type >= R_CONV && ops[i].type <= R_H_GAP_L2NORM);
+        Y7T_ARG_CHECK(ops[i].type >= R_CONV && ops[i].type <= R_LAST);
         Y7T_ARG_CHECK(ops[i].in_buf >= 0 && ops[i].in_buf < n_bufs && ops[i].out_buf >= 0 && ops[i].out_buf < n_bufs && ops[i].aux_buf < n_bufs);
+        if (ops[i].type >= R_H_OS_FIRST) { if (int rc = y7t_reid_osnet_check(ops[i])) return rc; }
         if (ops[i].type == R_GATE_ACC) Y7T_ARG_CHECK(ops[i].C <= 256 && ops[i].R <= 64 && ops[i].R >= 1);
         if (ops[i].type == R_H_CONV) Y7T_ARG_CHECK(ops[i].C % 8 == 0 && ops[i].Co % 64 == 0 && (ops[i].k == 1 || ops[i].k == 3) && ops[i].b_off >= 0);
         if (ops[i].type == R_H_MAXPOOL_RELU || ops[i].type == R_H_RELU || ops[i].type == R_H_ADD_RELU) Y7T_ARG_CHECK(ops[i].C % 8 == 0);
@@ -431,6 +435,9 @@ static int reid_forward_impl(y7t_reid* r, const void* frames_u8, int n_frames, i
             break;
         case R_FC:
             hipLaunchKernelGGL(k_reid_fc, dim3(blocks_for((long long)N * op.Co)), dim3(256), 0, s, in, N, op.C, w, bias, op.Co, op.relu, out);
+            break;
+        default:
+            if (int rc = y7t_reid_osnet_launch(op, in, out, aux, r->w, N, r->max_n, s)) return rc;
             break;
         }
         Y7T_LAUNCH_CHECK();

@@ -43,11 +43,18 @@ class _VectorPoolTrack(_PoolTrack):
         pass
 
 
+def osnet_family_archs(**kw):
+    """"random:osnet_x0_25" .. "random:osnet_ibn_x1_0": the reference's five OSNet constructors (reid_models/OSNet.py:522-592) with seeded weights on the general
+    fp16 path (ReIDExtractor(half=True)) at the tracker's crop size"""
+    from .reid import OSNET_NAMES
+    return {name: dict(arch="osnet", width=width, ibn=ibn, half=True, **kw) for name, (width, ibn) in OSNET_NAMES.items()}
+
+
 class AppearanceTracker(BaseTracker):
     _KALMAN_FORMATS = ("default", "strongsort")      # the kalman_format values the tracker's device program accepts
     _KALMAN_NOTE = ""       # why the tracker needs these filters
     _FEATURE_AT_THRESHOLD = False      # a detection gets a feature when its score is > det_thresh (deepsort.py:98, strongsort.py:110); True: >= (botsort.py:339)
-    _REID_ARCHS = {}        # "random:<arch>" -> ReIDExtractor keyword arguments; the first is what a bare "random" means
+    _REID_ARCHS = {}        # "random:<arch>" -> ReIDExtractor keyword arguments (arch: the name itself unless given); the first is what a bare "random" means
     _REID_ARCH_NOTE = ""    # the accepted forms of a "random" reid_model_path, for the error message
     _REID_CKPT = {}         # ReIDExtractor.from_checkpoint keyword arguments
     _REID_HINT = ""         # the extractor to name when none was given
@@ -67,10 +74,14 @@ class AppearanceTracker(BaseTracker):
             arch = path.partition(":")[2] or next(iter(self._REID_ARCHS))
             if arch not in self._REID_ARCHS:
                 raise ValueError("reid_model_path %r: %s" % (path, self._REID_ARCH_NOTE))
-            self.reid_model = ReIDExtractor(None, arch=arch, **self._REID_ARCHS[arch])
+            kw = dict(self._REID_ARCHS[arch])
+            kw.setdefault("arch", arch)
+            if getattr(opts, "reid_half", False) and kw["arch"] == "osnet":      # (extension) --reid_half: the general fp16 OSNet path
+                kw["half"] = True
+            self.reid_model = ReIDExtractor(None, **kw)
         elif self.reid_model is None and path and os.path.isfile(str(path)):      # deepsort.py:14, strongsort.py:29: the weights of opts.reid_model_path
             from .reid import ReIDExtractor
-            self.reid_model = ReIDExtractor.from_checkpoint(path, **self._REID_CKPT)
+            self.reid_model = ReIDExtractor.from_checkpoint(path, **dict(self._REID_CKPT, **({"half": True} if getattr(opts, "reid_half", False) else {})))
         self._feat = None           # feature state, allocated when the feature dimension is known
         self._feat_dim = 0
         self._feat_used = False     # a frame with appearance vectors has been stepped (from then on the width is fixed)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .appearance import AppearanceTracker, OneVectorViews
+from .appearance import AppearanceTracker, OneVectorViews, osnet_family_archs
 from .basetrack import BaseTracker, STrack, TrackState, joint_stracks, sub_stracks  # noqa: F401
 
 
@@ -78,8 +78,8 @@ class BoTSORTReID(OneVectorViews, AppearanceTracker):
     _KALMAN_FORMATS = ("botsort",)
     _KALMAN_NOTE = "runs the xywh filter (track.py:68-69)"
     _FEATURE_AT_THRESHOLD = True      # botsort.py:339: det_results[:, 4] >= self.det_thresh
-    _REID_ARCHS = {"deepsort": dict(max_crops=128), "osnet": dict(max_crops=512)}      # botsort.py:3,278: Extractor = the DeepSORT Net on 128 x 64 crops
-    _REID_ARCH_NOTE = "random, random:deepsort or random:osnet"
+    _REID_ARCHS = dict({"deepsort": dict(max_crops=128), "osnet": dict(max_crops=512)}, **osnet_family_archs(max_crops=128))      # botsort.py:3,278: Extractor = the DeepSORT Net on 128 x 64 crops
+    _REID_ARCH_NOTE = "random, random:deepsort, random:osnet or random:osnet_x0_25 / _x0_5 / _x0_75 / _x1_0 / osnet_ibn_x1_0 (the general fp16 path)"
     _REID_HINT = "ReIDExtractor(arch='deepsort')"
     _OVERFLOW_NOTE = (": bit 2 = the feature state is smaller than the pool, 4 = an appearance vector with zero or non-finite norm (the reference hands NaN costs "
                       "to lapjv; the frame was not stepped), 16 = more queued vectors than the list holds, 32 = more pairs at or under theta_iou than the pair table holds")

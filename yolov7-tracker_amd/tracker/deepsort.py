@@ -5,7 +5,7 @@ fallbacks and the list bookkeeping run in liby7t.so (y7t_tracker_step_deepsort; 
 Appearance features enter at the reference's own seam, `get_feature(tlbrs, ori_img) -> (N, D)` (deepsort.py:19-41; tracker/appearance.py).
 The reference hard-wires `Extractor(opts.reid_model_path)` with weights/ckpt.t7, which does not ship with it."""
 from .. import _lib
-from .appearance import AppearanceTracker
+from .appearance import AppearanceTracker, osnet_family_archs
 
 STORE_FEATURES_BUDGET = 100     # STrack.__init__ store_features_budget (basetrack.py:76)
 
@@ -13,8 +13,8 @@ STORE_FEATURES_BUDGET = 100     # STrack.__init__ store_features_budget (basetra
 class DeepSORT(AppearanceTracker):
     _KIND = 3  # Y7T_TRACKER_DEEPSORT
     _KALMAN_NOTE = "gates on xyah measurements (deepsort.py:59)"
-    _REID_ARCHS = {"osnet": dict(max_crops=512), "deepsort": dict(max_crops=128)}
-    _REID_ARCH_NOTE = "random, random:osnet or random:deepsort"
+    _REID_ARCHS = dict({"osnet": dict(max_crops=512), "deepsort": dict(max_crops=128)}, **osnet_family_archs(max_crops=128))
+    _REID_ARCH_NOTE = "random, random:osnet, random:deepsort or random:osnet_x0_25 / _x0_5 / _x0_75 / _x1_0 / osnet_ibn_x1_0 (the general fp16 path)"
     _REID_HINT = "ReIDExtractor"
 
     def __init__(self, opts, frame_rate=30, gamma=0.02, reid_model=None, *args, **kwargs):

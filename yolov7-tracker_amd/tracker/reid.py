@@ -6,6 +6,9 @@ into its convolution / linear layer, pack the fp32 weights into one blob.  Devic
 DeepSORT's `get_feature` seam (deepsort.py:19-41) calls: `features_for_boxes(frame, tlbrs)` does crop + /255 + resize to 128 x 64 +
 Normalize on the GPU like the reference's Extractor (reid_models/deepsort_reid.py:112-153) and returns (N, 512) device features.
 
+Three OSNet paths: the fp32 op list (`lower`: every width, the IBN variant, any crop size; the exact path), the one-kernel fused path (`pack_fused`: x0_25 at
+128 x 64, the default there) and the general fp16 / MFMA op list (`lower_osnet_f16`: every width, IBN, crops with sides that are multiples of 16; opt-in, half=True).
+
 Weights: a state dict with torchreid's OSNet parameter names (what weights/osnet_x0_25.pth holds) or seeded random ones."""
 import ctypes
 
@@ -19,13 +22,45 @@ OP_DTYPE = np.dtype([("type", "<i4"), ("in_buf", "<i4"), ("out_buf", "<i4"), ("a
                      ("w_kmajor", "<i4"), ("w_off", "<i8"), ("b_off", "<i8"), ("w2_off", "<i8"), ("b2_off", "<i8")], align=False)
 assert OP_DTYPE.itemsize == 96      # == sizeof(y7t_reid_op)
 CONV, DWCONV3, MAXPOOL3S2, AVGPOOL2, GATE_ACC, ADD_RELU, GAP, FC, L2NORM, H_PACK, H_CONV, H_MAXPOOL_RELU, H_RELU, H_ADD_RELU, H_GAP_L2NORM = range(15)
+H_OS_STEM, H_OS_PW, H_OS_LIGHT, H_OS_GATESUM, H_OS_INSTNORM, H_OS_AVGPOOL, H_OS_GAPFC, INSTNORM = range(15, 23)      # the general OSNet path (csrc/y7t_reid_osnet.hip)
+RES_NONE, RES_ADD, RES_GEMM = 0, 1, 2           # H_OS_PW's residual mode (field k)
+OS_SLOTS = 10                                   # branch buffer: 4 + 3 + 2 + 1 slots per crop (csrc/y7t_reid_osnet.h)
+OS_LDS_BUDGET = 61440
 BN_EPS = 1e-5
+# the reference's five constructors (OSNet.py:522-592): name -> (width, ibn)
+OSNET_NAMES = {"osnet_x1_0": (1.0, False), "osnet_x0_75": (0.75, False), "osnet_x0_5": (0.5, False), "osnet_x0_25": (0.25, False), "osnet_ibn_x1_0": (1.0, True)}
 
 
-def osnet_spec(width=0.25, feature_dim=512):
-    """channels of osnet_x1_0 .. osnet_x0_25 (OSNet.py:522-579)"""
+def osnet_spec(width=0.25, feature_dim=512, ibn=False):
+    """channels of osnet_x1_0 .. osnet_x0_25 (OSNet.py:522-579); ibn: osnet_ibn_x1_0's instance norms (:582-592: conv1 and the two blocks of conv2)"""
     ch = {1.0: [64, 256, 384, 512], 0.75: [48, 192, 288, 384], 0.5: [32, 128, 192, 256], 0.25: [16, 64, 96, 128]}[width]
-    return {"channels": ch, "layers": [2, 2, 2], "feature_dim": feature_dim}
+    spec = {"channels": ch, "layers": [2, 2, 2], "feature_dim": feature_dim}
+    if ibn:
+        spec["ibn"] = True
+    return spec
+
+
+def is_ibn(sd):
+    """an OSNet state dict with instance norms: OSBlock.IN of conv2.0 exists (OSNet.py:258-260)"""
+    return "conv2.0.IN.weight" in sd or "module.conv2.0.IN.weight" in sd
+
+
+def pad16(c):
+    return (int(c) + 15) // 16 * 16
+
+
+def os_strip_rows(H, W, midp, override=0):
+    """y7t_osnet_strip_rows (csrc/y7t_reid_osnet.h)"""
+    s = OS_LDS_BUDGET // ((W + 2) * midp * 2) - 2
+    if s < 1:
+        return 0
+    if 0 < override < s:
+        s = override
+    return min(s, H)
+
+
+def os_level_slot(level):
+    return level * 4 - level * (level - 1) // 2
 
 
 def random_state_dict(spec, seed=0):
@@ -80,6 +115,15 @@ def random_state_dict(spec, seed=0):
     sd["fc.0.weight"] = torch.from_numpy(rng.normal(0, (1.0 / ch[3]) ** 0.5, (fd, ch[3])).astype(np.float32))
     sd["fc.0.bias"] = torch.from_numpy(rng.normal(0, 0.1, fd).astype(np.float32))
     bn("fc.1", fd)
+    if spec.get("ibn"):         # drawn after everything else: without ibn the sequence is the one the existing goldens were generated from
+        def inorm(name, c):
+            sd[name + ".weight"] = torch.from_numpy(rng.uniform(0.7, 1.3, c).astype(np.float32))
+            sd[name + ".bias"] = torch.from_numpy(rng.normal(0, 0.1, c).astype(np.float32))
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            del sd["conv1.bn." + k]                             # InstanceNorm2d(affine=True) keeps no running statistics
+        inorm("conv1.bn", ch[0])
+        inorm("conv2.0.IN", ch[1])
+        inorm("conv2.1.IN", ch[1])
     return sd
 
 
@@ -138,6 +182,13 @@ class _Lowering:
         self.op(type=DWCONV3, in_buf=y, out_buf=z, H=H, W=W, C=c, Ho=H, Wo=W, Co=c, k=3, s=1, p=1, relu=1, w_off=self.put(Wd), b_off=self.put(bias))
         return z
 
+    def instnorm(self, x, H, W, c, name, add=-1):
+        """InstanceNorm2d(affine=True) + ReLU over x (+ add) (OSNet.py:52, 260, 274-276)"""
+        y = self.buf(H * W * c)
+        self.op(type=INSTNORM, in_buf=x, aux_buf=add, out_buf=y, H=H, W=W, C=c, Ho=H, Wo=W, Co=c, relu=1,
+                w_off=self.put(self.sd[name + ".weight"].numpy()), b_off=self.put(self.sd[name + ".bias"].numpy()))
+        return y
+
     def osblock(self, x, H, W, cin, cout, name):
         mid = cout // 4
         x1, _, _ = self.conv(x, H, W, cin, mid, 1, 1, 0, name + ".conv1.conv", name + ".conv1.bn", relu=1)
@@ -156,16 +207,23 @@ class _Lowering:
         idn = x
         if cin != cout:
             idn, _, _ = self.conv(x, H, W, cin, cout, 1, 1, 0, name + ".downsample.conv", name + ".downsample.bn")
+        if name + ".IN.weight" in self.sd:
+            return self.instnorm(x3, H, W, cout, name + ".IN", add=idn)
         y = self.buf(H * W * cout)
         self.op(type=ADD_RELU, in_buf=x3, aux_buf=idn, out_buf=y, H=H, W=W, C=cout)
         return y
 
 
 def lower(sd, spec, in_h=128, in_w=64):
-    """-> (ops structured array, buffer sizes in floats per crop, weight blob float32)"""
+    """-> (ops structured array, buffer sizes in floats per crop, weight blob float32).  An IBN state dict (is_ibn) lowers to the IBN graph: instance norms after
+    the stem convolution and on x3 + identity of conv2.0 and conv2.1"""
     L = _Lowering(sd, in_h, in_w)
     ch = spec["channels"]
-    x, H, W = L.conv(L.in_buf, in_h, in_w, 3, ch[0], 7, 2, 3, "conv1.conv", "conv1.bn", relu=1)
+    if "conv1.bn.running_mean" in sd:
+        x, H, W = L.conv(L.in_buf, in_h, in_w, 3, ch[0], 7, 2, 3, "conv1.conv", "conv1.bn", relu=1)
+    else:
+        x, H, W = L.conv(L.in_buf, in_h, in_w, 3, ch[0], 7, 2, 3, "conv1.conv")
+        x = L.instnorm(x, H, W, ch[0], "conv1.bn")
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = L.buf(Ho * Wo * ch[0])
     L.op(type=MAXPOOL3S2, in_buf=x, out_buf=y, H=H, W=W, C=ch[0], Ho=Ho, Wo=Wo, Co=ch[0])
@@ -188,6 +246,137 @@ def lower(sd, spec, in_h=128, in_w=64):
     bf = sd["fc.0.bias"].double().numpy() * scale + bias
     out = L.buf(fd)
     L.op(type=FC, in_buf=v, out_buf=out, H=1, W=1, C=ch[3], Co=fd, relu=1, w_off=L.put(Wf), b_off=L.put(bf))
+    return np.array(L.ops, dtype=OP_DTYPE), L.bufs, np.concatenate(L.w)
+
+
+def stem_frags(W1):
+    """(co, 3, 7, 7) -> A operands of the 7x7 stem, [co_p / 16][14][lane][4] fp16: K-step (kh, half) covers input pixels kw = 4 half + lane // 16 x 4 channels
+    (the 4th channel and kw = 7 are zero) -- the K-step layout of k_osnet_x025's stem, for any width"""
+    cop = pad16(W1.shape[0])
+    Wp = np.zeros((cop, 3, 7, 7))
+    Wp[:W1.shape[0]] = W1
+    lane = np.arange(64)
+    fr = np.zeros((cop // 16, 14, 64, 4), np.float16)
+    for g in range(cop // 16):
+        for kh in range(7):
+            for h in range(2):
+                kw = 4 * h + lane // 16
+                ok = kw < 7
+                for c in range(3):
+                    fr[g, kh * 2 + h, ok, c] = Wp[g * 16 + (lane % 16)[ok], c, kh, kw[ok]]
+    return fr.tobytes()
+
+
+def lower_osnet_f16(sd, spec, in_h=128, in_w=64, strip=0):
+    """OSNet of any width, with or without instance norms, for the general fp16 path (include/y7t.h: Y7T_REID_H_OS_*; csrc/y7t_reid_osnet.hip): fp16 NHWC maps
+    with the channels padded to a multiple of 16 (zero weights, bias, gamma and beta keep the pad channels exactly zero), BatchNorm folded, 1x1 weights as MFMA
+    fragments.  in_h, in_w: multiples of 16.  strip: rows of a strip of the LightConv3x3 level kernel (0: as many as fit the LDS).
+    -> (ops, buffer sizes in floats per crop, weight blob float32)"""
+    if in_h % 16 or in_w % 16 or in_h < 16 or in_w < 16:
+        raise ValueError("the fp16 OSNet path wants crops whose height and width are multiples of 16 (got %d x %d)" % (in_h, in_w))
+    L = _Lowering(sd, in_h, in_w)
+    ch = spec["channels"]
+    ibn = is_ibn(sd)
+    hbuf = lambda halves: L.buf((halves + 1) // 2)            # buffer sizes are in floats per crop
+
+    def put(raw):                                              # 16-byte aligned pieces: the kernels read 8- and 16-byte vectors
+        if L.w_floats % 4:
+            L.put(np.zeros(4 - L.w_floats % 4))
+        a = np.frombuffer(raw, dtype=np.float32) if isinstance(raw, (bytes, bytearray)) else np.asarray(raw, np.float32)
+        return L.put(a)
+
+    def conv_bn(name, bnname):
+        Wt = sd[name + ".weight"].double().numpy()
+        Wt = Wt.reshape(Wt.shape[0], -1) if Wt.shape[2] == 1 else Wt
+        if bnname is None:
+            return Wt, np.zeros(Wt.shape[0])
+        scale, bias = L._bn(bnname)
+        return Wt * scale.reshape((-1,) + (1,) * (Wt.ndim - 1)), bias
+
+    def pw(x, H, W, cin, cout, name, bnname, relu, res=RES_NONE, aux=-1, name2=None, bn2=None, cin2=0):
+        Wm, b = conv_bn(name, bnname)
+        kw = {}
+        if res == RES_GEMM:                                    # conv3 + downsample as one launch: two GEMMs into one accumulator, bias bc3 + bd
+            W2, b2 = conv_bn(name2, bn2)
+            b = b + b2
+            kw = dict(s=pad16(cin2), w2_off=put(_frags(W2, pad16(cout), pad16(cin2))))
+        y = hbuf(H * W * pad16(cout))
+        L.op(type=H_OS_PW, in_buf=x, out_buf=y, aux_buf=aux, H=H, W=W, C=pad16(cin), Ho=H, Wo=W, Co=pad16(cout), k=res, relu=int(relu),
+             w_off=put(_frags(Wm, pad16(cout), pad16(cin))), b_off=put(_f32(b, pad16(cout))), **kw)
+        return y
+
+    def light_params(name, mid, midp):
+        scale, bias = L._bn(name + ".bn")
+        Wd = sd[name + ".conv2.weight"].double().numpy().reshape(mid, 9) * scale[:, None]
+        dw = np.zeros((9, midp))
+        dw[:, :mid] = Wd.T
+        return _frags(sd[name + ".conv1.weight"].double().numpy().reshape(mid, mid), midp, midp) + _f32(dw) + _f32(bias, midp)
+
+    def osblock(x, H, W, cin, cout, name):
+        mid = cout // 4
+        midp, R = pad16(mid), mid // 16
+        x1 = pw(x, H, W, cin, mid, name + ".conv1.conv", name + ".conv1.bn", 1)
+        T = hbuf(OS_SLOTS * H * W * midp)
+        S = os_strip_rows(H, W, midp, strip)
+        if S < 1:
+            raise ValueError("a %d-pixel-wide map with %d channels does not fit the LightConv3x3 level kernel's LDS" % (W, midp))
+        part = L.buf(4 * ((H + S - 1) // S) * midp)
+        chains = [[name + ".conv2a"]] + [["%s.%s.%d" % (name, tag, j) for j in range(n)] for tag, n in (("conv2b", 2), ("conv2c", 3), ("conv2d", 4))]
+        for lev in range(4):
+            raw = b"".join(light_params(chains[b][lev], mid, midp) for b in range(lev, 4))
+            L.op(type=H_OS_LIGHT, in_buf=x1 if lev == 0 else T, out_buf=T, aux_buf=part, H=H, W=W, C=midp, Ho=H, Wo=W, Co=midp, k=lev, s=4 - lev, p=strip, w_off=put(raw))
+        g = name + ".gate"
+        w1 = np.zeros((R, midp)); w1[:, :mid] = sd[g + ".fc1.weight"].double().numpy().reshape(R, mid)
+        w2 = np.zeros((midp, R)); w2[:mid] = sd[g + ".fc2.weight"].double().numpy().reshape(mid, R)
+        x2 = hbuf(H * W * midp)
+        L.op(type=H_OS_GATESUM, in_buf=T, out_buf=x2, aux_buf=part, H=H, W=W, C=midp, Ho=H, Wo=W, Co=midp, R=R, p=strip, w_off=put(_f32(w1)),
+             b_off=put(_f32(sd[g + ".fc1.bias"].double().numpy())), w2_off=put(_f32(w2)), b2_off=put(_f32(sd[g + ".fc2.bias"].double().numpy(), midp)))
+        inorm = name + ".IN.weight" in sd
+        if cin != cout:
+            y = pw(x2, H, W, mid, cout, name + ".conv3.conv", name + ".conv3.bn", not inorm, RES_GEMM, x, name + ".downsample.conv", name + ".downsample.bn", cin)
+        else:
+            y = pw(x2, H, W, mid, cout, name + ".conv3.conv", name + ".conv3.bn", not inorm, RES_ADD, x)
+        if inorm:                                              # the epilogue stored the pre-norm sum
+            y = instnorm(y, H, W, cout, name + ".IN")
+        return y
+
+    def instnorm(x, H, W, c, name):
+        y = hbuf(H * W * pad16(c))
+        L.op(type=H_OS_INSTNORM, in_buf=x, out_buf=y, H=H, W=W, C=pad16(c), Ho=H, Wo=W, Co=pad16(c), relu=1,
+             w_off=put(_f32(sd[name + ".weight"].double().numpy(), pad16(c))), b_off=put(_f32(sd[name + ".bias"].double().numpy(), pad16(c))))
+        return y
+
+    W1, b1 = conv_bn("conv1.conv", None if ibn else "conv1.bn")
+    c0p = pad16(ch[0])
+    H, W = (in_h + 6 - 7) // 2 + 1, (in_w + 6 - 7) // 2 + 1
+    x = hbuf(H * W * c0p)
+    L.op(type=H_OS_STEM, in_buf=L.in_buf, out_buf=x, H=in_h, W=in_w, C=3, Ho=H, Wo=W, Co=c0p, k=7, s=2, p=3, w_off=put(stem_frags(W1)), b_off=put(_f32(b1, c0p)))
+    if ibn:
+        x = instnorm(x, H, W, ch[0], "conv1.bn")
+    Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+    y = hbuf(Ho * Wo * c0p)
+    L.op(type=H_MAXPOOL_RELU, in_buf=x, out_buf=y, H=H, W=W, C=c0p, Ho=Ho, Wo=Wo, Co=c0p)
+    x, H, W = y, Ho, Wo
+    for si, (cin, cout, nblk) in enumerate(zip(ch[:-1], ch[1:], spec["layers"])):
+        stage = "conv%d" % (si + 2)
+        for bi in range(nblk):
+            x = osblock(x, H, W, cin if bi == 0 else cout, cout, "%s.%d" % (stage, bi))
+        if si < 2:
+            x = pw(x, H, W, cout, cout, "%s.%d.0.conv" % (stage, nblk), "%s.%d.0.bn" % (stage, nblk), 1)
+            y = hbuf((H // 2) * (W // 2) * pad16(cout))
+            L.op(type=H_OS_AVGPOOL, in_buf=x, out_buf=y, H=H, W=W, C=pad16(cout), Ho=H // 2, Wo=W // 2, Co=pad16(cout))
+            x, H, W = y, H // 2, W // 2
+    x = pw(x, H, W, ch[3], ch[3], "conv5.conv", "conv5.bn", 1)
+    fd = spec["feature_dim"]
+    if fd % 16:
+        raise ValueError("feature_dim %d: the fp16 path writes whole 16-channel groups" % fd)
+    scale, bias = L._bn("fc.1")
+    Wf = sd["fc.0.weight"].double().numpy() * scale[:, None]
+    bf = sd["fc.0.bias"].double().numpy() * scale + bias
+    v = hbuf(pad16(ch[3]))
+    out = L.buf(pad16(fd))
+    L.op(type=H_OS_GAPFC, in_buf=x, aux_buf=v, out_buf=out, H=H, W=W, C=pad16(ch[3]), Ho=1, Wo=1, Co=pad16(fd), relu=1,
+         w_off=put(_frags(Wf, pad16(fd), pad16(ch[3]))), b_off=put(_f32(bf, pad16(fd))))
     return np.array(L.ops, dtype=OP_DTYPE), L.bufs, np.concatenate(L.w)
 
 
@@ -426,12 +615,19 @@ class ReIDExtractor:
     `net_dict` of the reference's own DeepSORT embedding network (arch="deepsort": reid_models/deepsort_reid.py Net, what Extractor loads from
     weights/ckpt.t7), or None for seeded random weights.  size = (W, H) of the network input like Extractor.size (deepsort_reid.py:122)."""
 
-    def __init__(self, state_dict=None, width=0.25, size=(64, 128), max_crops=512, seed=0, fused=None, arch=None, mfma=True):
+    def __init__(self, state_dict=None, width=0.25, size=(64, 128), max_crops=512, seed=0, fused=None, arch=None, mfma=True, half=False, ibn=None):
         """fused: run frame crops through the one-workgroup-per-crop MFMA kernel (fp16 storage, fp32 accumulate).  Default: on for the
         configuration it exists for (OSNet x0_25, 128 x 64 crops); off = the fp32 op list (also what forward_crops always uses).
         arch: "osnet" | "deepsort"; default: read off the state dict's parameter names (OSNet without one).  The deepsort network (1.1 GMAC per
         crop, all of it dense 3x3 convolutions) runs on the detector's MFMA conv kernels with fp16 activations (mfma=True, 4.9 MB of buffers per
-        crop) or as the exact fp32 op list (mfma=False, 9.4 MB per crop: keep max_crops near the detections of a frame)."""
+        crop) or as the exact fp32 op list (mfma=False, 9.4 MB per crop: keep max_crops near the detections of a frame).  mfma is ignored for OSNet.
+        half: OSNet of any width, with or without instance norms, on crops whose sides are multiples of 16, through the general fp16 / MFMA op list
+        (lower_osnet_f16; csrc/y7t_reid_osnet.hip) -- opt-in, for frame crops and forward_crops alike; not together with fused=True.
+        ibn: osnet_ibn_x1_0's instance norms; default: read off the state dict (conv2.0.IN.weight), off for seeded random weights."""
+        if half and fused:
+            raise ValueError("fused=True and half=True: the fused kernel and the general fp16 op list are two paths, choose one")
+        if half and arch not in (None, "osnet"):
+            raise ValueError("half=True is the OSNet family's fp16 path (arch %r)" % (arch,))
         _lib.require_gpu()
         self._L = _lib.load()
         if arch is None:
@@ -446,12 +642,19 @@ class ReIDExtractor:
             if state_dict is None:
                 state_dict = deepsort_net_random_state_dict(seed)
         else:
-            self.spec = osnet_spec(width)
+            if ibn is None:
+                ibn = state_dict is not None and is_ibn(state_dict)
+            self.spec = osnet_spec(width, ibn=bool(ibn))
             if state_dict is None:
                 state_dict = random_state_dict(self.spec, seed)
+            elif bool(ibn) != is_ibn(state_dict):
+                raise ValueError("ibn=%r, but the state dict %s conv2.0.IN.weight" % (ibn, "has" if is_ibn(state_dict) else "has no"))
         self.sd = {k.replace("module.", "", 1) if k.startswith("module.") else k: v.detach().float().cpu() for k, v in state_dict.items()}
         self.mfma = bool(mfma) and arch == "deepsort"
-        if arch == "deepsort":
+        self.half = bool(half) and arch == "osnet"
+        if self.half:
+            ops, bufs, w = lower_osnet_f16(self.sd, self.spec, self.in_h, self.in_w)
+        elif arch == "deepsort":
             ops, bufs, w = (lower_deepsort_net_f16 if self.mfma else lower_deepsort_net)(self.sd, self.in_h, self.in_w)
         else:
             ops, bufs, w = lower(self.sd, self.spec, self.in_h, self.in_w)
@@ -468,7 +671,7 @@ class ReIDExtractor:
                                            _lib.ptr(self._arena), self._arena.numel() * 4, _lib.ptr(self._w), self.max_crops, self.in_h, self.in_w,
                                            self.feat_dim, ctypes.byref(h)))
         self._h = h
-        can_fuse = arch == "osnet" and width == 0.25 and (self.in_w, self.in_h) == (64, 128)
+        can_fuse = arch == "osnet" and width == 0.25 and (self.in_w, self.in_h) == (64, 128) and not self.half and not self.spec.get("ibn")
         if fused and not can_fuse:
             raise _lib.Y7TError("the fused ReID kernel is OSNet x0_25 on 128 x 64 crops (got width %s, size %s)" % (width, size))
         self.fused = can_fuse if fused is None else bool(fused)
@@ -493,7 +696,7 @@ class ReIDExtractor:
         if "conv1.conv.weight" not in sd:
             raise _lib.Y7TError("%s is neither an OSNet checkpoint (conv1.conv.weight) nor a DeepSORT one ({'net_dict': ...})" % path)
         width = {64: 1.0, 48: 0.75, 32: 0.5, 16: 0.25}[int(sd["conv1.conv.weight"].shape[0])]
-        return cls(sd, width=width, **kw)
+        return cls(sd, width=width, ibn=is_ibn(sd), **kw)
 
     def features_for_boxes(self, frame, tlbrs):
         """frame: (H, W, 3) uint8 BGR (host or device); tlbrs: (N, 4) -> (N, feat_dim) float32 DEVICE tensor"""

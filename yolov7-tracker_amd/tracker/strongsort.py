@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .appearance import AppearanceTracker, OneVectorViews, _VectorPoolTrack as _SSPoolTrack  # noqa: F401
+from .appearance import AppearanceTracker, OneVectorViews, osnet_family_archs, _VectorPoolTrack as _SSPoolTrack  # noqa: F401
 from .botsort import _device_warp
 from .basetrack import STrack, TrackState, _PoolTrack, joint_stracks, sub_stracks, remove_duplicate_stracks  # noqa: F401
 
@@ -27,8 +27,8 @@ class StrongSORT(OneVectorViews, AppearanceTracker):
     reid_model_path (+ the optional capacities of BaseTracker)."""
     _KIND = 6  # Y7T_TRACKER_STRONGSORT
     _KALMAN_NOTE = "fuses the IoU of xyah means (strongsort.py:150)"
-    _REID_ARCHS = {"osnet": dict(size=REID_SIZE, max_crops=128)}
-    _REID_ARCH_NOTE = "random or random:osnet (strongsort.py:26: osnet_x0_25)"
+    _REID_ARCHS = dict({"osnet": dict(size=REID_SIZE, max_crops=128)}, **osnet_family_archs(size=REID_SIZE, max_crops=128))
+    _REID_ARCH_NOTE = "random or random:osnet (strongsort.py:26: osnet_x0_25), or random:osnet_x0_25 / _x0_5 / _x0_75 / _x1_0 / osnet_ibn_x1_0 (the general fp16 path)"
     _REID_CKPT = dict(size=REID_SIZE, max_crops=128)
     _REID_HINT = "ReIDExtractor(size=(256, 128))"
     _OVERFLOW_NOTE = ": the feature state is smaller than the pool"

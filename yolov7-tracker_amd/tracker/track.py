@@ -9,6 +9,7 @@ Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / 
 --nc, --synthetic_dets, --synthetic_frames/--synthetic_objs/--synthetic_seqs, --results_root, --device_preprocess, --batch,
 --gmc {none,ecc,features} / --gmc_faithful 0|1 (the camera-motion estimate of tracker/gmc.py for strongsort and botsort; default none).
 --augment (the detector's three-pass test-time augmentation, as detect.py --augment; default off).
+--reid_half (an OSNet --reid_model_path through the general fp16 / MFMA op list: any width, the IBN variant, any crop size; default off).
 --botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
 """
 import argparse
@@ -249,6 +250,9 @@ def build_parser():
     parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc', 'features'],
                         help='(extension) camera-motion estimate for strongsort / botsort on the device (tracker/gmc.py): ecc = findTransformECC, '
                              'features = FAST corners, rotated BRIEF, Hamming matching and RANSAC (the applyFeaures path the reference runs as orb)')
+    parser.add_argument('--reid_half', action='store_true',
+                        help="(extension) run an OSNet --reid_model_path (a checkpoint or random:osnet) through the general fp16 / MFMA op list: any width, "
+                             "osnet_ibn_x1_0, any crop size (default off: the fused kernel for x0_25 at 128 x 64, the fp32 op list elsewhere)")
     parser.add_argument('--botsort_reid', action='store_true',
                         help="(extension) --tracker botsort with its appearance branch (use_apperance_model, off in the reference): IoU-gated cosine fusion with "
                              "--reid_model_path features")
