@@ -476,6 +476,8 @@ int y7t_det_destroy(y7t_det* det);
  * One forward of a detector at a time: the arena, the split-K slabs and the tile counters of the persistent kernels belong to the plan.  Launches on one
  * stream are ordered; a forward (or a piece of one, y7t_det_forward_ops / _fused) issued on another stream than the previous one waits for it on the device.
  * While `stream` is being captured into a hipGraph nothing is recorded or waited for: whoever replays the graph orders the replays.
+ * What a replay relies on -- tile counters back at zero, slabs rewritten before they are read, the candidate counters zeroed by a kernel node of the graph, the event skipped --
+ * and the test that pins each item: DESIGN.md, section 2 "What a replayed launch list relies on".
  * The kernels address a tensor through 32-bit byte offsets: a conv whose input or output tensor of B images is larger than 2 GiB goes out as several launches over
  * runs of consecutive images (w6 @ 1280 x 1280: the 640^2 / 320^2 layers from 41 images on); results do not depend on where the runs are cut. */
 int y7t_det_forward(y7t_det* det, int B, y7t_stream stream);
@@ -483,6 +485,9 @@ int y7t_det_forward(y7t_det* det, int B, y7t_stream stream);
  * two parts of Model.forward_once (models/yolo.py:321-351) -- bench.py starts the previous batch's decode+NMS on another stream once
  * the memory-bound high-resolution layers of the next forward are through.  y7t_det_num_ops: length of the list. */
 int y7t_det_num_ops(const y7t_det* det);
+/* the eight tile-counter words of op `op` of the plan, copied to the host (a blocking copy: not for a hot path, never while a stream is being captured).  They
+ * read zero whenever no forward of the plan is in flight: the last workgroup of a persistent kernel to leave resets them, eager or replayed from a hipGraph. */
+int y7t_det_tile_counters(const y7t_det* det, int op, int* out_host);
 int y7t_det_forward_ops(y7t_det* det, int B, int first, int last, y7t_stream stream);
 
 /* Fused Detect: describe the Detect levels once (strides / anchors in pixels, models/yolo.py:23-62), then y7t_det_forward_fused runs

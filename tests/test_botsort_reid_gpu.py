@@ -129,8 +129,9 @@ def test_plain_entry_points_refuse_a_pool_of_the_new_kind():
     dets = torch.tensor([d.data_ptr(), d.data_ptr()], dtype=torch.int64, device="cuda")
     outs = torch.tensor([out3.data_ptr(), out4.data_ptr()], dtype=torch.int64, device="cuda")
     counts = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+    ndets = torch.ones(2, dtype=torch.int32, device="cuda")      # (bound to a name: it lives until the launches that read it are through)
     for threads in (0, 1024):
-        _lib.check(L.y7t_tracker_step_batch(_lib.ptr(states), _lib.ptr(dets), _lib.ptr(torch.ones(2, dtype=torch.int32, device="cuda")), _lib.ptr(outs),
+        _lib.check(L.y7t_tracker_step_batch(_lib.ptr(states), _lib.ptr(dets), _lib.ptr(ndets), _lib.ptr(outs),
                                             _lib.ptr(counts), cap, 2, threads, None, _lib.stream_ptr()))
         torch.cuda.synchronize()
         assert tc.pool_status(L, st3) & 8 and tc.pool_status(L, st4) == 0 and counts.tolist()[0] == 0

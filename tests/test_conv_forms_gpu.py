@@ -164,13 +164,20 @@ class Case:
                 rc, name = plan.run()
                 assert rc == 0, (rc, self.L.y7t_last_error())
                 assert name == kernel, "%s ran %r, the dispatch code says %r" % (self.label, name, kernel)
-                outs.append(self.out_view()[..., self.out_coff:self.out_coff + self.Cout].clone())
+                outs.append(self.out_slice().clone())
         finally:
             plan.close()
         for o in outs[1:]:
             assert torch.equal(bits(o), bits(outs[0])), "%s: runs differ" % self.label
         assert not bool(torch.isnan(outs[0]).any()), "%s: %d NaN in the output (the kernel read a position it must not read)" % (self.label, int(torch.isnan(outs[0]).sum()))
-        # nothing but the output slice has changed
+        self.assert_only_the_output_slice_changed(snap)
+        return self.check_values(outs[0], kernel, rows)
+
+    def out_slice(self):
+        return self.out_view()[..., self.out_coff:self.out_coff + self.Cout]
+
+    def assert_only_the_output_slice_changed(self, snap):
+        """nothing but the output slice has changed against the snapshot `snap` of the arena"""
         after = self.arena.mem.clone()
         a, b = _span(self.arena, 3)
         av, sv = after[a:b].view(self.B, self.Ho, self.Wo, -1), snap[a:b].view(self.B, self.Ho, self.Wo, -1)
@@ -178,15 +185,17 @@ class Case:
         av[..., f * self.out_coff:f * (self.out_coff + self.Cout)] = sv[..., f * self.out_coff:f * (self.out_coff + self.Cout)]
         changed = int((bits(after) != bits(snap)).sum())
         assert changed == 0, "%s: %d fp16 positions outside the output slice were written" % (self.label, changed)
-        # the values
+
+    def check_values(self, out, kernel, rows=None, note=""):
+        """the values of one forward (a clone of the output slice) against float64 at the bar; prints the MARGIN line.  -> worst err / tol"""
         ref, absum, tol, K = self.reference(rows)
-        got = outs[0].reshape(self.M, self.Cout)
+        got = out.reshape(self.M, self.Cout)
         got = (got if rows is None else got[torch.from_numpy(rows).cuda()]).double().cpu().numpy()
         ratio = cr.worst_ratio(got, ref, tol)
         extra = ""
         if self.out_f32:
             extra = "   fp32-only bound: %.3g" % cr.worst_ratio(got, ref, cr.f32_bound(ref, absum, K, self.act))
-        print("\nMARGIN %-44s %-86s %.3f%s%s" % (kernel, self.label, ratio, extra, "" if rows is None else "   (%d of %d pixels)" % (len(rows), self.M)))
+        print("\nMARGIN %-44s %-86s %.3f%s%s%s" % (kernel, self.label, ratio, extra, "" if rows is None else "   (%d of %d pixels)" % (len(rows), self.M), note))
         assert ratio <= 1.0, "%s: worst err / tol %.3g" % (self.label, ratio)
         SEEN.add(kernel)
         return ratio
@@ -283,8 +292,8 @@ def test_p8_upsample_on_read(L, ncu, up, form):
 
 
 # ------------------------------------------------------------------------------------------------ 3. tile-counter forms
-def _dyn_case(L, ncu, kernel, which, korder, s, Cin, Cout, TH, TW, n_nt, act):
-    """TH x TW OUTPUT tiles, 2 tiles per chunk, grid = min(chunks * n_nt, ncu) workgroups of which grid / n_nt share a counter: chunks 0 and 1 of a workgroup are
+def dyn_case(L, ncu, which, korder, s, Cin, Cout, TH, TW, n_nt, act):
+    """-> (Case, rows to compare).  TH x TW OUTPUT tiles, 2 tiles per chunk, grid = min(chunks * n_nt, ncu) workgroups of which grid / n_nt share a counter: chunks 0 and 1 of a workgroup are
     static, every later one comes from the counter"""
     assert ncu % 4 == 0
     wgs = ncu // n_nt                                                               # workgroups per counter on a full grid
@@ -303,7 +312,17 @@ def _dyn_case(L, ncu, kernel, which, korder, s, Cin, Cout, TH, TW, n_nt, act):
     H, W = ty * TH * s, tx * TW * s
     c = Case(L, "%s: %d tiles, %d chunks, %d workgroups per counter; B %d %dx%d act %d" % (which, tiles, chunks, grid_c, B, H, W, act), B, H, W, Cin, Cout, 3, s, act, korder,
              in_ld=Cin + 64, in_coff=64, out_ld=Cout + 128, out_coff=128)
-    c.run(kernel, some_rows(c, TH * TW * 2, 0.03))
+    return c, some_rows(c, TH * TW * 2, 0.03)
+
+
+def _dyn_case(L, ncu, kernel, which, korder, s, Cin, Cout, TH, TW, n_nt, act):
+    c, rows = dyn_case(L, ncu, which, korder, s, Cin, Cout, TH, TW, n_nt, act)
+    c.run(kernel, rows)
+
+
+# the three tile-counter kernels of _dyn_case: kernel -> (korder, stride, Cin, Cout, TH, TW, counters, activation of regime i)
+DYN_FORMS = {"ws64<16,16> dyn": (WL.WS64, 1, 64, 64, 16, 16, 1, lambda i: i), "ws128<4,16> dyn": (WL.WS128, 1, 128, 256, 4, 16, 2, lambda i: i),
+             "ws128_s2<2,16> dyn": (WL.WS128, 2, 128, 256, 2, 16, 2, lambda i: (i + 1) % 3)}
 
 
 DYN_WHICH = ["fewer chunks than workgroups", "exactly 2 chunks per workgroup", "more chunks, odd tile count"]
@@ -324,28 +343,40 @@ def test_ws128_stride2_on_two_tile_counters(L, ncu, which, act):
     _dyn_case(L, ncu, "ws128_s2<2,16> dyn", which, WL.WS128, 2, 128, 256, 2, 16, 2, (act + 1) % 3)
 
 
-@pytest.mark.parametrize("Cin,Cout,form", [(128, 256, "persistent"), (128, 768, "persistent"), (192, 768, "one tile per workgroup")],
-                         ids=["one channel tile", "three channel tiles", "odd Cin / 64 stays on one tile per workgroup"])
-def test_p8_in_a_plan(L, ncu, Cin, Cout, form):
+def p8_plan_case(L, ncu, Cin, Cout, form):
+    """-> (Case, rows to compare)"""
     ntn = Cout // 256
     tm = -(-2 * (ncu // ntn * ntn) // ntn)                                            # pixel tiles for grid >= 2 * gp_
     B = -(-((tm - 1) * 256 + 1) // 77)                                                # 7 x 11 maps
     assert p8_form(B * 77, Cin, Cout, ncu) == form and (B * 77) % 256 != 0             # ... and a ragged last pixel tile
     c = Case(L, "p8 %s: %d pixel tiles x %d channel tiles on %d CUs, %d -> %d" % (form, -(-B * 77 // 256), ntn, ncu, Cin, Cout), B, 7, 11, Cin, Cout, 1, 1, 1 + (ntn == 1), WL.P8,
              in_ld=Cin + 64, in_coff=64, out_ld=Cout + 64, out_coff=32 if ntn == 1 else 0)
-    c.run("p8<256,256,64> 1x1", cr.pixel_rows(1, c.M, 1, 256, 7, 0.02))
+    return c, cr.pixel_rows(1, c.M, 1, 256, 7, 0.02)
+
+
+@pytest.mark.parametrize("Cin,Cout,form", [(128, 256, "persistent"), (128, 768, "persistent"), (192, 768, "one tile per workgroup")],
+                         ids=["one channel tile", "three channel tiles", "odd Cin / 64 stays on one tile per workgroup"])
+def test_p8_in_a_plan(L, ncu, Cin, Cout, form):
+    c, rows = p8_plan_case(L, ncu, Cin, Cout, form)
+    c.run("p8<256,256,64> 1x1", rows)
 
 
 # ------------------------------------------------------------------------------------------------ 4. ws_s2 and its twin form in a plan
 @pytest.mark.parametrize("twin", [False, True], ids=["ws_s2", "ws_s2 + 1x1"])
 @pytest.mark.parametrize("which", ["one tile", "more tiles than workgroups"])
 def test_ws_s2_in_a_plan(L, ncu, which, twin):
+    c, rows = ws_s2_case(L, ncu, which, twin)
+    c.run("ws_s2<2,32> + 1x1" if twin else "ws_s2<2,32>", rows)
+
+
+def ws_s2_case(L, ncu, which, twin):
+    """-> (Case, rows to compare)"""
     B, H, W = (1, 4, 64) if which == "one tile" else (3, 4 * next(n for n in range(1, 999, 2) if 3 * 3 * n > ncu), 192)      # 2 x 32 output tiles: 3 per row, an odd number
     tiles = B * (H // 4) * (W // 64)
     assert tiles == 1 or tiles > ncu
     c = Case(L, "%s: %d tiles on %d CUs, B %d %dx%d" % (which, tiles, ncu, B, H, W), B, H, W, 64, 128, 3, 2, 1 + (which == "one tile"), WL.WS_S2_TWIN if twin else WL.WS_S2,
              in_ld=128, in_coff=64, out_ld=256, out_coff=128, twin=twin)
-    c.run("ws_s2<2,32> + 1x1" if twin else "ws_s2<2,32>", some_rows(c, 64, 0.1))
+    return c, some_rows(c, 64, 0.1)
 
 
 # ------------------------------------------------------------------------------------------------ 5. the patch family

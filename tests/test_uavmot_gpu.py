@@ -96,7 +96,8 @@ def test_uavmot_batch_mixed_with_shared_id_counter_equals_single_runs(threads):
             _lib.check(L.y7t_tracker_init(_lib.ptr(st[s]), nbytes, kinds[s], 0, cap, cap, 0.2, 0.5, 30, 1, _lib.ptr(ids[s]), _lib.stream_ptr()))
         return st
     outs = torch.zeros((nseq, cap + 1, 8), dtype=torch.float64, device="cuda")
-    st = mk([torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(nseq)])
+    own_ids = [torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(nseq)]      # one id counter per pool; the states keep their ADDRESSES: the tensors live as long as the states
+    st = mk(own_ids)
     single = [[] for _ in range(nseq)]
     for f in range(nfr):
         for s in range(nseq):

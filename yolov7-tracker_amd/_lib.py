@@ -106,6 +106,7 @@ SIGNATURES = {
     "y7t_det_destroy": (c_int, [c_void_p]),
     "y7t_det_forward": (c_int, [c_void_p, c_int, c_void_p]),
     "y7t_det_num_ops": (c_int, [c_void_p]),
+    "y7t_det_tile_counters": (c_int, [c_void_p, c_int, c_void_p]),
     "y7t_det_forward_ops": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "y7t_det_set_detect": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "y7t_det_forward_fused": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),

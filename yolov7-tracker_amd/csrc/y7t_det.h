@@ -116,4 +116,9 @@ struct Y7TPostWs {
     size_t total;
 };
 Y7TPostWs y7t_post_ws(void* base, int B, int cap, int max_nms);
+// Zero the B candidate counters of a workspace on `s`: a KERNEL, not hipMemsetAsync.  Every chain that fills the candidate arrays starts with this, and the chains are
+// captured into hipGraphs (Detector.capture).  As a memset node the zeroing did not survive replays: the second replay of a two-node graph (memset, Detect conv) wrote a
+// repeating 16-byte pattern of stale words over the counters instead of zeros (tests/graph_replay_gpu_cases.py::test_fused_detect_epilogue_replayed; negative counters
+// then index the candidate arrays out of bounds).  A kernel node carries its arguments by value and replays as recorded.
+int y7t_zero_counters(int* count, int B, hipStream_t s);
 int y7t_post_run(const Y7TPostArgs& a, hipStream_t s);

@@ -86,6 +86,12 @@ extern "C" int y7t_det_destroy(y7t_det* d) {
 
 extern "C" int y7t_det_num_ops(const y7t_det* d) { return d ? (int)d->ops.size() : Y7T_E_ARG; }
 
+extern "C" int y7t_det_tile_counters(const y7t_det* d, int op, int* out_host) {
+    Y7T_ARG_CHECK(d && out_host && op >= 0 && op < (int)d->ops.size());
+    Y7T_HIP_CHECK(hipMemcpy(out_host, d->tile_ctr + Y7T_TILE_CTR_INTS * op, sizeof(int) * Y7T_TILE_CTR_INTS, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int y7t_det_forward(y7t_det* d, int B, y7t_stream stream) { return y7t_det_forward_ops(d, B, 0, -1, stream); }
 
 static int forward_impl(y7t_det* d, int B, int first, int last, const Y7TCand* fused, hipStream_t s) {
@@ -227,7 +233,7 @@ extern "C" int y7t_det_forward_fused(y7t_det* d, int B, int first, int last, flo
     Y7T_ARG_CHECK(ws_bytes >= w.total);
     Y7TCand f = w.cand;
     f.conf_thres = conf_thres;
-    if (first == 0) Y7T_HIP_CHECK(hipMemsetAsync(f.count, 0, sizeof(int) * B, (hipStream_t)stream));
+    if (first == 0) { if (int rc = y7t_zero_counters(f.count, B, (hipStream_t)stream)) return rc; }      // (a kernel, not a memset node: y7t_det.h)
     return forward_impl(d, B, first, last, &f, (hipStream_t)stream);
 }
 

@@ -731,6 +731,17 @@ Y7TPostWs y7t_post_ws(void* base, int B, int cap, int max_nms) {
     return w;
 }
 
+__global__ void __launch_bounds__(256) k_zero_counters(int* __restrict__ count, int B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) count[i] = 0;
+}
+
+int y7t_zero_counters(int* count, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_zero_counters, dim3((B + 255) / 256), dim3(256), 0, s, count, B);
+    Y7T_LAUNCH_CHECK();
+    return 0;
+}
+
 Y7TLevel y7t_level(int l, int na, const int* ny, const int* nx, const float* stride, const float* anchors) {
     Y7TLevel L;
     memset(&L, 0, sizeof(L));
@@ -750,7 +761,7 @@ int y7t_post_run(const Y7TPostArgs& a, hipStream_t s) {
     const Y7TPostWs w = y7t_post_ws(a.ws, B, cap, a.max_nms);
     const Y7TCand& c = w.cand;
     if (w.total > a.ws_bytes) { y7t_set_error("postprocess workspace too small (%zu < %zu)", a.ws_bytes, w.total); return Y7T_E_ARG; }
-    if (!a.predecoded) Y7T_HIP_CHECK(hipMemsetAsync(c.count, 0, sizeof(int) * B, s));
+    if (!a.predecoded) { if (int rc = y7t_zero_counters(c.count, B, s)) return rc; }
     Y7T_HIP_CHECK(hipMemcpyAsync(w.lb, a.letterbox_dev, sizeof(float) * 5 * B, hipMemcpyDeviceToDevice, s));
     DecodeArgs d;
     memset(&d, 0, sizeof(d));

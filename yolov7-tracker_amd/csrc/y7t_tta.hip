@@ -101,7 +101,7 @@ extern "C" int y7t_det_decode_append(const float* const* head, const int* ny, co
     const hipStream_t s = (hipStream_t)stream;
     const Y7TPostWs w = y7t_post_ws(workspace, B, cap, max_nms);
     if (w.total > workspace_bytes) { y7t_set_error("decode_append: workspace too small (%zu < %zu)", workspace_bytes, w.total); return Y7T_E_ARG; }
-    if (first_pass) Y7T_HIP_CHECK(hipMemsetAsync(w.cand.count, 0, sizeof(int) * B, s));
+    if (first_pass) { if (int rc = y7t_zero_counters(w.cand.count, B, s)) return rc; }
     AppendArgs a;
     memset(&a, 0, sizeof(a));
     a.na = na; a.no = no; a.B = B; a.c = w.cand; a.c.conf_thres = conf_thres;

@@ -593,24 +593,34 @@ class Detector:
             _lib.check(self._L.y7t_det_postprocess_ex(*args, ctypes.byref(opts)))
         return a.dets, a.ndets
 
-    def postprocess(self, out, conf_thres=0.01, iou_thres=0.45, ori_shapes=None, classes=None, agnostic=False, multi_label=False):
-        """decode + NMS + scale_coords + round on the device.  ori_shapes: list of (H0, W0) per image (None: no rescale).
-        classes / agnostic / multi_label: as in non_max_suppression (utils/general.py:607); multi_label needs a forward without fuse_decode.
-        An AugmentedOutput (forward_augment) is post-processed on its own set: one NMS over the union of its passes, conf_thres as in the forward, no multi_label.
-        -> (dets (B, 300, 6) float32 device tensor, ndets (B,) int32 device tensor); asynchronous."""
-        if isinstance(out, AugmentedOutput):
-            return self._postprocess_aug(out, conf_thres, iou_thres, ori_shapes, classes, agnostic, multi_label)
-        p, B = self.plan, out.B
-        H, W = out.img_shape
+    @staticmethod
+    def _letterbox_rows(B, img_shape, ori_shapes):
+        """(B, 5) float32 rows (gain, pad x, pad y, h0, w0) of scale_coords (utils/general.py:319-340) for images of `img_shape` letterboxed from `ori_shapes`"""
+        H, W = img_shape
         lb = np.zeros((B, 5), np.float32)
         for b in range(B):
             h0, w0 = (H, W) if ori_shapes is None else ori_shapes[b][:2]
             gain = min(H / h0, W / w0)
             lb[b] = (gain, (W - w0 * gain) / 2, (H - h0 * gain) / 2, h0, w0)
-        key = lb.tobytes()
-        if getattr(p, "_lb_key", None) != key:
-            p.lb[:B].copy_(torch.from_numpy(lb))
-            p._lb_key = key
+        return lb
+
+    def postprocess(self, out, conf_thres=0.01, iou_thres=0.45, ori_shapes=None, classes=None, agnostic=False, multi_label=False, letterbox=None):
+        """decode + NMS + scale_coords + round on the device.  ori_shapes: list of (H0, W0) per image (None: no rescale).
+        classes / agnostic / multi_label: as in non_max_suppression (utils/general.py:607); multi_label needs a forward without fuse_decode.
+        An AugmentedOutput (forward_augment) is post-processed on its own set: one NMS over the union of its passes, conf_thres as in the forward, no multi_label.
+        letterbox: a (B, 5) float32 device tensor of `_letterbox_rows` that the caller owns, read instead of the plan's shared one (`ori_shapes` is then not looked at,
+        nothing is uploaded): what `capture` bakes into its graph.
+        -> (dets (B, 300, 6) float32 device tensor, ndets (B,) int32 device tensor); asynchronous."""
+        if isinstance(out, AugmentedOutput):
+            return self._postprocess_aug(out, conf_thres, iou_thres, ori_shapes, classes, agnostic, multi_label)
+        p, B = self.plan, out.B
+        if letterbox is None:
+            lb = self._letterbox_rows(B, out.img_shape, ori_shapes)
+            key = lb.tobytes()
+            if getattr(p, "_lb_key", None) != key:
+                p.lb[:B].copy_(torch.from_numpy(lb))
+                p._lb_key = key
+            letterbox = p.lb
         ps = p.post[out.pset]
         ps.last_B = B                    # the workspace arrays are laid out for THIS batch (y7t_post_ws): candidate_arrays needs it
         if out.fused is not None:
@@ -625,7 +635,7 @@ class Detector:
             head_ptrs = out.staged[1] if getattr(out, "staged", None) is not None else p.head_ptrs
         opts = _lib.nms_opts(classes, agnostic, multi_label)
         args = (head_ptrs, p.ny, p.nx, p.strides, p.anchors, len(p.heads), p.det["na"], p.det["no"], B, float(conf_thres), float(iou_thres), MAX_DET, MAX_NMS,
-                self.max_cand, _lib.ptr(p.lb), _lib.ptr(ps.dets), _lib.ptr(ps.ndets), _lib.ptr(ps.keep), _lib.ptr(ps.cand), _lib.ptr(ps.ws), ps.ws.numel(),
+                self.max_cand, _lib.ptr(letterbox), _lib.ptr(ps.dets), _lib.ptr(ps.ndets), _lib.ptr(ps.keep), _lib.ptr(ps.cand), _lib.ptr(ps.ws), ps.ws.numel(),
                 _lib.stream_ptr())
         if opts is None:
             _lib.check(self._L.y7t_det_postprocess(*args))
@@ -662,14 +672,26 @@ class Detector:
         """Capture input layout + the whole conv launch list + decode/NMS for the (fixed) device buffer `img` into a
         hipGraph (torch.cuda.CUDAGraph drives the capture; every launch of liby7t.so goes to the capturing stream, and
         nothing in the list allocates or synchronises).  Returns (graph, dets, ndets): `graph.replay()` re-runs the chain
-        on whatever `img` holds, with no per-launch host cost."""
-        out = self.forward(img, fuse_decode=conf_thres)   # warm-up: plan selection, attribute setup, letterbox upload
-        self.postprocess(out, conf_thres, iou_thres, ori_shapes)
+        on whatever `img` holds, with no per-launch host cost.
+
+        What the graph bakes in, and who owns it.  OWNED by the graph: a letterbox tensor of its own, filled here from `ori_shapes` (kept alive as
+        `graph.letterbox`) -- an eager `postprocess` with other `ori_shapes` uploads into the plan's shared letterbox tensor and cannot change what a live graph
+        rescales with.  SHARED with eager work on the same plan, by pointer: `img` (the caller writes the next frame into it), the arena, the weights, the plan's
+        tile counters and split-K slabs, and post-processing set 0 -- its workspace (candidate arrays and counters, zeroed by a kernel node of the graph), `keep`,
+        `cand`, and the returned `dets` / `ndets`, which ARE `plan.post[0].dets` / `.ndets`: an eager `postprocess` of a pset-0 output overwrites them (copy what is
+        still needed first), and the next replay overwrites them again.  Eager forwards between replays are fine (one forward of a detector at a time: the caller
+        orders replays and eager work, e.g. on one stream); post-processing set 1 is untouched by a replay.  The graph is valid while the plan lives: delete it
+        before the detector, and never replay it after its plan has been dropped (`evaluate(max_plans=...)`).
+        tests/graph_replay_gpu_cases.py pins every replay against an eager run; DESIGN.md section 2 lists the state a replay relies on."""
+        out = self.forward(img, fuse_decode=conf_thres)   # warm-up: plan selection, attribute setup
+        lb = torch.from_numpy(self._letterbox_rows(out.B, out.img_shape, ori_shapes)).cuda()
+        self.postprocess(out, conf_thres, iou_thres, letterbox=lb)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             out = self.forward(img, fuse_decode=conf_thres)
-            dets, nd = self.postprocess(out, conf_thres, iou_thres, ori_shapes)
+            dets, nd = self.postprocess(out, conf_thres, iou_thres, letterbox=lb)
+        g.letterbox = lb
         return g, dets, nd
 
     def check_overflow(self):
