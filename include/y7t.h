@@ -368,6 +368,38 @@ int y7t_gsi_interpolate(void* obj, const double* runs, const int* offsets, int n
 int y7t_gsi_smooth(void* obj, const double* runs, const int* offsets, const double* len_scale, int n_tracks, int longest, double reg, double* out,
                    int* status_out, y7t_stream stream);
 
+/* Annotated frames, tracker/track.py:176-177, 275-340 (plot_img, save_videos; --save_images / --save_videos): the overlay and a baseline JPEG encoder for what
+ * it returns, both on the device (DESIGN.md section 4 "Rendering" is the specification; csrc/y7t_render.h states the arithmetic).  Integer arithmetic decides
+ * every pixel and every bit, no global atomics: results are bit-identical from call to call and a frame's do not depend on the rest of the batch.
+ *
+ * y7t_render_draw: frames (B, H, W, 3) uint8 BGR -> out, the same shape (another buffer; the frames are not modified).  `tracks`: the rows of all frames, frame b's
+ *   rows [offsets[b], offsets[b + 1]) (offsets: B + 1 int32); a row is y7t_render_track: the box as tlwh, the id (the colour: get_color of track.py:311-316) and
+ *   the label the host assembled.  A track draws the 3-pixel outline of the rectangle int(x), int(y), int(x + w), int(y + h) in its colour, then its label in
+ *   (255, 164, 0) with this project's 8 x 12 bitmap font (csrc/y7t_font.h), the baseline at the rectangle's first corner; the tracks draw in row order and a pixel
+ *   keeps the last primitive that covers it.  Not cv2's rasteriser and not its Hershey glyphs.  frames, out and tracks are 4-byte aligned; H, W, B <= 65535.
+ * The JPEG ENCODER is caller-owned device memory of y7t_jpeg_bytes(H, W, subsampling, max_batch, &out_bytes) bytes at a 256-byte aligned address (0: sizes out of
+ *   range or a batch whose image could pass 2 GiB); out_bytes = the bytes the `out` buffer of a batch of max_batch frames must have: every MCU row has a slot for
+ *   its longest possible code, so nothing can overflow.  y7t_jpeg_init writes the tables and the file header for (quality 1 .. 100, subsampling); y7t_jpeg_release:
+ *   the object's memory is about to be freed.
+ * y7t_jpeg_encode: frames (B, H, W, 3) uint8 BGR, B <= max_batch -> out: the B files one after the other, file b = bytes [lens[b], lens[b + 1]) (lens: B + 1 int32,
+ *   device).  Sequential baseline DCT, 8 bit, YCbCr, JFIF APP0, the Annex K Huffman tables, the Annex K quantisation tables scaled the IJG way, a restart interval of
+ *   one MCU row (DRI, RST0 .. 7 between the rows), frames padded to whole MCUs by edge replication.  Three launches, no read-back, asynchronous.
+ * Errors: Y7T_E_ARG (a null or misaligned pointer, sizes out of range, a buffer too small), Y7T_E_STATE (an address y7t_jpeg_init never saw), Y7T_E_CAPACITY
+ * (B > max_batch). */
+enum { Y7T_JPEG_SUB_420 = 0, Y7T_JPEG_SUB_444 = 1 };
+#define Y7T_RENDER_LABEL_BYTES 24
+typedef struct y7t_render_track {
+    float x, y, w, h;                                   /* tlwh */
+    int32_t id;
+    int32_t len;                                        /* bytes of the label, 0 .. 24 */
+    unsigned char label[Y7T_RENDER_LABEL_BYTES];        /* CATEGORY_DICT[cls] + '-' + str(id), printable ASCII */
+} y7t_render_track;                                     /* sizeof == 48 */
+int y7t_render_draw(const uint8_t* frames, int B, int H, int W, const void* tracks, const int* offsets, uint8_t* out, y7t_stream stream);
+size_t y7t_jpeg_bytes(int H, int W, int subsampling, int max_batch, size_t* out_bytes_host);
+int y7t_jpeg_init(void* obj, size_t bytes, int H, int W, int quality, int subsampling, int max_batch, y7t_stream stream);
+int y7t_jpeg_release(void* obj);
+int y7t_jpeg_encode(void* obj, const uint8_t* frames, int B, uint8_t* out, size_t out_bytes, int* lens, y7t_stream stream);
+
 /* mAP evaluation of the detector, as the reference's test.py grades a checkpoint: the per-image statistics of test.py:126-209 and ap_per_class / compute_ap of
  * utils/metrics.py:18-106 (DESIGN.md section 4 "mAP evaluation").  No prediction row reaches the host; no atomics; the stored rows do not depend on how the images
  * were split into calls, and two computes over one state give the same bits.

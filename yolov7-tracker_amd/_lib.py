@@ -83,6 +83,11 @@ SIGNATURES = {
     "y7t_gsi_release": (c_int, [c_void_p]),
     "y7t_gsi_interpolate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "y7t_gsi_smooth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "y7t_render_draw": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "y7t_jpeg_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_void_p]),
+    "y7t_jpeg_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "y7t_jpeg_release": (c_int, [c_void_p]),
+    "y7t_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "y7t_map_bytes": (c_size_t, [c_int, c_int]),
     "y7t_map_layout": (c_int, [c_int, c_int, c_void_p]),
     "y7t_map_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p]),

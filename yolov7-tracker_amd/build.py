@@ -38,7 +38,9 @@ _CONV = ["-ffp-contract=fast", "-fno-slp-vectorize"]
 # instructions and resource numbers (profiles/conv_forms_margins.txt)
 _CONV_IGEMM = ["-ffp-contract=fast-honor-pragmas", "-fno-slp-vectorize"]
 FILE_FLAGS = {"y7t_conv.hip": _CONV_IGEMM, "y7t_conv_patch.hip": _CONV, "y7t_conv_patch_s2.hip": _CONV, "y7t_stem.hip": ["-fno-slp-vectorize"],
-              "y7t_conv_ws.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_ws128.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_p8.hip": _CONV, "y7t_conv_ws_s2.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_post.hip": []}
+              "y7t_conv_ws.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_ws128.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_p8.hip": _CONV, "y7t_conv_ws_s2.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_post.hip": [],
+              # k_jpeg_blocks keeps a block's 64 samples in registers only when its loops are unrolled whole (272 bytes of scratch a lane otherwise)
+              "y7t_render.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"]}
 
 
 def _sources():

@@ -11,6 +11,8 @@ Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / 
 --augment (the detector's three-pass test-time augmentation, as detect.py --augment; default off).
 --reid_half (an OSNet --reid_model_path through the general fp16 / MFMA op list: any width, the IBN variant, any crop size; default off).
 --botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
+--save_images / --save_videos (the reference's flags): the overlay and the JPEG encoding run on the device (tracker/render.py); the video is a Motion-JPEG AVI of the
+very same JPEG files, not the reference's mp4v.
 """
 import argparse
 import os
@@ -140,6 +142,9 @@ def main(opts, cfgs):
             else:
                 tracker.gmc = estimator.apply_device
         results, frame_id, i = [], 0, -1
+        if opts.save_images:      # track.py:176-177: <DATASET_ROOT>/result_images/<seq>/; the synthetic dataset has no root of its own and writes beside its results
+            image_dir = os.path.join(os.path.join(opts.results_root, folder_name) if synthetic else DATASET_ROOT, 'result_images', seq)
+            jpeg_files = []
         for imgs, imgs0 in data_loader:
             # --batch N (extension, default 1 = the reference's frame-at-a-time loop): the detector + decode/NMS run once over N
             # consecutive frames (that is where the throughput of bench.py comes from), the tracker then takes them in order
@@ -181,6 +186,11 @@ def main(opts, cfgs):
                 results.append((frame_id + 1, cur_id, cur_tlwh, cur_cls))
                 timer.toc()
                 frame_id += 1
+            if opts.save_images:      # outside the timed region, like plot_img: the batch's frames (uploaded once if they came on the host) with the rows just recorded
+                from . import render
+                renderer = _renderer_for(imgs0.shape[1], imgs0.shape[2], max(1, opts.batch))
+                rows = [render.tracks_from_results(ids, tlwhs, clses, cfgs.get('CATEGORY_DICT')) for _, ids, tlwhs, clses in results[-nb:]]
+                jpeg_files += renderer.save(imgs0, rows, [os.path.join(image_dir, f'{fid - 1:05d}.jpg') for fid, _, _, _ in results[-nb:]])
         seq_fps.append(i / timer.total_time)   # track.py:181 (sic: last index, not the frame count)
         timer.clear()
         if aflink_weights is not None:      # (extension) --aflink: the rows that would have been written, linked; the file and TrackEval see the linked ids
@@ -190,10 +200,26 @@ def main(opts, cfgs):
             from . import gsi
             results = gsi.smooth_results(results, interval=opts.gsi_interval, tau=opts.gsi_tau)
         save_results(opts.results_root, folder_name, seq, results)
+        if opts.save_images and opts.save_videos and jpeg_files:      # track.py:190-191; the chunks are the .jpg files' bytes, nothing is encoded again
+            from . import render
+            render.write_mjpeg_avi(os.path.join(os.path.dirname(image_dir), seq + '.avi'), jpeg_files, (imgs0.shape[2], imgs0.shape[1]), fps=15)
     print(f'average fps: {np.mean(seq_fps)}')
     if opts.track_eval and (synthetic or cfgs.get('TRACK_EVAL')):
         evaluate_results(opts, cfgs, seqs, folder_name, synthetic)
     return os.path.join(opts.results_root, folder_name)
+
+
+_renderers = {}
+
+
+def _renderer_for(H, W, batch):
+    """one DeviceRenderer per frame size (a sequence's frames share one); its encoder takes at most 8 frames at a time, longer batches go in parts"""
+    key = (int(H), int(W), min(int(batch), 8))
+    if key not in _renderers:
+        from .render import DeviceRenderer
+        _renderers.clear()      # (the encoder's row slots are sized for the worst case: keep one size alive)
+        _renderers[key] = DeviceRenderer(key[0], key[1], max_batch=key[2])
+    return _renderers[key]
 
 
 def evaluate_results(opts, cfgs, seqs, folder_name, synthetic):
@@ -260,8 +286,12 @@ def build_parser():
                         help="(extension) 1 = the reference's applyEcc as written (every frame aligned to frame 0, half-resolution translation); "
                              "0 = previous-frame template, full-resolution translation")
     parser.add_argument('--min_area', type=float, default=150, help='use to filter small bboxs')
-    parser.add_argument('--save_images', action='store_true', help='save tracking results (image)')
-    parser.add_argument('--save_videos', action='store_true', help='save tracking results (video)')
+    parser.add_argument('--save_images', action='store_true',
+                        help="save tracking results (image): <frame_id:05d>.jpg under <DATASET_ROOT>/result_images/<seq>/ (--dataset synthetic: under "
+                             "<results_root>/<folder>/result_images/<seq>/); drawn and JPEG-encoded on the device with this project's outline rule and bitmap font")
+    parser.add_argument('--save_videos', action='store_true',
+                        help="save tracking results (video), together with --save_images: <seq>.avi beside the image folder, a Motion-JPEG AVI at 15 fps made of the "
+                             "same JPEG files -- NOT the reference's mp4v container, which needs a codec library")
     parser.add_argument('--detect_per_frame', type=int, default=1, help='choose how many frames per detect')
     parser.add_argument('--track_eval', type=bool, default=True, help='Use TrackEval to evaluate')
     # additions (defaults keep the reference's behaviour)
