@@ -400,6 +400,41 @@ int y7t_jpeg_init(void* obj, size_t bytes, int H, int W, int quality, int subsam
 int y7t_jpeg_release(void* obj);
 int y7t_jpeg_encode(void* obj, const uint8_t* frames, int B, uint8_t* out, size_t out_bytes, int* lens, y7t_stream stream);
 
+/* Frames from JPEG files, tracker/tracker_dataloader.py:94-104 (the loader's cv2.imread): a baseline JPEG DECODER on the device, the encoder's mirror (DESIGN.md
+ * section 4 "JPEG decoding" is the specification; csrc/y7t_jpegdec.h states the arithmetic).  The frame is, byte for byte, what libjpeg-turbo returns with its
+ * defaults (the accurate integer inverse DCT, "fancy" chroma upsampling, YCbCr -> RGB), stored as B, G, R.  A call takes B files of ONE geometry (H, W,
+ * components, sampling); integer arithmetic decides every bit, no atomics, no read-back, bit-identical from call to call, a file's frame independent of the batch.
+ * The DECODER is caller-owned device memory of y7t_jpegdec_bytes(...) bytes at a 256-byte aligned address (0: arguments out of range): H, W <=
+ *   Y7T_JPEGDEC_MAX_SIDE; components 3 with Y7T_JPEGDEC_444 / _422 / _420 (luminance 1x1, 2x1, 2x2 over chrominance 1x1) or 1 with Y7T_JPEGDEC_GRAY; max_file_bytes
+ *   <= 2^28: the longest file a call may hold; subseq_bytes: the stuffed bytes of the scan a lane decodes, a multiple of 4 in Y7T_JPEGDEC_SUBSEQ_MIN .. 4096, 0 =
+ *   Y7T_JPEGDEC_SUBSEQ_DEFAULT.  y7t_jpegdec_release: the object's memory is about to be freed.
+ * y7t_jpegdec_decode: files (device): the B files' bytes, file b at descs[b].file_off; descs (HOST, copied before the call returns): what a parser of the markers
+ *   found, see y7t_jpegdec_desc (tracker/jpeg_decode.py: parse); frames (device, 4-byte aligned) <- (B, H, W, 3) uint8 BGR; status (device, B int32) <- 0, or
+ *   Y7T_JPEGDEC_E_* bits for a file whose scan is malformed: its frame then holds the blocks that were decoded before and after the damage, mid-grey where none
+ *   was, and no other file of the batch is affected.  Every read of a file is clamped to its bytes and every index to its array: no input can make a kernel read
+ *   or write elsewhere.  After a call the int32 at byte 256 + 4 * b of the object is the last launch of the synchronisation that found work for file b, plus one.
+ *   Launches: the runs of the batch's longest scan (of 256 * subseq_bytes bytes each: those that find their run settled return at once) + 4; asynchronous.
+ * Errors: Y7T_E_ARG (a null or misaligned pointer, sizes out of range, a record that points outside its file), Y7T_E_STATE (an address y7t_jpegdec_init never
+ * saw), Y7T_E_CAPACITY (B > max_batch, a file longer than max_file_bytes); none of them launches anything. */
+enum { Y7T_JPEGDEC_444 = 0, Y7T_JPEGDEC_422 = 1, Y7T_JPEGDEC_420 = 2, Y7T_JPEGDEC_GRAY = 3 };
+enum { Y7T_JPEGDEC_E_CODE = 1, Y7T_JPEGDEC_E_TRUNC = 2, Y7T_JPEGDEC_E_COUNT = 4, Y7T_JPEGDEC_E_RANGE = 8, Y7T_JPEGDEC_E_RESTART = 16 };
+#define Y7T_JPEGDEC_MAX_SIDE 16384
+#define Y7T_JPEGDEC_SUBSEQ_MIN 16
+#define Y7T_JPEGDEC_SUBSEQ_DEFAULT 64
+typedef struct y7t_jpegdec_desc {
+    uint32_t file_off, file_len;          /* the file inside `files`; every other offset counts from the file's first byte */
+    uint32_t scan_off, scan_len;          /* the entropy-coded bytes: from behind the SOS header up to the marker that ends the scan */
+    uint32_t restart_interval;            /* DRI, in MCUs; 0: none */
+    uint32_t dqt_off[4];                  /* by table id: the 64 bytes of an 8-bit quantisation table (zig-zag order); 0: not defined */
+    uint32_t dc_off[4], ac_off[4];        /* by table id: a Huffman table's 16 BITS bytes, HUFFVAL behind them; 0: not defined */
+    uint8_t tq[4], td[4], ta[4];          /* by component (scan order): the ids of its quantisation, DC and AC table */
+} y7t_jpegdec_desc;                                     /* sizeof == 80 */
+size_t y7t_jpegdec_bytes(int H, int W, int components, int sampling, int max_batch, size_t max_file_bytes, int subseq_bytes);
+int y7t_jpegdec_init(void* obj, size_t bytes, int H, int W, int components, int sampling, int max_batch, size_t max_file_bytes, int subseq_bytes,
+                     y7t_stream stream);
+int y7t_jpegdec_release(void* obj);
+int y7t_jpegdec_decode(void* obj, const uint8_t* files, const y7t_jpegdec_desc* descs, int B, uint8_t* frames, int* status, y7t_stream stream);
+
 /* mAP evaluation of the detector, as the reference's test.py grades a checkpoint: the per-image statistics of test.py:126-209 and ap_per_class / compute_ap of
  * utils/metrics.py:18-106 (DESIGN.md section 4 "mAP evaluation").  No prediction row reaches the host; no atomics; the stored rows do not depend on how the images
  * were split into calls, and two computes over one state give the same bits.

@@ -88,6 +88,10 @@ SIGNATURES = {
     "y7t_jpeg_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "y7t_jpeg_release": (c_int, [c_void_p]),
     "y7t_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "y7t_jpegdec_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_size_t, c_int]),
+    "y7t_jpegdec_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int, c_void_p]),
+    "y7t_jpegdec_release": (c_int, [c_void_p]),
+    "y7t_jpegdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "y7t_map_bytes": (c_size_t, [c_int, c_int]),
     "y7t_map_layout": (c_int, [c_int, c_int, c_void_p]),
     "y7t_map_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p]),

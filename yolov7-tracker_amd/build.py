@@ -40,7 +40,9 @@ _CONV_IGEMM = ["-ffp-contract=fast-honor-pragmas", "-fno-slp-vectorize"]
 FILE_FLAGS = {"y7t_conv.hip": _CONV_IGEMM, "y7t_conv_patch.hip": _CONV, "y7t_conv_patch_s2.hip": _CONV, "y7t_stem.hip": ["-fno-slp-vectorize"],
               "y7t_conv_ws.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_ws128.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_conv_p8.hip": _CONV, "y7t_conv_ws_s2.hip": _CONV + ["-mllvm", "-pragma-unroll-threshold=10000000"], "y7t_post.hip": [],
               # k_jpeg_blocks keeps a block's 64 samples in registers only when its loops are unrolled whole (272 bytes of scratch a lane otherwise)
-              "y7t_render.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"]}
+              "y7t_render.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"],
+              # k_jd_pixels likewise: a block's 64 coefficients and samples stay in registers only when the inverse DCT's loops are unrolled whole
+              "y7t_jpegdec.hip": ["-mllvm", "-pragma-unroll-threshold=10000000"]}
 
 
 def _sources():

@@ -13,6 +13,8 @@ Extra flags (defaults reproduce the reference's behaviour): --model_cfg (yaml / 
 --botsort_reid (with --tracker botsort: its appearance branch, use_apperance_model, with --reid_model_path features; default off, as in the reference).
 --save_images / --save_videos (the reference's flags): the overlay and the JPEG encoding run on the device (tracker/render.py); the video is a Motion-JPEG AVI of the
 very same JPEG files, not the reference's mp4v.
+--device_decode (implies --device_preprocess): the loader hands over the JPEG files' bytes and the frames are decoded on the device (tracker/jpeg_decode.py); files
+the device decoder does not take (progressive, CMYK, PNG, ...) are decoded on the host as before, and a line per sequence says how many went each way.
 """
 import argparse
 import os
@@ -39,6 +41,7 @@ TRACKER_DICT = {'sort': BaseTracker, 'bytetrack': ByteTrack, 'botsort': BoTSORT,
 
 timer = Timer()
 seq_fps = []
+decode_counts = {}      # --device_decode: sequence -> {'device': frames decoded on the device, 'host': frames that fell back to the host}
 
 
 def post_process_v7(out, img_size, ori_img_size, conf_thres=0.01, all_images=False, classes=None, agnostic=False):
@@ -105,6 +108,11 @@ def main(opts, cfgs):
     if getattr(opts, 'aflink', None):
         from .aflink import load_aflink_weights
         aflink_weights = load_aflink_weights(opts.aflink)
+    device_decode = bool(getattr(opts, 'device_decode', False))
+    if device_decode:
+        if opts.dataset == 'synthetic':
+            raise ValueError("--device_decode decodes the files of a dataset: the synthetic sequences have none")
+        opts.device_preprocess = True      # the decoded frame is on the device already
     img_size = opts.img_size[0] if isinstance(opts.img_size, (list, tuple)) else opts.img_size
     model = attempt_load(opts.model_path, cfg=opts.model_cfg, nc=opts.nc, img_size=img_size, max_batch=max(1, opts.batch))
     stride = int(model.stride.max())
@@ -130,8 +138,9 @@ def main(opts, cfgs):
             loader = tracker_dataloader.TrackerLoader(path, opts.img_size, opts.data_format, seq,
                                                       pre_process_method='v7', model_stride=stride,
                                                       device_preprocess=opts.device_preprocess,
-                                                      yolo_data_root=cfgs.get('YOLO_DATA_ROOT', DATASET_ROOT))
-        data_loader = torch.utils.data.DataLoader(loader, batch_size=max(1, opts.batch))
+                                                      yolo_data_root=cfgs.get('YOLO_DATA_ROOT', DATASET_ROOT), device_decode=device_decode)
+        data_loader = torch.utils.data.DataLoader(loader, batch_size=max(1, opts.batch), **({'collate_fn': tracker_dataloader.collate_bytes} if device_decode else {}))
+        decoded = {'device': 0, 'host': 0}
         # (extension) --botsort_reid: BoTSORT's use_apperance_model, which the reference hard-codes to False (botsort.py:276)
         tracker = TRACKER_DICT[opts.tracker](opts, frame_rate=30, gamma=opts.gamma, **({'use_apperance_model': True} if botsort_reid else {}))
         if opts.gmc in ('ecc', 'features'):      # (extension) estimate the camera motion on the device; one estimator per sequence, like the reference's per-tracker GMC
@@ -148,6 +157,9 @@ def main(opts, cfgs):
         for imgs, imgs0 in data_loader:
             # --batch N (extension, default 1 = the reference's frame-at-a-time loop): the detector + decode/NMS run once over N
             # consecutive frames (that is where the throughput of bench.py comes from), the tracker then takes them in order
+            if device_decode:      # imgs0 is the list of the files' bytes: the frames come into being on the device (outside the timed region, like the loader's decode)
+                from . import jpeg_decode
+                imgs0 = jpeg_decode.decode_batch(imgs0, max_batch=max(1, opts.batch), counts=decoded)
             nb = imgs0.shape[0]
             timer.tic()
             detect = [not (i + 1 + k) % opts.detect_per_frame for k in range(nb)]
@@ -191,6 +203,9 @@ def main(opts, cfgs):
                 renderer = _renderer_for(imgs0.shape[1], imgs0.shape[2], max(1, opts.batch))
                 rows = [render.tracks_from_results(ids, tlwhs, clses, cfgs.get('CATEGORY_DICT')) for _, ids, tlwhs, clses in results[-nb:]]
                 jpeg_files += renderer.save(imgs0, rows, [os.path.join(image_dir, f'{fid - 1:05d}.jpg') for fid, _, _, _ in results[-nb:]])
+        if device_decode:
+            decode_counts[seq] = decoded
+            print(f"device_decode: {decoded['device']} frames decoded on the device, {decoded['host']} on the host (fallback)")
         seq_fps.append(i / timer.total_time)   # track.py:181 (sic: last index, not the frame count)
         timer.clear()
         if aflink_weights is not None:      # (extension) --aflink: the rows that would have been written, linked; the file and TrackEval see the linked ids
@@ -273,6 +288,9 @@ def build_parser():
     parser.add_argument('--kalman_format', type=str, default='default', help='use what kind of Kalman, default, naive, strongsort or bot-sort like')
     parser.add_argument('--batch', type=int, default=1, help='(extension) frames per detector forward; the tracker still steps frame by frame')
     parser.add_argument('--device_preprocess', action='store_true', help='(extension) letterbox raw frames on the GPU instead of in the loader')
+    parser.add_argument('--device_decode', action='store_true',
+                        help='(extension) decode the JPEG frames on the GPU from the files\' bytes (implies --device_preprocess); files the device decoder does not '
+                             'take are decoded on the host as before')
     parser.add_argument('--gmc', type=str, default='none', choices=['none', 'ecc', 'features'],
                         help='(extension) camera-motion estimate for strongsort / botsort on the device (tracker/gmc.py): ecc = findTransformECC, '
                              'features = FAST corners, rotated BRIEF, Hamming matching and RANSAC (the applyFeaures path the reference runs as orb)')

@@ -63,13 +63,14 @@ def _resize_linear(img, new_h, new_w):
 
 class TrackerLoader(torch.utils.data.Dataset):
     def __init__(self, path, img_size=1280, format='origin', seq=None, pre_process_method='v7', model_stride=32, device_preprocess=False,
-                 yolo_data_root=''):
+                 yolo_data_root='', device_decode=False):
         """tracker_dataloader.py:21-62.  format 'origin': `path` is one sequence's folder of frames.  format 'yolo': `path` is the path FILE (test.txt) whose lines
         are image paths relative to the data root; the frames of sequence `seq` are the lines whose parent folder name is contained in `seq` (the reference's
         `elems[-2] in seq`, :50).  The reference hard-codes its data root ('/data/wujiapeng/datasets/', :33); here it comes from the dataset yaml
         (YOLO_DATA_ROOT, default DATASET_ROOT)."""
         super().__init__()
         self.device_preprocess = device_preprocess   # True: hand over only the raw frame; letterbox runs on the GPU (Detector.forward_frames)
+        self.device_decode = device_decode           # True: hand over the FILE's bytes; the frame is decoded on the GPU too (tracker/jpeg_decode.py; collate_bytes)
         self.DATA_ROOT = yolo_data_root if format == 'yolo' else path
         self.format, self.pre_process_method, self.model_stride = format, pre_process_method, model_stride
         self.img_files = []
@@ -94,6 +95,9 @@ class TrackerLoader(torch.utils.data.Dataset):
     def __getitem__(self, index):
         from PIL import Image
         p = os.path.join(self.DATA_ROOT, self.img_files[index]) if self.format == 'origin' else self.img_files[index]
+        if self.device_decode:
+            with open(p, 'rb') as f:
+                return torch.empty(0), f.read()
         ori_img = np.asarray(Image.open(p).convert("RGB"))[:, :, ::-1].copy()   # (H, W, C) BGR like cv2.imread
         if self.device_preprocess:
             return torch.empty(0), torch.from_numpy(ori_img)
@@ -105,6 +109,11 @@ class TrackerLoader(torch.utils.data.Dataset):
 
     def __len__(self):
         return len(self.img_files)
+
+
+def collate_bytes(batch):
+    """the DataLoader collate of TrackerLoader(device_decode=True): the files' bytes stay a list (the default collate would turn a batch of them into one string)"""
+    return torch.empty(0), [b for _, b in batch]
 
 
 class SyntheticLoader(torch.utils.data.Dataset):
